@@ -233,6 +233,32 @@ PARITY_LIMITS = {
 }
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of each flat buffer by --dump-outputs (4 MB in float32; four buffers + the loss terms)
+
+
+def dump_outputs(out_dir, terms, model, opt):
+    """--dump-outputs: what a caller of the timed step receives from its last step, as float32 .npy files - the per-sample loss
+    terms ([B] each) and the updated flat parameter buffer, its gradient and the two EMA copies.  The flat buffers are sampled at
+    DUMP_SAMPLE fixed positions (CPU generator, seed 0: the same positions for the same model in every run) when they are larger."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {f"loss_{k}": v for k, v in terms.items()}
+    flats = {"params": model._pflat, "grads": model._gflat}
+    flats.update({f"ema_{s:g}": e for s, e in zip(opt.ema_stds, opt.ema)})
+    n = model._pflat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.numpy().astype(np.float64))
+        idx = idx.to(model._pflat.device)
+    for k, v in flats.items():
+        if v is not None:
+            arrays[k] = v if idx is None else v[idx]
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -263,6 +289,9 @@ def main():
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=10)          # ~10 s of host work at ~1 s per DiT-B/2 batch-8 step with the swept thread count
     ap.add_argument("--cpu-c1-steps", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): per-sample loss "
+                         "terms, and a fixed seeded sample of the updated parameters, their gradients and the two EMA copies")
     args = ap.parse_args()
 
     import torch.distributed as dist
@@ -295,8 +324,9 @@ def main():
                for f in mp_off), f"--mp-off: unknown flag in {mp_off}"
     unpinned = bool(args.rotation_modulation or mp_off)      # configurations with no reference code behind them
 
-    def timed_run(precision, steps, warmup):
-        """Builds the model in `precision`, runs `warmup` untimed + `steps` timed training steps; returns the measurements."""
+    def timed_run(precision, steps, warmup, dump_dir=None):
+        """Builds the model in `precision`, runs `warmup` untimed + `steps` timed training steps; returns the measurements.
+        With `dump_dir`, what the last timed step computed is written there afterwards (dump_outputs)."""
         parity = None
         if rank == 0 and not args.no_parity and not unpinned:
             parity = parity_leg(args.model, precision, dev)
@@ -322,12 +352,13 @@ def main():
             x = torch.randn(B, 4, 32, 32, device=dev, generator=g)              # a fresh batch every step
             y = torch.randint(0, 1000, (B,), device=dev, generator=g)
             t = torch.randint(0, diffusion.num_timesteps, (B,), device=dev)
-            loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
+            terms = diffusion.training_losses(model, x, t, dict(y=y))
+            loss = terms["loss"].mean()
             opt.zero_grad()
             loss.backward()
             reducer.finish()
             opt.step()
-            return loss
+            return loss, terms
 
         def fence():
             if world > 1:
@@ -345,7 +376,7 @@ def main():
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(steps):
-            loss = step()
+            loss, terms = step()
             marks[i + 1].record()                          # on the compute stream; no host synchronisation inside the region
         fence()
         elapsed = time.perf_counter() - t0
@@ -358,6 +389,8 @@ def main():
             elapsed = float(tmax.item())
         final_loss = float(loss.item())
         model.check_device_errors()
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, terms, model, opt)
         geo = dict(T=(model.input_size // model.patch_size) ** 2, D=model.hidden_size, Hm=model.blocks[0].mlp.hidden_dim,
                    P=model.patch_size ** 2 * model.in_channels, depth=model.depth)
         res = dict(parity=parity, elapsed=elapsed, per_step=per_step, fc1_count=cnt.value, fc1_ms=tot_ms.value, final_loss=final_loss,
@@ -366,7 +399,7 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    r = timed_run(args.precision, args.steps, args.warmup)
+    r = timed_run(args.precision, args.steps, args.warmup, args.dump_outputs)
     parity, elapsed, per_step, final_loss = r["parity"], r["elapsed"], r["per_step"], r["final_loss"]
     geo = r["geo"]
 
