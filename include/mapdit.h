@@ -437,6 +437,38 @@ int mapdit_ddim_step(const float* model_out, const float* x, const float* noise,
                      const float* dtab, int nsteps, int clip_denoised, float eta, int reverse, float* sample, float* pred_xstart,
                      int N, int per_sample, void* stream);
 
+/* Every objective create_diffusion() builds (abi 5).  mean_type: 0 EPSILON, 1 START_X; var_type: 0 LEARNED_RANGE, 1 FIXED_SMALL,
+ * 2 FIXED_LARGE; loss_type: 0 MSE, 1 RESCALED_MSE, 2 KL, 3 RESCALED_KL.  model_out holds 2C channels per sample for LEARNED_RANGE
+ * (mean | v) and C for the fixed variances.  `tab` is the 8-row table above; `otab` = fp32 [5][nsteps] of the (respaced) schedule:
+ * alphas_cumprod, alphas_cumprod_prev, alphas_cumprod_next, log(append(posterior_variance[1], betas[1:])) (FIXED_LARGE),
+ * log_one_minus_alphas_cumprod.  The default configuration keeps the entry points above. */
+/* training_losses (:715-787, 682-713).  MSE losses: mse, loss [N] and, with LEARNED_RANGE, vb [N] (x nsteps/1000 for RESCALED_MSE;
+ * the vb term sees the mean channels detached); noise may be null for START_X.  KL losses: loss [N] only (the bound term with
+ * clip_denoised = 0, x nsteps for RESCALED_KL), mse / vb / noise may be null.  G (model_out's shape) = d key / d model_out per
+ * channel group: mse (or the KL loss) on the mean channels, vb on the v channels. */
+int mapdit_obj_loss_fwd(const float* model_out, const float* x0, const float* xt, const float* noise, const int64_t* t,
+                        const float* tab, const float* otab, int nsteps, int mean_type, int var_type, int loss_type, float* mse,
+                        float* vb, float* loss, float* G, int N, int per_sample, void* stream);
+/* dout = G x (g_loss + g_mse) on the mean channels, G x (g_loss + g_vb) on the v channels; groups = 2 (LEARNED_RANGE) or 1. */
+int mapdit_obj_loss_bwd(const float* G, const float* g_loss, const float* g_mse, const float* g_vb, float* dout, int N,
+                        int per_sample, int groups, void* stream);
+/* p_mean_variance (:254-332) followed by mode 0: p_sample (:376-417; noise null -> the model mean), 1: ddim_sample (:513-567),
+ * 2: ddim_reverse_sample (:569-605, eta 0, noise unused).  pred_xstart may be null. */
+int mapdit_obj_step(const float* model_out, const float* x, const float* noise, const int64_t* t, const float* tab,
+                    const float* otab, int nsteps, int mean_type, int var_type, int clip_denoised, int mode, float eta,
+                    float* sample, float* pred_xstart, int N, int per_sample, void* stream);
+/* _vb_terms_bpd (:682-713) and calc_bpd_loop's per-timestep terms (:805-858): vb (bits; decoder NLL at t = 0, KL otherwise),
+ * xstart_mse and, when noise is given, mse of the eps re-derived from pred_xstart.  Each lands at [n * ld + (col_from_t ?
+ * nsteps - 1 - t[n] : 0)]: col_from_t = 1 with ld = nsteps fills the column of [N][nsteps] arrays that calc_bpd_loop's loop order
+ * (t = nsteps - 1 first) gives timestep t.  xstart_mse, mse, pred_xstart may be null. */
+int mapdit_obj_vb_terms(const float* model_out, const float* x0, const float* xt, const float* noise, const int64_t* t,
+                        const float* tab, const float* otab, int nsteps, int mean_type, int var_type, int clip_denoised, float* vb,
+                        float* xstart_mse, float* mse, float* pred_xstart, int ld, int col_from_t, int N, int per_sample,
+                        void* stream);
+/* _prior_bpd (:789-803) [N]; with vb [N][nsteps] given, total [N] = sum over t of vb + prior (calc_bpd_loop's total_bpd). */
+int mapdit_prior_bpd(const float* x0, const float* tab, const float* otab, int nsteps, const float* vb, float* prior, float* total,
+                     int N, int per_sample, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Engine: the whole DiT forward / backward sequenced from C++ on one stream (src/dit.py:70-105 and its autograd).
  * ------------------------------------------------------------------------------------------------------------ */

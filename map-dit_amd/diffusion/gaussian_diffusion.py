@@ -1,14 +1,17 @@
 """``GaussianDiffusion`` on HIP kernels — the surface of reference diffusion/gaussian_diffusion.py that the
 training and sampling scripts use: ``num_timesteps``, the float64 numpy schedule tables, ``q_sample``,
-``training_losses``, ``p_mean_variance``, ``p_sample``, ``p_sample_loop`` (+ ``_progressive``).
+``training_losses``, ``p_mean_variance``, ``p_sample``, ``p_sample_loop`` (+ ``_progressive``), DDIM, and the likelihood
+evaluation (``calc_bpd_loop``, ``_vb_terms_bpd``, ``_prior_bpd``) with its helpers.
 
 What differs by design: the schedule tables are uploaded to the GPU once (the reference uploads a numpy table on
 every ``_extract_into_tensor`` call, :861-873), the loss / posterior / sampling pointwise math is one fused kernel
 each (``mapdit_loss_fwd`` / ``mapdit_psample_step``), and there is no host synchronisation inside a step.
 
-Built: the configuration ``create_diffusion`` produces by default and every reference script uses — epsilon
-prediction, learned-range variance, MSE (+ vb) loss.  Other enum members exist for API parity and raise
-NotImplementedError when exercised.
+Built: every objective ``create_diffusion`` can produce — mean type EPSILON / START_X, variance type LEARNED_RANGE /
+FIXED_SMALL / FIXED_LARGE, loss MSE / RESCALED_MSE / KL / RESCALED_KL.  The default (EPSILON, LEARNED_RANGE, MSE) runs the
+kernels it always ran (``mapdit_loss_fwd`` / ``mapdit_psample_step`` / ``mapdit_ddim_step``); the others run the
+generalised ``mapdit_obj_*`` kernels.  ``ModelMeanType.PREVIOUS_X`` and ``ModelVarType.LEARNED`` (never produced by
+``create_diffusion``) exist for API parity and raise NotImplementedError when exercised.
 """
 import enum
 import math
@@ -85,6 +88,48 @@ class _LossFunction(torch.autograd.Function):
         return dout, None, None, None, None, None, None
 
 
+class _ObjLossFunction(torch.autograd.Function):
+    """training_losses of the non-default objectives (mapdit_obj_loss_fwd / mapdit_obj_loss_bwd): loss, mse, vb per sample
+    (mse / vb are zeros where the objective has no such key) and the gradient wrt the model output."""
+
+    @staticmethod
+    def forward(ctx, model_output, x_start, x_t, noise, t, tab, otab, nsteps, kinds):
+        mean_type, var_type, loss_type = kinds
+        n = model_output.shape[0]
+        per = x_start[0].numel()
+        mo = model_output.contiguous().float()
+        mse, vb, loss = (torch.zeros(n, device=mo.device) for _ in range(3))
+        G = torch.empty_like(mo)
+        with torch.cuda.device(mo.device):
+            L.lib().obj_loss_fwd(mo.data_ptr(), x_start.data_ptr(), x_t.data_ptr(), noise.data_ptr(), t.data_ptr(), tab.data_ptr(),
+                                 otab.data_ptr(), nsteps, mean_type, var_type, loss_type, mse.data_ptr(), vb.data_ptr(),
+                                 loss.data_ptr(), G.data_ptr(), n, per, L.cur_stream())
+        ctx.save_for_backward(G)
+        ctx.per = per
+        ctx.groups = 2 if var_type == _VAR_CODE[ModelVarType.LEARNED_RANGE] else 1
+        ctx.kl = loss_type >= _LOSS_CODE[LossType.KL]
+        return loss, mse, vb
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mse, g_vb):
+        (G,) = ctx.saved_tensors
+        dout = torch.empty_like(G)
+        if ctx.kl:                      # the KL losses have no mse / vb keys
+            g_mse = g_vb = None
+        gl, gm, gv = (None if g is None else g.contiguous().float() for g in (g_loss, g_mse, g_vb))
+        with torch.cuda.device(G.device):
+            L.lib().obj_loss_bwd(G.data_ptr(), L.ptr(gl), L.ptr(gm), L.ptr(gv), dout.data_ptr(), G.shape[0], ctx.per, ctx.groups,
+                                 L.cur_stream())
+        return dout, None, None, None, None, None, None, None, None
+
+
+# kernel codes of the objectives (include/mapdit.h, mapdit_obj_*)
+_MEAN_CODE = {ModelMeanType.EPSILON: 0, ModelMeanType.START_X: 1}
+_VAR_CODE = {ModelVarType.LEARNED_RANGE: 0, ModelVarType.FIXED_SMALL: 1, ModelVarType.FIXED_LARGE: 2}
+_LOSS_CODE = {LossType.MSE: 0, LossType.RESCALED_MSE: 1, LossType.KL: 2, LossType.RESCALED_KL: 3}
+_STEP_PSAMPLE, _STEP_DDIM, _STEP_DDIM_REVERSE = 0, 1, 2
+
+
 class GaussianDiffusion:
     """reference gaussian_diffusion.py:144-201 (constructor and tables)."""
 
@@ -132,18 +177,68 @@ class GaussianDiffusion:
             self._tab_cache[("ddim", device)] = tab
         return tab
 
+    def _fixed_large_variance(self):
+        """FIXED_LARGE's variance row (reference gaussian_diffusion.py:300-305)."""
+        return np.append(self.posterior_variance[1], self.betas[1:])
+
+    def _obj_tables(self, device):
+        """The rows the mapdit_obj_* kernels read besides `tab` (layout in include/mapdit.h)."""
+        tab = self._tab_cache.get(("obj", device))
+        if tab is None:
+            rows = [self.alphas_cumprod, self.alphas_cumprod_prev, self.alphas_cumprod_next, np.log(self._fixed_large_variance()),
+                    self.log_one_minus_alphas_cumprod]
+            tab = torch.from_numpy(np.stack(rows)).float().to(device).contiguous()
+            self._tab_cache[("obj", device)] = tab
+        return tab
+
+    def _extract(self, name, t, shape):
+        """reference _extract_into_tensor (:861-873) with the fp32 row resident on the device (uploaded once per row)."""
+        key = ("row", name, t.device)
+        row = self._tab_cache.get(key)
+        if row is None:
+            if name == "fixed_large_variance":
+                arr = self._fixed_large_variance()
+            elif name == "fixed_large_log_variance":
+                arr = np.log(self._fixed_large_variance())
+            else:
+                arr = getattr(self, name)
+            row = torch.from_numpy(np.asarray(arr, dtype=np.float64)).float().to(t.device)
+            self._tab_cache[key] = row
+        res = row[t]
+        return res.view((-1,) + (1,) * (len(shape) - 1)) + torch.zeros(shape, device=t.device)
+
+    def _is_default(self):
+        return (self.model_mean_type == ModelMeanType.EPSILON and self.model_var_type == ModelVarType.LEARNED_RANGE
+                and self.loss_type == LossType.MSE)
+
     def _supported(self):
-        if (self.model_mean_type != ModelMeanType.EPSILON or self.model_var_type != ModelVarType.LEARNED_RANGE
-                or self.loss_type != LossType.MSE):
-            raise NotImplementedError("only the create_diffusion() default (EPSILON, LEARNED_RANGE, MSE) is built; "
+        if self.model_mean_type not in _MEAN_CODE or self.model_var_type not in _VAR_CODE or self.loss_type not in _LOSS_CODE:
+            raise NotImplementedError("built: mean EPSILON / START_X, variance LEARNED_RANGE / FIXED_SMALL / FIXED_LARGE (every "
+                                      "objective create_diffusion() produces); "
                                       f"got {self.model_mean_type}, {self.model_var_type}, {self.loss_type}")
+
+    def _kinds(self):
+        return _MEAN_CODE[self.model_mean_type], _VAR_CODE[self.model_var_type], _LOSS_CODE[self.loss_type]
+
+    def _out_channels(self, C):
+        return 2 * C if self.model_var_type == ModelVarType.LEARNED_RANGE else C
 
     def _wrap_model(self, model):
         return model
 
+    def _model_output(self, model, x, t, model_kwargs):
+        """model(x, t) through the timestep map, checked against the channel count of the variance type."""
+        out = self._wrap_model(model)(x, t, **(model_kwargs or {}))
+        B, C = x.shape[:2]
+        assert out.shape == (B, self._out_channels(C), *x.shape[2:]), (tuple(out.shape), self.model_var_type)
+        return out
+
     @staticmethod
     def _prep(x):
-        assert x.is_cuda, "the diffusion kernels run on the MI355X only (no CPU path)"
+        # an explicit raise, not an assert: under python -O an assert vanishes and a host pointer would reach a kernel
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            where = f"a tensor on {x.device}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise NotImplementedError(f"the diffusion kernels run on the MI355X only (no CPU path); got {where}")
         return x.contiguous().float()
 
     # ---- forward process ------------------------------------------------------------------------------------------------
@@ -161,9 +256,42 @@ class GaussianDiffusion:
                              self.num_timesteps, out.data_ptr(), x_start.shape[0], x_start[0].numel(), L.cur_stream())
         return out
 
+    def q_mean_variance(self, x_start, t):
+        """reference gaussian_diffusion.py:203-213 -> (mean, variance, log_variance), each of x_start's shape."""
+        shape = x_start.shape
+        mean = self._extract("sqrt_alphas_cumprod", t, shape) * x_start
+        return mean, self._extract("one_minus_alphas_cumprod", t, shape), self._extract("log_one_minus_alphas_cumprod", t, shape)
+
+    @property
+    def one_minus_alphas_cumprod(self):
+        return 1.0 - self.alphas_cumprod
+
+    @property
+    def _log_betas(self):
+        return np.log(self.betas)
+
+    def q_posterior_mean_variance(self, x_start, x_t, t):
+        """reference gaussian_diffusion.py:232-252 -> (posterior mean, variance, clipped log-variance)."""
+        assert x_start.shape == x_t.shape
+        shape = x_t.shape
+        mean = self._extract("posterior_mean_coef1", t, shape) * x_start + self._extract("posterior_mean_coef2", t, shape) * x_t
+        return mean, self._extract("posterior_variance", t, shape), self._extract("posterior_log_variance_clipped", t, shape)
+
+    def _predict_xstart_from_eps(self, x_t, t, eps):
+        """reference gaussian_diffusion.py:334-339."""
+        assert x_t.shape == eps.shape
+        return (self._extract("sqrt_recip_alphas_cumprod", t, x_t.shape) * x_t
+                - self._extract("sqrt_recipm1_alphas_cumprod", t, x_t.shape) * eps)
+
+    def _predict_eps_from_xstart(self, x_t, t, pred_xstart):
+        """reference gaussian_diffusion.py:341-344."""
+        return ((self._extract("sqrt_recip_alphas_cumprod", t, x_t.shape) * x_t - pred_xstart)
+                / self._extract("sqrt_recipm1_alphas_cumprod", t, x_t.shape))
+
     # ---- training ----------------------------------------------------------------------------------------------------------
     def training_losses(self, model, x_start, t, model_kwargs=None, noise=None):
-        """reference gaussian_diffusion.py:715-787 -> {"loss", "mse", "vb"}, each [N]."""
+        """reference gaussian_diffusion.py:715-787 -> {"loss", "mse", "vb"} (LEARNED_RANGE with an MSE loss), {"loss", "mse"}
+        (fixed variance, MSE loss) or {"loss"} (KL losses), each [N]."""
         self._supported()
         if model_kwargs is None:
             model_kwargs = {}
@@ -173,6 +301,15 @@ class GaussianDiffusion:
         noise = self._prep(noise)
         t = t.to(device=x_start.device, dtype=torch.int64).contiguous()
         x_t = self.q_sample(x_start, t, noise=noise)
+        if not self._is_default():
+            model_output = self._model_output(model, x_t, t, model_kwargs)
+            loss, mse, vb = _ObjLossFunction.apply(model_output, x_start, x_t, noise, t, self._tables(x_start.device),
+                                                   self._obj_tables(x_start.device), self.num_timesteps, self._kinds())
+            if self.loss_type.is_vb():
+                return {"loss": loss}
+            if self.model_var_type == ModelVarType.LEARNED_RANGE:
+                return {"vb": vb, "mse": mse, "loss": loss}
+            return {"mse": mse, "loss": loss}
         model_output = model(x_t, t, **model_kwargs)
         B, C = x_t.shape[:2]
         assert model_output.shape == (B, C * 2, *x_t.shape[2:])
@@ -181,7 +318,22 @@ class GaussianDiffusion:
         return {"vb": vb, "mse": mse, "loss": loss}
 
     # ---- reverse process ---------------------------------------------------------------------------------------------------
+    def _obj_step(self, model_output, x, t, noise, clip_denoised, mode, eta=0.0):
+        """mapdit_obj_step: p_mean_variance + p_sample / DDIM / reverse DDIM for any built objective -> (sample, pred_xstart).
+        noise None with mode p_sample: the model mean."""
+        x = self._prep(x)
+        mo = self._prep(model_output)
+        mean_type, var_type, _ = self._kinds()
+        sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.lib().obj_step(mo.data_ptr(), x.data_ptr(), L.ptr(noise), t.data_ptr(), self._tables(x.device).data_ptr(),
+                             self._obj_tables(x.device).data_ptr(), self.num_timesteps, mean_type, var_type, int(bool(clip_denoised)),
+                             mode, float(eta), sample.data_ptr(), xstart.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
+        return sample, xstart
+
     def _step_math(self, model_output, x, t, noise, clip_denoised):
+        if not self._is_default():
+            return self._obj_step(model_output, x, t, noise, clip_denoised, _STEP_PSAMPLE)
         x = self._prep(x)
         mo = self._prep(model_output)
         sample, xstart = torch.empty_like(x), torch.empty_like(x)
@@ -200,6 +352,22 @@ class GaussianDiffusion:
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         B, C = x.shape[:2]
         assert t.shape == (B,)
+        if not self._is_default():
+            model_output = self._model_output(model, x, t, model_kwargs)
+            mean, xstart = self._obj_step(model_output, x, t, None, clip_denoised, _STEP_PSAMPLE)
+            if self.model_var_type == ModelVarType.LEARNED_RANGE:
+                frac = (model_output[:, C:].float() + 1) / 2
+                log_var = (frac * self._extract("_log_betas", t, x.shape)
+                           + (1 - frac) * self._extract("posterior_log_variance_clipped", t, x.shape))
+                var = torch.exp(log_var)
+            elif self.model_var_type == ModelVarType.FIXED_SMALL:
+                var = self._extract("posterior_variance", t, x.shape)
+                log_var = self._extract("posterior_log_variance_clipped", t, x.shape)
+            else:
+                var = self._extract("fixed_large_variance", t, x.shape)
+                log_var = self._extract("fixed_large_log_variance", t, x.shape)
+            return {"mean": mean, "variance": var, "log_variance": log_var, "pred_xstart": xstart, "extra": None,
+                    "model_output": model_output}
         model_output = model(x, t, **(model_kwargs or {}))
         assert model_output.shape == (B, C * 2, *x.shape[2:])
         mean, xstart = self._step_math(model_output, x, t, torch.zeros_like(x), clip_denoised)
@@ -218,13 +386,16 @@ class GaussianDiffusion:
             raise NotImplementedError("denoised_fn / cond_fn are not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
-        model_output = self._wrap_model(model)(x, t, **(model_kwargs or {}))
+        model_output = (self._wrap_model(model)(x, t, **(model_kwargs or {})) if self._is_default()
+                        else self._model_output(model, x, t, model_kwargs))
         noise = torch.randn_like(x)
         sample, xstart = self._step_math(model_output, x, t, noise, clip_denoised)
         return {"sample": sample, "pred_xstart": xstart}
 
     # ---- DDIM (reference gaussian_diffusion.py:513-680; no reference script uses it) ----------------------------------
     def _ddim_math(self, model_output, x, t, noise, clip_denoised, eta, reverse):
+        if not self._is_default():
+            return self._obj_step(model_output, x, t, noise, clip_denoised, _STEP_DDIM_REVERSE if reverse else _STEP_DDIM, eta)
         x = self._prep(x)
         mo = self._prep(model_output)
         sample, xstart = torch.empty_like(x), torch.empty_like(x)
@@ -241,7 +412,8 @@ class GaussianDiffusion:
             raise NotImplementedError("denoised_fn / cond_fn are not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
-        model_output = self._wrap_model(model)(x, t, **(model_kwargs or {}))
+        model_output = (self._wrap_model(model)(x, t, **(model_kwargs or {})) if self._is_default()
+                        else self._model_output(model, x, t, model_kwargs))
         noise = torch.randn_like(x)
         sample, xstart = self._ddim_math(model_output, x, t, noise, clip_denoised, eta, False)
         return {"sample": sample, "pred_xstart": xstart}
@@ -254,9 +426,66 @@ class GaussianDiffusion:
             raise NotImplementedError("denoised_fn / cond_fn are not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
-        model_output = self._wrap_model(model)(x, t, **(model_kwargs or {}))
+        model_output = (self._wrap_model(model)(x, t, **(model_kwargs or {})) if self._is_default()
+                        else self._model_output(model, x, t, model_kwargs))
         sample, xstart = self._ddim_math(model_output, x, t, None, clip_denoised, 0.0, True)
         return {"sample": sample, "pred_xstart": xstart}
+
+    # ---- likelihood (reference gaussian_diffusion.py:682-713, 789-858) --------------------------------------------------
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """reference gaussian_diffusion.py:682-713 -> {"output": [N] bits (decoder NLL at t = 0, KL otherwise), "pred_xstart"}."""
+        self._supported()
+        x_start, x_t = self._prep(x_start), self._prep(x_t)
+        t = t.to(device=x_t.device, dtype=torch.int64).contiguous()
+        mo = self._prep(self._model_output(model, x_t, t, model_kwargs))
+        mean_type, var_type, _ = self._kinds()
+        out, xstart = torch.empty(x_t.shape[0], device=x_t.device), torch.empty_like(x_t)
+        with torch.cuda.device(x_t.device):
+            L.lib().obj_vb_terms(mo.data_ptr(), x_start.data_ptr(), x_t.data_ptr(), None, t.data_ptr(), self._tables(x_t.device).data_ptr(),
+                                 self._obj_tables(x_t.device).data_ptr(), self.num_timesteps, mean_type, var_type,
+                                 int(bool(clip_denoised)), out.data_ptr(), None, None, xstart.data_ptr(), 1, 0, x_t.shape[0],
+                                 x_t[0].numel(), L.cur_stream())
+        return {"output": out, "pred_xstart": xstart}
+
+    def _prior_bpd(self, x_start):
+        """reference gaussian_diffusion.py:789-803: KL(q(x_T | x_0) || N(0, I)) in bits, [N]."""
+        x_start = self._prep(x_start)
+        prior = torch.empty(x_start.shape[0], device=x_start.device)
+        with torch.cuda.device(x_start.device):
+            L.lib().prior_bpd(x_start.data_ptr(), self._tables(x_start.device).data_ptr(), self._obj_tables(x_start.device).data_ptr(),
+                              self.num_timesteps, None, prior.data_ptr(), None, x_start.shape[0], x_start[0].numel(), L.cur_stream())
+        return prior
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None):
+        """reference gaussian_diffusion.py:805-858 -> {"total_bpd", "prior_bpd" [N]; "vb", "xstart_mse", "mse" [N, T]}.
+
+        The whole loop is enqueued without a host synchronisation: per timestep (T-1 down to 0) one N(0,1) draw
+        (``torch.randn_like(x_start)``, the reference's order), q_sample, the model forward and one mapdit_obj_vb_terms launch
+        that writes column T-1-t of the three [N, T] arrays (the reference stacks them in loop order); then one mapdit_prior_bpd launch for the prior and the total.  Device
+        errors (an out-of-range timestep or label) are polled once at the end."""
+        self._supported()
+        x_start = self._prep(x_start)
+        dev, N, T = x_start.device, x_start.shape[0], self.num_timesteps
+        per = x_start[0].numel()
+        mean_type, var_type, _ = self._kinds()
+        tab, otab = self._tables(dev), self._obj_tables(dev)
+        vb, xstart_mse, mse = (torch.empty(N, T, device=dev) for _ in range(3))
+        for i in range(T)[::-1]:
+            t = torch.full((N,), i, device=dev, dtype=torch.int64)
+            noise = torch.randn_like(x_start)
+            x_t = self.q_sample(x_start, t, noise=noise)
+            with torch.no_grad():
+                mo = self._prep(self._model_output(model, x_t, t, model_kwargs))
+            with torch.cuda.device(dev):
+                L.lib().obj_vb_terms(mo.data_ptr(), x_start.data_ptr(), x_t.data_ptr(), noise.data_ptr(), t.data_ptr(), tab.data_ptr(),
+                                     otab.data_ptr(), T, mean_type, var_type, int(bool(clip_denoised)), vb.data_ptr(),
+                                     xstart_mse.data_ptr(), mse.data_ptr(), None, T, 1, N, per, L.cur_stream())
+        prior, total = torch.empty(N, device=dev), torch.empty(N, device=dev)
+        with torch.cuda.device(dev):
+            L.lib().prior_bpd(x_start.data_ptr(), tab.data_ptr(), otab.data_ptr(), T, vb.data_ptr(), prior.data_ptr(), total.data_ptr(),
+                              N, per, L.cur_stream())
+            L.lib().device_error_poll(L.cur_stream())
+        return {"total_bpd": total, "prior_bpd": prior, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0):

@@ -22,6 +22,10 @@ class GraphedSampler:
     def __init__(self, model, diffusion, shape, y, cfg_scale=None, clip_denoised=False):
         assert not model.training, "sampling runs the model in eval mode"
         diffusion._supported()
+        if diffusion.model_var_type.name != "LEARNED_RANGE":
+            raise NotImplementedError(f"GraphedSampler drives a DiT, whose output carries learned-range variance channels; a "
+                                      f"{diffusion.model_var_type.name} diffusion needs a model with C output channels "
+                                      "(DiT(learn_sigma=False) is not built): use diffusion.p_sample_loop")
         self.model, self.diffusion = model, diffusion
         dev = next(model.parameters()).device
         self.dev = dev
@@ -31,6 +35,8 @@ class GraphedSampler:
         self.y = y.to(dev).clone()
         self.cfg_scale, self.clip = cfg_scale, bool(clip_denoised)
         self.tab = diffusion._tables(dev)
+        # the default objective replays mapdit_psample_step; x0 prediction (START_X) the generalised mapdit_obj_step
+        self.otab = None if diffusion._is_default() else diffusion._obj_tables(dev)
         self.tmap = torch.tensor(diffusion.timestep_map, device=dev, dtype=torch.int64)
         self.graph = None
         with torch.no_grad():
@@ -57,9 +63,15 @@ class GraphedSampler:
             out = self.model.forward_with_cfg(self.img, mapped, self.y, self.cfg_scale)
         noise = torch.randn_like(self.img)
         nxt = torch.empty_like(self.img)
-        L.lib().psample_step(out.data_ptr(), self.img.data_ptr(), noise.data_ptr(), self.t.data_ptr(), self.tab.data_ptr(),
-                             d.num_timesteps, int(self.clip), nxt.data_ptr(), None, self.img.shape[0], self.img[0].numel(),
-                             L.cur_stream())
+        if self.otab is None:
+            L.lib().psample_step(out.data_ptr(), self.img.data_ptr(), noise.data_ptr(), self.t.data_ptr(), self.tab.data_ptr(),
+                                 d.num_timesteps, int(self.clip), nxt.data_ptr(), None, self.img.shape[0], self.img[0].numel(),
+                                 L.cur_stream())
+        else:
+            mean_type, var_type, _ = d._kinds()
+            L.lib().obj_step(out.data_ptr(), self.img.data_ptr(), noise.data_ptr(), self.t.data_ptr(), self.tab.data_ptr(),
+                             self.otab.data_ptr(), d.num_timesteps, mean_type, var_type, int(self.clip), 0, 0.0, nxt.data_ptr(), None,
+                             self.img.shape[0], self.img[0].numel(), L.cur_stream())
         self.img.copy_(nxt)
         self.t.sub_(1)
 
