@@ -14,9 +14,14 @@ SURVEY.md §8e): that is the default (`"scaling": "strong"`).  `--scaling weak` 
 
 Prints ONE JSON line on rank 0.  `value` = samples of all ranks / wall time of the K timed steps (barrier + synchronize on both
 sides, max over ranks); `ms_per_step_median` is the median over per-step HIP-event intervals of the same K steps.  `roofline` is
-for the dominant kernel (the block-MLP fc1 GEMM), timed with HIP events on its launch stream inside the timed region.  `parity`
-is the error of THIS engine (the timed precision) against the reference's own outputs for the same model (tests/golden fixture).
-`cpu_baseline` times the CPU oracle (oracle/) on a bounded sample of the same model on the host cores — a baseline, not a target.
+for the dominant kernel (the block-MLP fc1 GEMM), timed with HIP events on its launch stream inside the timed region.
+
+A plain run does only that: set-up, W warm-up and K timed steps, the --dump-outputs files, the line.  `--full` adds the legs that
+cost runs of their own (each can be dropped again with its --no-* switch):
+  `parity`       the error of THIS engine (the timed precision) against the reference's own outputs for the same model (tests/golden
+                 fixture); outside the stated limits the run exits 3 after printing its line.
+  `f16`          the same step timed again with IEEE fp16 operands (one-GPU bf16 runs).
+  `cpu_baseline` the CPU oracle (oracle/) timed on a bounded sample of the same model on the host cores — a baseline, not a target.
 """
 import argparse
 import ctypes as C
@@ -225,7 +230,7 @@ def parity_leg(model_name, precision, dev):
 
 # Stated limits of the timed engines against the reference's outputs (the same numbers tests/test_model_gpu.py::
 # test_named_models_match_reference asserts per precision; f16's logits limit is north_star's 1e-3).  A timed engine outside its limits
-# makes bench.py exit non-zero AFTER printing its line: a fast step with wrong results is not a result.
+# makes bench.py --full exit non-zero AFTER printing its line: a fast step with wrong results is not a result.
 PARITY_LIMITS = {
     "bf16": {"logits_rel": 1.6e-2, "loss_rel": 6e-3, "grad_rel": 8e-3, "grad_rel_worst": 4e-2},
     "f16": {"logits_rel": 1e-3, "loss_rel": 5e-4, "grad_rel": 1.5e-3, "grad_rel_worst": 3e-3},
@@ -271,8 +276,11 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=None, help="override the per-GPU batch directly")
     ap.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="bf16",
                     help="bf16: BASELINE.json's metric (the headline).  f16: the same engine with IEEE fp16 operands (also timed as the "
-                         "`f16` object of the default run).  bf16x3: the fp32-accurate parity engine (informational)")
-    ap.add_argument("--no-f16-leg", action="store_true", help="default bf16 run: skip the extra timed fp16 leg")
+                         "`f16` object of a --full run).  bf16x3: the fp32-accurate parity engine (informational)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: parity against the reference fixture, the timed fp16 "
+                         "leg and the CPU baseline")
+    ap.add_argument("--no-f16-leg", action="store_true", help="--full bf16 run: skip the extra timed fp16 leg")
     ap.add_argument("--grad-comm", choices=["allreduce", "zero1", "zero1w", "zero1w-bf16"], default=None,
                     help="gradient exchange under data parallelism (default: $MAPDIT_GRAD_COMM or allreduce); zero1w: sharded weight "
                          "passes (forced WN + imaging, Jacobian, Adam/EMA on 1/world of the rows), -bf16: with a 16-bit gradient exchange")
@@ -284,8 +292,8 @@ def main():
     ap.add_argument("--mp-off", default="", help="comma-separated off forms of the README's --use-* flags: mp_silu, mp_residual, mp_pos_enc, "
                                                  "mp_embedding, weight_normalization, cosine_attention, no_layernorm (README.md:57-66; not in the "
                                                  "reference snapshot: parity unpinned)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full run: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full run: skip the parity legs")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=10)          # ~10 s of host work at ~1 s per DiT-B/2 batch-8 step with the swept thread count
     ap.add_argument("--cpu-c1-steps", type=int, default=10)
@@ -328,7 +336,7 @@ def main():
         """Builds the model in `precision`, runs `warmup` untimed + `steps` timed training steps; returns the measurements.
         With `dump_dir`, what the last timed step computed is written there afterwards (dump_outputs)."""
         parity = None
-        if rank == 0 and not args.no_parity and not unpinned:
+        if rank == 0 and args.full and not args.no_parity and not unpinned:
             parity = parity_leg(args.model, precision, dev)
         torch.manual_seed(0)                               # model seed 0 on every rank: identical replicas, no broadcast needed
         mkw = dict(rotation_modulation=True) if args.rotation_modulation else {}
@@ -447,7 +455,7 @@ def main():
     }
     # The same step with IEEE fp16 operands (gemm_precision = "f16": same kernels, same MFMA rate, 10 mantissa bits): the path
     # whose forward logits are inside north_star's 1e-3 of the reference.  The headline above stays BASELINE.json's bf16.
-    if args.precision == "bf16" and world == 1 and not args.no_f16_leg and not unpinned:
+    if args.full and args.precision == "bf16" and world == 1 and not args.no_f16_leg and not unpinned:
         h = timed_run("f16", args.steps, max(3, args.warmup // 2))
         h_ms = h["fc1_ms"] / max(h["fc1_count"], 1)
         out["f16"] = {"value": world * B * args.steps / h["elapsed"], "unit": "latent-img/s", "ms_per_step": 1e3 * h["elapsed"] / args.steps,
@@ -456,7 +464,7 @@ def main():
                       "fc1_tflops": fc1_flops / (h_ms * 1e-3) / 1e12 if h["fc1_count"] else None,
                       "note": "same engine, IEEE fp16 GEMM / attention operands, static power-of-two loss scale"}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not unpinned:
+        if args.full and world == 1 and not args.no_cpu_baseline and not unpinned:
             out["cpu_baseline"] = cpu_baseline(args.model, args.cpu_batch, args.cpu_steps, args.cpu_c1_steps)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -192,7 +192,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, MAPDIT_DIST_BACKEND="gloo", MAPDIT_FORCE_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--global-batch", "32", "--model", "DiT-S/2"]
+           "--global-batch", "32", "--model", "DiT-S/2", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

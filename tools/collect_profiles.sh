@@ -8,16 +8,16 @@ tag=${1:-r05}
 out=gpurun_out/${tag}_final
 mkdir -p $out
 sha256sum map-dit_amd/csrc/gemm.hip > $out/gemm_hip.sha256
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 echo "bench default done: $(tail -c 300 $out/bench_default.json | head -c 200)"
 for b in 128 64 32; do python bench.py --steps 30 --warmup 5 --batch-per-gpu $b --no-cpu-baseline --no-parity --no-f16-leg > $out/bench_b$b.json 2>/dev/null; done
 # round 5: the compute side of sharded weight passes at the same per-GPU batches (one process = rank 0 of 256 / b ranks, no collectives)
 for b in 128 64 32; do python bench.py --steps 30 --warmup 5 --batch-per-gpu $b --no-cpu-baseline --no-parity --no-f16-leg --emulate-world $((256 / b)) > $out/bench_b${b}_emulated_zero1w.json 2>/dev/null; done
 python bench.py --steps 20 --warmup 5 --mp-off mp_silu,mp_residual,mp_pos_enc,mp_embedding > $out/bench_mp_off.json 2>/dev/null
 python bench.py --steps 20 --warmup 5 --rotation-modulation > $out/bench_rotation.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --model DiT-S/2 --no-cpu-baseline > $out/bench_S2.json 2>/dev/null
-python bench.py --steps 10 --warmup 3 --model DiT-XL/2 --batch-per-gpu 64 --no-cpu-baseline > $out/bench_XL2_b64.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --precision f16 --no-cpu-baseline > $out/bench_f16.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --model DiT-S/2 --no-cpu-baseline > $out/bench_S2.json 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 --model DiT-XL/2 --batch-per-gpu 64 --no-cpu-baseline > $out/bench_XL2_b64.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --precision f16 --no-cpu-baseline > $out/bench_f16.json 2>/dev/null
 python tools/sample_bench.py --model DiT-XL/2 --n 128 --steps 20 > $out/sample_XL2_bf16.json 2>/dev/null
 python tools/sample_bench.py --model DiT-XL/2 --n 128 --steps 20 --precision f16 > $out/sample_XL2_f16.json 2>/dev/null
 python tools/sample_bench.py --model DiT-B/2 --n 64 --steps 30 --precision f16 > $out/sample_B2_f16.json 2>/dev/null
