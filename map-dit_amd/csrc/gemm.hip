@@ -86,30 +86,6 @@ __device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ G, int ld,
     }
 }
 
-// one 1 KiB piece (j = 0..3 of this wave's four) of the same image
-template <int KIND, bool KTAIL>
-__device__ __forceinline__ void stage_piece(const bf16_t* __restrict__ G, int ld, int idx0, int idx_max, int k0, int kmax,
-                                            char* tile, int wave, int lane, int j) {
-    const int seg = wave * 4 + j;
-    const bf16_t* src;
-    if (KIND == OP_ROW) {
-        const int row = seg * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ (row & 7);
-        int grow = idx0 + row;
-        grow = grow < idx_max ? grow : idx_max - 1;
-        src = G + (size_t)grow * ld + k0 + c * 8;
-        if (KTAIL && k0 + c * 8 >= kmax) src = (const bf16_t*)g_zero16;
-    } else {
-        const int krow = seg * 4 + (lane >> 4);
-        const int c = (lane & 15) ^ (kswz(krow) << 1);
-        int col = idx0 + c * 8;
-        col = col < idx_max ? col : 0;
-        src = G + (size_t)(k0 + krow) * ld + col;
-        if (KTAIL && k0 + krow >= kmax) src = (const bf16_t*)g_zero16;
-    }
-    __builtin_amdgcn_global_load_lds(src, (lds_void_t*)(tile + seg * 1024), 16, 0, 0);
-}
-
 // ---- fragment reads ---------------------------------------------------------------------------------
 // 16x16x32 operand fragment: lane l holds [idx = i0 + (l & 15)][k = 32 ks + 8 (l >> 4) + j], j = 0..7.
 template <int KIND, bool TR_ASM = true>
@@ -123,12 +99,7 @@ __device__ __forceinline__ bf16x8_t read_frag(const char* tile, int i0, int ks, 
         const int c = (i0 >> 3) + (pp >> 1);
         const int sub = (pp & 1) << 3;
         bf16x4_t lo, hi;
-#ifdef MAPDIT_TR_BUILTIN        // A/B builds only (tools/_stamps): the builtin form everywhere
-        constexpr bool use_asm = false;
-#else
-        constexpr bool use_asm = TR_ASM;
-#endif
-        if constexpr (!use_asm) {
+        if constexpr (!TR_ASM) {
             // The builtin form: hipcc puts an s_waitcnt vmcnt(0) in front of it whenever an LDS-DMA is in flight.  Kept where that
             // measured FASTER: the NN layout of the 256^2 kernel (1,295 vs 1,238 TFLOP/s at K = 3072, same box).
             const int k_a = 32 * ks + 8 * g + q, k_b = k_a + 4;
@@ -179,14 +150,11 @@ template <class Epi> constexpr int kDirectOuts = 0;
 // (An `sc1` write-through store, which does not keep the line in L2 at all, was 5 % faster still but let a following kernel
 // read stale contents of a reused buffer now and then, even behind s_waitcnt vmcnt(0): not used.)
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-#ifndef MAPDIT_STORE_MODE
-#define MAPDIT_STORE_MODE 0        // A/B builds: 1 = plain stores instead of non-temporal ones
-#endif
 // keep: the tensor is the NEXT kernel's operand (e.g. the modulated activations a RESID epilogue hands to the following GEMM, a dX
 // result the residual backward reads at once): a plain store, so that it is still in the L2 / Infinity Cache when that kernel
 // starts - measured in the step: fc1 380 -> 358 us with its A operand stored that way by the preceding epilogue (round 4).
 __device__ __forceinline__ void store16_stream(void* p, u32x4_t v, bool keep = false) {
-    if (MAPDIT_STORE_MODE == 1 || keep) *(u32x4_t*)p = v;
+    if (keep) *(u32x4_t*)p = v;
     else __builtin_nontemporal_store(v, (u32x4_t*)p);
 }
 __device__ __forceinline__ void store8_bf16(bf16_t* p, const float* v, bool keep = false) {
@@ -857,11 +825,6 @@ constexpr int OFF_A0 = 0, OFF_A1 = SLOT_BYTES, OFF_B0 = 2 * SLOT_BYTES, OFF_B1 =
 constexpr int CS2_LD = 260;                               // fp32 row stride of the epilogue image (1040 B)
 constexpr int SMEM2_BYTES = 128 * CS2_LD * 4;             // 133,120 B >= 2 x 64 KiB staging
 #ifdef MAPDIT_GEMM_STAMPS
-constexpr int SMEM_PH1 = 163840;                          // one-phase loop: 3 A + 2 B buffers = all 160 KiB of LDS
-#else
-constexpr int SMEM_PH1 = 163840;
-#endif
-#ifdef MAPDIT_GEMM_STAMPS
 // Timeline instrumentation (tools/gemm_stamps.py builds this variant into its own library; never part of libmapdit_hip.so):
 // lane 0 of waves 0 and 4 of workgroup 0 stamps the shader clock at 11 points of every K-tile into spare LDS, and copies the
 // stamps out when the tile is done.
@@ -923,13 +886,6 @@ extern "C" __global__ void mapdit_debug_set_stamps_kernel(long long* p, int bloc
 #define G256_STAMPS_OUT()
 #endif
 
-// Ablation builds (tools/attic/gemm_ablate.py; timing experiments, results are garbage): MAPDIT_GEMM_ABLATE bit 0 drops the K loop's
-// LDS-DMA (after the prologue), bit 1 its fragment reads (after the first K-tile).
-#ifndef MAPDIT_GEMM_ABLATE
-#define MAPDIT_GEMM_ABLATE 0
-#endif
-#define ABL_DMA(...) do { if (!(MAPDIT_GEMM_ABLATE & 1)) { __VA_ARGS__; } } while (0)
-#define ABL_READ(...) do { if (!(MAPDIT_GEMM_ABLATE & 2) || t == 0) { __VA_ARGS__; } } while (0)
 template <int SIDE> __device__ __forceinline__ int half_map(int i, int h) {
     return SIDE == 0 ? ((i >> 6) * 128 + h * 64 + (i & 63)) : ((i >> 5) * 64 + h * 32 + (i & 31));
 }
@@ -972,10 +928,10 @@ __device__ __forceinline__ void stage_half(const bf16_t* __restrict__ G, int ld,
 
 // One output tile (virtual workgroup `bid` of `nwg` in the band-major tile order).  The kernel below calls it once per tile of its
 // workgroup.
-template <int AK, int BK, class Epi, bool KTAIL, int PH, bool FE = false>
+template <int AK, int BK, class Epi, bool KTAIL, bool FE = false>
 __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, char* smem, const int bid, const int nwg) {
 #ifdef MAPDIT_GEMM_STAMPS
-    long long* stamp_lds = PH != 2 ? g_stamps : (long long*)(smem + SMEM2_BYTES);
+    long long* stamp_lds = (long long*)(smem + SMEM2_BYTES);
     const long long wg_t0 = (long long)__builtin_readcyclecounter();
     const long long wg_r0 = (long long)__builtin_amdgcn_s_memrealtime();
     long long kl_[3] = {0, 0, 0};
@@ -1011,185 +967,6 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    if constexpr (PH == 1) {
-        // ---- ONE phase per K-tile ------------------------------------------------------------------------------------------
-        // The two wave groups still alternate LOAD and MFMA intervals one barrier apart, but an interval covers a whole K-tile:
-        // 24 fragment reads + 8 LDS-DMA pieces against 64 MFMAs (1024 cycles): half as many barriers per K-tile as the two-phase
-        // loop.  LDS (all 160 KiB): THREE A buffers and TWO B buffers of two 16 KiB slots each {rows of group 0 | rows of group 1}
-        // resp. {columns 0..127 | columns 128..255}, every slot the swizzled [128 idx][64 k] image of the 128^2 kernel.  A wave reads
-        // the A slot of its group and the B slot of its column half.  Group g stages, during its LOAD interval of tile t, B_g of
-        // tile t+1 and then A_g of tile t+2: the A panels stream from HBM and get four intervals (two K-tiles) of prefetch distance,
-        // the B panel is L2-resident and gets one or two.
-        //   RAW  every wait is vmcnt(4): it leaves the four youngest pieces (A_g of tile t+2) in flight.  Group 0's B pieces
-        //        (issued in interval 2t) are waited for at the end of its MFMA interval 2t+1 and read from 2t+2 on; group 1's B
-        //        pieces (issued in 2t+1) are read by group 0 in 2t+2, so group 1 retires them before the barrier that ends 2t+1.
-        //        A_g(t+2), issued in LOAD(t), is retired at the end of MFMA(t+1) at the latest and read in LOAD(t+2).
-        //   WAR  B buffer (t+1)&1 was last read in intervals 2t-2 (group 0) and 2t-1 (group 1); A buffer (t+2)%3 = (t-1)%3 slot g was
-        //        last read by group g itself in LOAD(t-1); all reads were drained (lgkmcnt(0)) before the barrier ending the interval.
-        constexpr int A_BUF = 2 * SLOT_BYTES, B_BASE = 3 * A_BUF, B_BUF = 2 * SLOT_BYTES;
-        static_assert(B_BASE + 2 * B_BUF <= SMEM_PH1, "LDS layout");
-        bf16x8_t fa[8][2], fb[4][2];
-        const int wq = wave & 3;                               // wave within its group: four 1 KiB pieces of every slot it stages
-        auto stage_a = [&](int kt, int abuf) {
-            stage_tile<AK, KTAIL>(p.A, p.lda, m0 + 128 * wm, p.M, kbeg + kt * BKT, p.K, smem + abuf * A_BUF + wm * SLOT_BYTES, wq, lane);
-        };
-        auto stage_b = [&](int kt) {
-            stage_tile<BK, KTAIL>(p.B, p.ldb, n0 + 128 * wm, p.N, kbeg + kt * BKT, p.K, smem + B_BASE + (kt & 1) * B_BUF + wm * SLOT_BYTES, wq, lane);
-        };
-        stage_a(0, 0);
-        stage_b(0);
-        if (nk > 1) {
-            stage_a(1, 1);
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (wm == 1) {                                         // stagger: group 1 runs one interval behind
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        G256_TSTAMP(1);
-        G256_RSTAMP(5);
-        int a_cur = 0;                                         // t % 3
-        for (int t = 0; t < nk; ++t) {
-            const char* a_slot = smem + a_cur * A_BUF + wm * SLOT_BYTES;
-            const char* b_slot = smem + B_BASE + (t & 1) * B_BUF + (wn >> 1) * SLOT_BYTES;
-            const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
-            G256_STAMP(0);
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fa[i][ks] = read_frag<AK>(a_slot, i * 16, ks, lane);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fb[j][ks] = read_frag<BK>(b_slot, (wn & 1) * 64 + j * 16, ks, lane);
-            if (has1) stage_b(t + 1);
-            if (has2) stage_a(t + 2, a_cur == 0 ? 2 : a_cur - 1);       // (t + 2) % 3
-            G256_STAMP(1);
-            if (wm == 1 && has1) {
-                if (has2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            G256_STAMP(2);
-            G256_END_LOAD();
-            G256_STAMP(3);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[i][j] = MFMA16(fb[j][ks], fa[i][ks], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-            G256_STAMP(4);
-            if (has2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            G256_END_MFMA();
-            G256_STAMP(5);
-            a_cur = a_cur == 2 ? 0 : a_cur + 1;
-        }
-        if (wm == 0) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    } else if constexpr (PH == 3) {
-        // ---- software-pipelined loop: no LOAD / MFMA alternation -----------------------------------------------------------------
-        // Every wave keeps TWO fragment sets (the two 32-deep k-steps of a K-tile: 2 x 48 registers) and always has 32 MFMAs whose
-        // operands were read one step earlier: the fragment reads of the next step are issued first, then the MFMAs of the current
-        // one.  Both waves of a SIMD offer MFMAs all the time, so the matrix pipe only idles at the ONE barrier per K-tile (the
-        // two-phase loop has four, and at any time only one of its two wave groups issues MFMAs: 77 % pipe occupancy even with empty
-        // LOAD intervals, tools/attic/gemm_ablate.py).  LDS and staging as in the one-phase loop: three A and two B buffers of two 16 KiB
-        // slots; group g stages B_g of tile t+2 and then A_g of tile t+3 right after the barrier of tile t.
-        //   RAW  the barrier of iteration t follows every wave's vmcnt(4) (its pieces of tile t+1 have landed; the four youngest,
-        //        A of tile t+2, stay in flight) and precedes the first read of tile t+1.
-        //   WAR  B buffer t&1 and A buffer t%3 are re-staged after that same barrier, which follows every wave's lgkmcnt(0) on its
-        //        last reads of tile t (step ks = 1; the ks = 0 reads were issued an iteration earlier).
-        constexpr int A_BUF = 2 * SLOT_BYTES, B_BASE = 3 * A_BUF, B_BUF = 2 * SLOT_BYTES;
-        static_assert(B_BASE + 2 * B_BUF <= SMEM_PH1, "LDS layout");
-        bf16x8_t f0a[8], f0b[4], f1a[8], f1b[4];
-        const int wq = wave & 3;
-        auto stage_a = [&](int kt, int abuf) {
-            stage_tile<AK, KTAIL>(p.A, p.lda, m0 + 128 * wm, p.M, kbeg + kt * BKT, p.K, smem + abuf * A_BUF + wm * SLOT_BYTES, wq, lane);
-        };
-        auto stage_b = [&](int kt) {
-            stage_tile<BK, KTAIL>(p.B, p.ldb, n0 + 128 * wm, p.N, kbeg + kt * BKT, p.K, smem + B_BASE + (kt & 1) * B_BUF + wm * SLOT_BYTES, wq, lane);
-        };
-#define G256_SP_READ(FA, FB, ABUF, KT, KS)                                                                              \
-        {                                                                                                               \
-            const char* a_slot_ = smem + (ABUF) * A_BUF + wm * SLOT_BYTES;                                              \
-            const char* b_slot_ = smem + B_BASE + ((KT) & 1) * B_BUF + (wn >> 1) * SLOT_BYTES;                          \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i) FA[i] = read_frag<AK>(a_slot_, i * 16, KS, lane);             \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) FB[j] = read_frag<BK>(b_slot_, (wn & 1) * 64 + j * 16, KS, lane); \
-        }
-#define G256_SP_MFMA(FA, FB)                                                                                            \
-        __builtin_amdgcn_s_setprio(1);                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                                   \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                   \
-            acc[i][j] = MFMA16(FB[j], FA[i], acc[i][j]);                      \
-        __builtin_amdgcn_s_setprio(0)
-        stage_a(0, 0);
-        stage_b(0);
-        if (nk > 1) { stage_a(1, 1); stage_b(1); }
-        if (nk > 2) stage_a(2, 2);
-        if (nk > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (nk > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        G256_TSTAMP(1);
-        G256_RSTAMP(5);
-        G256_SP_READ(f0a, f0b, 0, 0, 0);
-        int a_cur = 0;                                         // t % 3
-        for (int t = 0; t < nk; ++t) {
-            const bool has1 = t + 1 < nk, has2 = t + 2 < nk, has3 = t + 3 < nk;
-            const int a_nxt = a_cur == 2 ? 0 : a_cur + 1;
-            // the first MFMA of the step goes BEFORE the next step's reads: the wait for the f0 fragments (hipcc's own for tracked
-            // row-major reads, the explicit one for the inline-asm transposing reads) is then an lgkmcnt(0) with only those, long
-            // finished, reads outstanding; placed after the new reads it would wait for them too
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][0] = MFMA16(f0b[0], f0a[0], acc[0][0]);
-            __builtin_amdgcn_sched_barrier(0);
-            G256_SP_READ(f1a, f1b, a_cur, t, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i + j > 0) acc[i][j] = MFMA16(f0b[j], f0a[i], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (has1) {
-                if (has2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            G256_END_LOAD();                                   // lgkmcnt(0) + barrier
-            if (has2) stage_b(t + 2);
-            if (has3) stage_a(t + 3, a_cur);
-            acc[0][0] = MFMA16(f1b[0], f1a[0], acc[0][0]);
-            __builtin_amdgcn_sched_barrier(0);
-            G256_SP_READ(f0a, f0b, a_nxt, t + 1, 0);           // (after the last tile: a harmless read of stale LDS, no branch)
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i + j > 0) acc[i][j] = MFMA16(f1b[j], f1a[i], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            a_cur = a_nxt;
-        }
-#undef G256_SP_READ
-#undef G256_SP_MFMA
-    } else {
     bf16x8_t fa[4][2], fb0[2][2], fb1[2][2];               // B half 0 stays in registers for phases 1 and 4
     constexpr bool TR_ASM2 = AK == OP_KMAJ;                // transposing reads: asm for TN; NN keeps the builtin (see read_frag)
 
@@ -1254,11 +1031,11 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
             const int k1 = kbeg + (t + 1) * BKT, k2 = kbeg + (t + 2) * BKT;
             const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
             G256_STAMP(0);
-            ABL_READ(load_a(cur + OFF_A0));
-            ABL_READ(G256_LOAD_B(fb0, cur + OFF_B0));
-            ABL_READ(G256_LOAD_B(fb1, cur + OFF_B1));
+            load_a(cur + OFF_A0);
+            G256_LOAD_B(fb0, cur + OFF_B0);
+            G256_LOAD_B(fb1, cur + OFF_B1);
             if (has1) {
-                ABL_DMA(stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k1, p.K, 1, nxt + OFF_A1, wave, lane));
+                stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k1, p.K, 1, nxt + OFF_A1, wave, lane);
                 G256_STAMP(1);
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else {
@@ -1272,11 +1049,11 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
             G256_STAMP(4);
             G256_END_MFMA();
             G256_STAMP(5);
-            ABL_READ(load_a(cur + OFF_A1));
+            load_a(cur + OFF_A1);
             if (has2) {
-                ABL_DMA(stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k2, p.K, 0, cur + OFF_A0, wave, lane));
-                ABL_DMA(stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 0, cur + OFF_B0, wave, lane));
-                ABL_DMA(stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 1, cur + OFF_B1, wave, lane));
+                stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k2, p.K, 0, cur + OFF_A0, wave, lane);
+                stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 0, cur + OFF_B0, wave, lane);
+                stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 1, cur + OFF_B1, wave, lane);
                 G256_STAMP(6);
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else if (has1) {
@@ -1331,7 +1108,6 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     }
-    }   // PH != 1
     __syncthreads();
     G256_TSTAMP(2);
     G256_RSTAMP(6);
@@ -1592,20 +1368,17 @@ __device__ __forceinline__ void stagger_start(const GemmP& p) {
 // XCD either way, so the band-major order keeps its meaning).  What it saves is the hand-over between two workgroups on a CU: the
 // dispatch of the next one waits for the previous one's stores to drain and its LDS to be released (3-7 k cycles per tile of
 // ~50 k); inside one workgroup the next tile's prologue starts behind the last store's issue.
-template <int AK, int BK, class Epi, bool KTAIL = false, int PH = 2, bool FE = false>
+template <int AK, int BK, class Epi, bool KTAIL = false, bool FE = false>
 __global__ __launch_bounds__(512, 2) void gemm_mfma256_kernel(GemmP p, Epi epi) {
 #ifdef MAPDIT_GEMM_STAMPS
-    // (the one-phase loop uses all 160 KiB of LDS: its stamps go straight to the global buffer - the stamping waves then carry a
-    // few extra stores in their vmcnt queues, which the instrumented timeline has to live with)
-    constexpr int SM = PH != 2 ? SMEM_PH1 : SMEM2_BYTES;
-    __shared__ __attribute__((aligned(16))) char smem[SM + (PH != 2 ? 0 : (2 * STAMP_TILES * STAMP_POINTS + 8) * 8)];
+    __shared__ __attribute__((aligned(16))) char smem[SMEM2_BYTES + (2 * STAMP_TILES * STAMP_POINTS + 8) * 8];
 #else
-    __shared__ __attribute__((aligned(16))) char smem[PH != 2 ? SMEM_PH1 : kReduce<Epi> ? SMEM2_BYTES + 3 * 8 * 256 * 4 : SMEM2_BYTES];
+    __shared__ __attribute__((aligned(16))) char smem[kReduce<Epi> ? SMEM2_BYTES + 3 * 8 * 256 * 4 : SMEM2_BYTES];
 #endif
     const int total = p.tiles * p.split_k;
     stagger_start(p);
     for (int v = blockIdx.x; v < total; v += gridDim.x) {
-        gemm256_tile<AK, BK, Epi, KTAIL, PH, FE>(p, epi, smem, v, total);
+        gemm256_tile<AK, BK, Epi, KTAIL, FE>(p, epi, smem, v, total);
         __syncthreads();                                   // the tile's last LDS reads are done before the next prologue lands
     }
 }
@@ -1633,7 +1406,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256_group_kernel(GroupArgs g)
     for (int v = blockIdx.x; v < total; v += gridDim.x) {
         int i = 0;
         while (i + 1 < g.n && v >= g.first[i + 1]) ++i;
-        gemm256_tile<OP_KMAJ, OP_KMAJ, EpiStoreF32, false, 2, false>(g.p[i], g.e[i], smem, v - g.first[i], g.first[i + 1] - g.first[i]);
+        gemm256_tile<OP_KMAJ, OP_KMAJ, EpiStoreF32, false, false>(g.p[i], g.e[i], smem, v - g.first[i], g.first[i + 1] - g.first[i]);
         __syncthreads();
     }
 }
@@ -1908,465 +1681,6 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
     }
 }
 
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-// ---- the same kernel with a THREE-deep A ring: MEASURED AND REJECTED (round 4) ------------------------------------------------------
-// Bit-identical results, 5-12 % SLOWER isolated (QKV store 1,117 -> 996, heads 1,064 -> 939, fc1 871 -> 825 TFLOP/s on one box), slower
-// inside the step (fc1 349 -> 375 us, step 43.9 -> 44.8 ms) and slower from cold caches (fc1 362 -> 397 us): what the cold K loop lacks
-// is not prefetch distance.  Compiled only with -DMAPDIT_GEMM_EXPERIMENTS (MAPDIT_GEMM_W3=1 selects it there).  The idea was:
-// Inside the training step a GEMM's A operand was written by the kernel before it and comes from HBM, next to the launch's own
-// output stream (fc1: 806 MB of stores per launch); an isolated launch finds it in the Infinity Cache.  tools/gemm_phases.py --cold
-// reproduces the difference: fc1's K loop takes 41 k cycles per tile instead of 29 k, the waits of the two-deep staging ring exposed
-// (fc1 328 -> 392 us; in the step 365 us).  The 32 KiB the staging leaves free become a third A buffer: the A panels (which stream)
-// are requested a K-tile earlier, the B panel (L2-resident) keeps two buffers.  The wave-private epilogue buffers alias the A slot the
-// next tile's prologue does not touch (K-tile 2's A goes out after the epilogue).
-//   LDS: A ring 3 x {A0 | A1} at 0 / 32 / 64 KiB, B ring 2 x {B0 | B1} at 96 / 128 KiB; A(t) -> slot t % 3, B(t) -> slot t & 1.
-//   Issue order per wave: ... A1[t+2] (phase A of K-tile t), A0[t+3] B0[t+2] B1[t+2] (phase B of t) ...; the prologue issues
-//   A0[0] A1[0] A0[1] B0[0] B1[0] A1[1] A0[2] B0[1] B1[1] in that same order.
-//   RAW  phase A waits until A1[t] has landed (read in phase B): every wave's counted vmcnt leaves exactly what was issued after it in
-//        flight (16 pieces in the steady state); phase B waits for B1[t+1], the youngest piece phase A of t+1 reads (8 in flight).
-//   WAR  A1[t+2] goes to the slot whose A1 was last read in phase B of t-1; A0[t+3] to slot t % 3, whose A0 phase A of t has just read
-//        (drained by lgkmcnt(0) before the barrier between); B0 / B1[t+2] likewise - the distances of the two-deep loop.
-constexpr int W3_ASLOT = 2 * SLOT_BYTES, W3_BBASE = 3 * W3_ASLOT, W3_BOUNCE = 2 * W3_ASLOT;
-static_assert(W3_BBASE + 2 * 2 * SLOT_BYTES == SMEM_W_BYTES && W3_BOUNCE + 8 * WPRIV_BYTES <= W3_BBASE, "LDS layout");
-__device__ __forceinline__ void wait_vm_even(int n) {      // s_waitcnt vmcnt(n) for a wave-uniform even n in 0..16 (an immediate in the ISA)
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    }
-}
-
-template <int AK, int BK, class Epi, bool KTAIL = false>
-__global__ __launch_bounds__(512, 2) void gemm_mfma256w3_kernel(GemmP p, Epi epi) {
-    __shared__ __attribute__((aligned(16))) char smem[SMEM_W_BYTES];
-    const int total = p.tiles * p.split_k;
-    int v = blockIdx.x;
-    if (v >= total) return;
-    constexpr bool TR_ASM2 = AK == OP_KMAJ;
-    TileCoord c = tile_coord(p, v, total);
-    // pieces of K-tile kt (tile-local index): into A slot kt % 3 / B slot kt & 1
-    auto st_a = [&](const TileCoord& tc, int kt, int slot, int h, int wave, int lane) {
-        stage_half<AK, 0, KTAIL>(p.A, p.lda, tc.m0, p.M, tc.kbeg + kt * BKT, p.K, h, smem + slot * W3_ASLOT + h * SLOT_BYTES, wave, lane);
-    };
-    auto st_b = [&](const TileCoord& tc, int kt, int h, int wave, int lane) {
-        stage_half<BK, 1, KTAIL>(p.B, p.ldb, tc.n0, p.N, tc.kbeg + kt * BKT, p.K, h, smem + W3_BBASE + (kt & 1) * W3_ASLOT + h * SLOT_BYTES, wave, lane);
-    };
-    // the part of a tile's prologue that may go out before the previous epilogue (A slots 0, 1 and both B slots): everything but A0[2]
-    auto prologue_early = [&](const TileCoord& tc, int wave, int lane) {        // needs nk >= 4 (the launcher guarantees it)
-        st_a(tc, 0, 0, 0, wave, lane); st_a(tc, 0, 0, 1, wave, lane); st_a(tc, 1, 1, 0, wave, lane);
-        st_b(tc, 0, 0, wave, lane); st_b(tc, 0, 1, wave, lane);
-        st_a(tc, 1, 1, 1, wave, lane);
-    };
-    {
-        const int tid0 = threadIdx.x, w0 = __builtin_amdgcn_readfirstlane(tid0 >> 6), l0 = tid0 & 63;
-        prologue_early(c, w0, l0);
-        st_a(c, 2, 2, 0, w0, l0);                          // first tile: the canonical order, A0[2] ahead of B0[1] B1[1]
-        st_b(c, 1, 0, w0, l0); st_b(c, 1, 1, w0, l0);
-    }
-    bool first = true;
-    for (;;) {
-        int tid_ = threadIdx.x;
-        asm volatile("" : "+v"(tid_));
-        const int tid = tid_, lane = tid & 63;
-        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int wm = wave >> 2, wn = wave & 3;
-        const int nk = c.nk;
-        f32x4_t acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        bf16x8_t fa[4][2], fb0[2][2], fb1[2][2];
-        auto load_a = [&](const char* slot) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fa[i][ks] = read_frag<AK, TR_ASM2>(slot, wm * 64 + i * 16, ks, lane);
-        };
-        if (first) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // A0 A1 A0' B0 B1 of the canonical order have landed
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the early prologue (and the epilogue's stores behind it)
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // A0[2] goes to the slot that held the epilogue buffers of ALL waves: only behind the barrier every wave reaches after its
-        // epilogue (the same holds for A1[2], issued in phase A of K-tile 0).  It is then the youngest piece instead of the seventh of
-        // the canonical order: the counted waits below stay upper bounds (phase B of K-tile 0 retires it early, nothing later is delayed).
-        if (!first) st_a(c, 2, 2, 0, wave, lane);
-        if (wm == 1) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // pieces issued in phase A / phase B of K-tile u (u < 0: the prologue, in the canonical order)
-        auto n_a1 = [&](int u) { return u + 2 < nk ? 2 : 0; };
-        auto n_b = [&](int u) { return (u + 3 < nk ? 2 : 0) + (u + 2 < nk ? 4 : 0); };
-        int a = 0;                                                         // t % 3
-        for (int t = 0; t < nk; ++t) {
-            const int a1 = a == 2 ? 0 : a + 1, a2 = a == 0 ? 2 : a - 1;    // (t + 1) % 3, (t + 2) % 3
-            const char* As = smem + a * W3_ASLOT;
-            const char* Bs = smem + W3_BBASE + (t & 1) * W3_ASLOT;
-            load_a(As);
-            G256_LOAD_B(fb0, Bs);
-            G256_LOAD_B(fb1, Bs + SLOT_BYTES);
-            if (t + 2 < nk) st_a(c, t + 2, a2, 1, wave, lane);
-            wait_vm_even(n_b(t - 2) + n_a1(t - 1) + n_b(t - 1) + n_a1(t));       // A1[t] and everything older have landed
-            G256_END_LOAD();
-            G256_MFMA(0, 0, fb0);
-            G256_MFMA(0, 1, fb1);
-            G256_END_MFMA();
-            load_a(As + SLOT_BYTES);
-            if (t + 3 < nk) st_a(c, t + 3, a, 0, wave, lane);
-            if (t + 2 < nk) { st_b(c, t + 2, 0, wave, lane); st_b(c, t + 2, 1, wave, lane); }
-            wait_vm_even(n_a1(t) + n_b(t));                                        // B1[t+1] and everything older have landed
-            G256_END_LOAD();
-            G256_MFMA(1, 1, fb1);
-            G256_MFMA(1, 0, fb0);
-            G256_END_MFMA();
-            a = a1;
-        }
-        if (wm == 0) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const int vn = v + (int)gridDim.x;
-        TileCoord cn = c;
-        if (vn < total) {
-            cn = tile_coord(p, vn, total);
-            prologue_early(cn, wave, lane);
-            st_b(cn, 1, 0, wave, lane); st_b(cn, 1, 1, wave, lane);
-        }
-        if (c.m0 + BM2 <= p.M && c.n0 + BN2 <= p.N)
-            g256w_epilogue<Epi, true>(p, epi, c, acc, smem + W3_BOUNCE + wave * WPRIV_BYTES, wave, lane);
-        else
-            g256w_epilogue<Epi, false>(p, epi, c, acc, smem + W3_BOUNCE + wave * WPRIV_BYTES, wave, lane);
-        if (vn >= total) break;
-        v = vn;
-        c = cn;
-        first = false;
-    }
-}
-
-#endif   // MAPDIT_GEMM_EXPERIMENTS (three-deep A ring)
-
-// ---- the one-wave-per-SIMD kernel: 256x256x64 tile, 4 waves (2 M x 2 N), 128x128 per wave ----------------------------
-// MEASURED AND REJECTED (round 3, profiles/r03_gemm_w4_experiment.log): bit-correct on all layouts, 7-10 % SLOWER than the 8-wave
-// kernel on every shape of the block (NN K = 3072: 1,174 vs 1,268 TFLOP/s; NT K = 768: 967 vs 1,077).  The ablation builds say why:
-// with neither LDS-DMA nor fragment reads in the loop both kernels run at ~1,650 TFLOP/s (the clock the part holds under MFMA load),
-// but a single wave per SIMD pays for every read and every DMA piece on its own in-order issue stream (reads alone: -24 % here,
-// -10 % in the 8-wave kernel, where the partner wave issues them beside the other wave's MFMAs).  Compiled only with
-// -DMAPDIT_GEMM_EXPERIMENTS (gemm_tuning phases = 5); never part of the product library.
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-// The 8-wave kernel above alternates two wave groups between LOAD and MFMA intervals: at any time one of the two waves of a SIMD
-// issues MFMAs, and its partner's LDS reads stretch those intervals (the matrix pipe issues 71 % of the K loop).  Here a SIMD has
-// ONE wave that owns the whole 512-entry register file: 256 accumulators (8 x 8 tiles of 16x16) and two sets of fragments, the
-// reads of the next 32-deep k-step and the LDS-DMA of the tile after next issued BETWEEN the MFMAs of the current k-step:
-//   * LDS bytes read per K-tile: 4 waves x 32 KiB = 128 KiB (8 waves x 24 KiB = 192 KiB above);
-//   * ONE barrier per K-tile, in the middle of it: before it every wave has issued and retired all its reads of tile t (the
-//     second k-step's fragments are in registers) and waited for its own LDS-DMA pieces of tile t+1; after it the stage of tile t
-//     is free (DMA of tile t+2 goes there: a two-stage ring, 128 KiB) and tile t+1 may be read (its first k-step's fragments are
-//     fetched under the MFMAs of tile t's second k-step).  RAW and WAR both hang on that one barrier.
-//   * every wave stages a quarter of each of the four 16 KiB slots {A rows 0-127, A rows 128-255, B cols 0-127, B cols 128-255}
-//     (the swizzled images of the 128^2 kernel): 16 LDS-DMA pieces per K-tile and wave.
-template <int AK, int BK, class Epi, bool KTAIL>
-__device__ __forceinline__ void gemm_w4_tile(const GemmP& p, const Epi& epi, char* smem, const int bid, const int nwg) {
-    int tid_ = threadIdx.x;
-    asm volatile("" : "+v"(tid_));                         // per tile: nothing derived from the thread index is kept across tiles
-    const int tid = tid_, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int z = wg / p.tiles, tile = wg - z * p.tiles;
-    const int tiles_m = p.tiles / p.tiles_n;
-    const int bsz = tiles_m * p.band;
-    const int bidx = tile / bsz, rem = tile - bidx * bsz;
-    const int bw = (bidx + 1) * p.band <= p.tiles_n ? p.band : p.tiles_n - bidx * p.band;
-    const int m0 = (rem / bw) * BM2, n0 = (bidx * p.band + rem % bw) * BN2;
-    const int nkt = (p.K + BKT - 1) / BKT, kbase = nkt / p.split_k, krem = nkt % p.split_k;
-    const int kbeg = (z * kbase + (z < krem ? z : krem)) * BKT;
-    const int nk = kbase + (z < krem ? 1 : 0);
-    constexpr bool ASM_READS = AK == OP_KMAJ || BK == OP_KMAJ;      // transposing reads are inline asm: explicit lgkmcnt waits
-
-    f32x4_t acc[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    bf16x8_t fa0[8], fb0[8], fa1[8], fb1[8];
-
-    // LDS: three A stages and two B stages of two 16 KiB slots each (160 KiB): the A panels stream from HBM and get two K-tiles
-    // of prefetch distance, the B (weight) panel is L2-resident and gets one.  A(kt) -> A stage kt % 3, B(kt) -> B stage kt % 2.
-    constexpr int A_STAGE = 2 * SLOT_BYTES, B_BASE = 3 * A_STAGE, B_STAGE = 2 * SLOT_BYTES;
-    static_assert(B_BASE + 2 * B_STAGE <= SMEM_PH1, "LDS layout");
-    auto a_stage = [&](int kt) { return smem + (kt % 3) * A_STAGE; };
-    auto b_stage = [&](int kt) { return smem + B_BASE + (kt & 1) * B_STAGE; };
-    // piece q = 0..7 of an operand's K-tile: slot q >> 2 (rows / columns 0-127 | 128-255), piece q & 3 of this wave
-    auto stage_a = [&](int kt, int q) {
-        stage_piece<AK, KTAIL>(p.A, p.lda, m0 + 128 * (q >> 2), p.M, kbeg + kt * BKT, p.K, a_stage(kt) + (q >> 2) * SLOT_BYTES, wave, lane, q & 3);
-    };
-    auto stage_b = [&](int kt, int q) {
-        stage_piece<BK, KTAIL>(p.B, p.ldb, n0 + 128 * (q >> 2), p.N, kbeg + kt * BKT, p.K, b_stage(kt) + (q >> 2) * SLOT_BYTES, wave, lane, q & 3);
-    };
-#define W4_READ(FA, FB, KT, KS)                                                                                       \
-    {                                                                                                                 \
-        const char* a_slot_ = a_stage(KT) + wm * SLOT_BYTES;                                                          \
-        const char* b_slot_ = b_stage(KT) + wn * SLOT_BYTES;                                                          \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) FA[i] = read_frag<AK>(a_slot_, i * 16, KS, lane);               \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) FB[j] = read_frag<BK>(b_slot_, j * 16, KS, lane);               \
-    }
-    // The MFMAs are inline asm with the accumulator operand constrained to the accumulator half of the register file ("+a"): left to
-    // itself hipcc spread 256 accumulators + 128 fragment registers over both halves and shuffled them with v_accvgpr_read / _write
-    // inside the loop.  A volatile asm also pins the program order of the LDS reads and LDS-DMA issues written between them.
-#if MAPDIT_DT == 1
-#define W4_MFMA1(I, J, FA, FB) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[I][J]) : "v"(FB[J]), "v"(FA[I]))
-#else
-#define W4_MFMA1(I, J, FA, FB) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[I][J]) : "v"(FB[J]), "v"(FA[I]))
-#endif
-    // One 32-deep k-step: 64 MFMAs (rows i of A fragments x columns j of B fragments) with, between them, the 16 fragment reads
-    // of the NEXT k-step (READ_ROW0: the first of the two rows of MFMAs that carry them, one read per MFMA) and, in rows 0..3, the
-    // 16 LDS-DMA pieces of later tiles (one per two MFMAs).
-#define W4_STEP(FA, FB, NFA, NFB, NKT, NKS, READ_ROW0, DMA_B, DMA_B_KT, DMA_A, DMA_A_KT)                              \
-    {                                                                                                                 \
-        const char* a_slot_ = a_stage(NKT) + wm * SLOT_BYTES;                                                         \
-        const char* b_slot_ = b_stage(NKT) + wn * SLOT_BYTES;                                                         \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                               \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                           \
-                W4_MFMA1(i, j, FA, FB);                                                                               \
-                if (i >= (READ_ROW0) && i < (READ_ROW0) + 2 && !(MAPDIT_GEMM_ABLATE & 2)) {                           \
-                    const int r_ = (i - (READ_ROW0)) * 8 + j;     /* B fragments first (every row needs them) */      \
-                    if (r_ < 8) NFB[r_] = read_frag<BK>(b_slot_, r_ * 16, NKS, lane);                                 \
-                    else NFA[r_ - 8] = read_frag<AK>(a_slot_, (r_ - 8) * 16, NKS, lane);                              \
-                }                                                                                                     \
-                if (i < 4 && (j & 1) == 1) {                                                                          \
-                    const int q_ = i * 4 + (j >> 1);                                                                  \
-                    if (q_ < 8) { if ((DMA_B) && !(MAPDIT_GEMM_ABLATE & 1)) stage_b(DMA_B_KT, q_); }                  \
-                    else { if ((DMA_A) && !(MAPDIT_GEMM_ABLATE & 1)) stage_a(DMA_A_KT, q_ - 8); }                     \
-                }                                                                                                     \
-            }                                                                                                         \
-        }                                                                                                             \
-    }
-
-    // prologue, in steady-state order: {A(0) B(0)} {B(1) A(1)} {A(2)}; the wait leaves everything behind tile 0 in flight
-#pragma unroll
-    for (int q = 0; q < 8; ++q) stage_a(0, q);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) stage_b(0, q);
-    if (nk > 1) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) stage_b(1, q);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) stage_a(1, q);
-    }
-    if (nk > 2) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) stage_a(2, q);
-        asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    } else if (nk > 1) {
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    W4_READ(fa0, fb0, 0, 0);
-    for (int t = 0; t < nk; ++t) {
-        if (ASM_READS) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // first k-step of tile t; the second one's fragments arrive under its first two rows of MFMAs
-        W4_STEP(fa0, fb0, fa1, fb1, t, 1, 0, false, 0, false, 0);
-        // A(t+1), B(t+1) (this wave's pieces) have landed - only A(t+2), the youngest eight pieces, may still fly - and every read
-        // of tile t has returned
-        if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // second k-step.  Rows 0..3: the LDS-DMA of B(t+2) and A(t+3) into the stages tile t has just left; rows 4, 5: the first
-        // fragments of tile t+1 (after the last tile: a harmless read of stale LDS)
-        W4_STEP(fa1, fb1, fa0, fb0, t + 1, 0, 4, t + 2 < nk, t + 2, t + 3 < nk, t + 3);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // the last MFMAs' results are read by compiler code below (asm hides the hazard)
-#undef W4_STEP
-#undef W4_MFMA1
-#undef W4_READ
-    __syncthreads();                                       // (every wave's reads are long done; orders the image writes below)
-
-    // epilogue: two passes of 128 rows (rows [64 pass, 64 pass + 64) of both wave rows) through an fp32 image in LDS, then whole
-    // 8-column row chunks per thread with the pass's stream operands prefetched (as in the 8-wave kernel)
-    float* cs = (float*)smem;
-    const int ecol = (tid & 31) * 8, gn = n0 + ecol;
-    const bool col_ok = gn < p.N;
-    typename Epi::Tile tctx;
-    if (col_ok) tctx = epi.tile_begin(m0, (m0 + BM2 <= p.M ? m0 + BM2 : p.M) - 1, gn);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int row = wm * 64 + i * 16 + (lane & 15);
-                const int col = wn * 128 + j * 16 + 4 * (lane >> 4);
-                *(f32x4_t*)(cs + row * CS2_LD + col) = acc[pass * 4 + i][j];
-            }
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            typename Epi::Aux aux[8];
-#pragma unroll
-            for (int it = 0; it < 8; ++it) {
-                const int row = (tid >> 5) + 8 * (half * 8 + it);
-                const int gm = m0 + (row >> 6) * 128 + pass * 64 + (row & 63);
-                if (gm < p.M && col_ok) aux[it] = epi.load(gm, gn);
-            }
-            if (half == 0) __syncthreads();
-#pragma unroll
-            for (int it = 0; it < 8; ++it) {
-                const int row = (tid >> 5) + 8 * (half * 8 + it);
-                const int gm = m0 + (row >> 6) * 128 + pass * 64 + (row & 63);
-                if (gm < p.M && col_ok) {
-                    float v[8];
-                    *(f32x4_t*)(v) = *(const f32x4_t*)(cs + row * CS2_LD + ecol);
-                    *(f32x4_t*)(v + 4) = *(const f32x4_t*)(cs + row * CS2_LD + ecol + 4);
-                    epi.apply(gm, gn, v, z, aux[it], tctx);
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-template <int AK, int BK, class Epi, bool KTAIL = false>
-__global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmP p, Epi epi) {
-    __shared__ __attribute__((aligned(16))) char smem[SMEM_PH1];
-    const int total = p.tiles * p.split_k;
-    for (int v = blockIdx.x; v < total; v += gridDim.x) {
-        gemm_w4_tile<AK, BK, Epi, KTAIL>(p, epi, smem, v, total);
-        __syncthreads();
-    }
-}
-#endif   // MAPDIT_GEMM_EXPERIMENTS
-
-
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-// ---- round 5 experiment: the 256x128 geometry of "two tiles in flight per CU" - K LOOP ONLY ------------------------------------------------
-// VERDICT r04 item 2(b) asks for a 256x128 tile whose waves hold 64 accumulator registers for the current tile beside the previous tile's 64,
-// with that tile's epilogue issued inside this tile's K loop.  Before any epilogue is placed there, the geometry's K loop has to hold the
-// 256^2 loop's rate - this kernel measures exactly that: 8 waves as 4 (M) x 2 (N), 64 x 64 per wave (16 accumulator tiles = 64 registers),
-// a three-deep ring of {A 256 x 64 | B 128 x 64} K-tile stages (144 KiB), one phase per K-tile (LOAD: 16 fragment reads + 6 LDS-DMA
-// pieces; MFMA: 32), the two wave groups alternating LOAD and MFMA intervals one barrier apart as in the shipped kernels, DMA two K-tiles
-// ahead.  Results are correct (plain 16-bit store straight from the accumulator layout: 8-byte pieces, slow but once per tile).
-// gemm_tuning phases = 8 selects it for the plain 16-bit store (tools/gemm_bench.py --x128).  Not part of the product.
-template <int KIND>
-__device__ __forceinline__ void stage_id128(const bf16_t* __restrict__ G, int ld, int idx0, int idx_max, int k0, char* slot, int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int seg = wave * 2 + j;
-        const bf16_t* src;
-        if (KIND == OP_ROW) {
-            const int row = seg * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ (row & 7);
-            int g = idx0 + row;
-            g = g < idx_max ? g : idx_max - 1;
-            src = G + (size_t)g * ld + k0 + c * 8;
-        } else {
-            const int krow = seg * 4 + (lane >> 4);
-            const int c = (lane & 15) ^ (kswz(krow) << 1);
-            int col = idx0 + c * 8;
-            col = col < idx_max ? col : 0;
-            src = G + (size_t)(k0 + krow) * ld + col;
-        }
-        __builtin_amdgcn_global_load_lds(src, (lds_void_t*)(slot + seg * 1024), 16, 0, 0);
-    }
-}
-
-template <int AK, int BK, class Epi>
-__global__ __launch_bounds__(512, 2) void gemm_x128_kernel(GemmP p, Epi epi) {
-    constexpr int STAGE = 3 * SLOT_BYTES;                  // A rows 0..127 | A rows 128..255 | B 128 columns
-    __shared__ __attribute__((aligned(16))) char smem[3 * STAGE];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wg = wave >> 2;                              // stagger group (waves 4-7 run one interval behind)
-    const int wm = wave & 3, wn = wave >> 2;               // 4 x 2 wave grid: group 0 = column half 0, group 1 = column half 1
-    const int tiles_n = p.N / 128;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int m0 = (tile / tiles_n) * 256, n0 = (tile % tiles_n) * 128;
-    const int nk = p.K / BKT;
-    constexpr bool TR_ASM2 = AK == OP_KMAJ;
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    auto stage = [&](int t) {
-        char* b = smem + (t % 3) * STAGE;
-        stage_id128<AK>(p.A, p.lda, m0, p.M, t * BKT, b, wave, lane);
-        stage_id128<AK>(p.A, p.lda, m0 + 128, p.M, t * BKT, b + SLOT_BYTES, wave, lane);
-        stage_id128<BK>(p.B, p.ldb, n0, p.N, t * BKT, b + 2 * SLOT_BYTES, wave, lane);
-    };
-    stage(0);
-    if (nk > 1) { stage(1); asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (wg == 1) {
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    bf16x8_t fa[4][2], fb[4][2];
-    for (int t = 0; t < nk; ++t) {
-        const char* b = smem + (t % 3) * STAGE;
-        const char* as = b + (wm >> 1) * SLOT_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fa[i][ks] = read_frag<AK, TR_ASM2>(as, (wm & 1) * 64 + i * 16, ks, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fb[j][ks] = read_frag<BK, TR_ASM2>(b + 2 * SLOT_BYTES, wn * 64 + j * 16, ks, lane);
-        // buffer (t + 2) % 3 = (t - 1) % 3 was last read in LOAD(t - 1) of both groups, which ended before this interval began
-        if (t + 2 < nk) { stage(t + 2); asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }      // tile t + 1 has landed
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        G256_END_LOAD();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(fb[j][ks], fa[i][ks], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        G256_END_MFMA();
-    }
-    if (wg == 0) {
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (kDirectOuts<Epi> == 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int R = m0 + wm * 64 + i * 16 + (lane & 15), Cc = n0 + wn * 64 + j * 16 + 4 * (lane >> 4);
-                u32x2_t o[1];
-                epi.pw(acc[i][j], o, 1);
-                if (R < p.M && Cc < p.N) *(u32x2_t*)(epi.dst(0) + (size_t)R * epi.ldo + Cc) = o[0];
-            }
-    }
-}
-#endif   // MAPDIT_GEMM_EXPERIMENTS (256x128 K loop)
-
 // ---- generic fallback for shapes the MFMA tiling does not take (K % 8 != 0, unaligned operands) --------------
 // One thread per (row, 8-column chunk); strides are in elements.  Only used for negligible-FLOP shapes.
 template <class Epi>
@@ -2404,6 +1718,10 @@ extern "C" void mapdit_debug_set_stamps_block(long long* p, int block) {      //
 }
 #endif
 
+// The K-loop / kernel selector of the 256^2 path (MAPDIT_GEMM_PHASES, mapdit_gemm_tuning): 2 = default, 4 = one quadrant per phase,
+// 6 = the wave-private-epilogue kernel for every epilogue, 7 = the shared-image kernel for every epilogue; anything else is 2.
+static int gemm_phases_arg(int v) { return v == 4 || v == 6 || v == 7 ? v : 2; }
+
 // A/B switches for benchmarking, read from the environment ONCE (the first launch): the launch path makes no getenv calls.
 // (One instance in the library: the bf16 build of this file owns it, the fp16 build refers to it.)
 struct GemmEnv {
@@ -2416,7 +1734,6 @@ struct GemmEnv {
     // operand): 1 RESID xm, 2 STORE_BF16 out, 4 QKV_HEADS q^ k^ v, 8 SILU2_GRAD act, 16 MUL_AUX out; 32: RESID xout NON-temporal
     int keep_mask = 1;
     int nsplit = 1;          // MAPDIT_GEMM_NSPLIT = 0: no column split of results whose width is an odd multiple of 128
-    int w3 = 0;              // MAPDIT_GEMM_W3 = 1 (experiment builds only): the three-deep A ring variant of the round-4 kernel
     int fast_epi = 1;        // MAPDIT_GEMM_FE = 0: never the straight-line epilogue instantiation (RESID; A/B)
     int band768 = 3;         // MAPDIT_GEMM_BAND768 = column tiles per band of the K <= 768 forward (NT) GEMMs (fc1, QKV)
     int stagger = -1;        // MAPDIT_GEMM_STAGGER = late start of every second workgroup, units of 8,128 cycles (persistent launches); -1: by epilogue
@@ -2424,13 +1741,12 @@ struct GemmEnv {
         if (const char* e = getenv("MAPDIT_GEMM_PERSIST")) persist = atoi(e);
         if (const char* e = getenv("MAPDIT_KEEP")) keep_mask = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_NSPLIT")) nsplit = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_W3")) w3 = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_STAGGER")) stagger = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_BAND768")) band768 = atoi(e) > 0 ? atoi(e) : 3;
         if (const char* e = getenv("MAPDIT_GEMM_FE")) fast_epi = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_TILE_RULE")) old_tile_rule = e[0] == 'o';
         if (const char* e = getenv("MAPDIT_GEMM_TILE")) tile = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_PHASES")) phases = atoi(e) == 4 ? 4 : atoi(e) == 1 ? 1 : atoi(e) == 3 ? 3 : atoi(e) == 5 ? 5 : atoi(e) == 7 ? 7 : atoi(e) == 6 ? 6 : atoi(e) == 8 ? 8 : 2;
+        if (const char* e = getenv("MAPDIT_GEMM_PHASES")) phases = gemm_phases_arg(atoi(e));
         if (const char* e = getenv("MAPDIT_GEMM_BAND")) band = atol(e);
     }
 };
@@ -2442,11 +1758,11 @@ GemmEnv& mapdit_gemm_env_ref() {
     return env;
 }
 // Tuning hook of the benchmarking tools (tools/gemm_bench.py, gemm_band_sweep.py): overrides what the environment said.
-// tile: 0 = by shape | 128 | 256;  phases: 2 | 4;  band: 0 = derived from K.  Not for use while launches are in flight elsewhere.
+// tile: 0 = by shape | 128 | 256;  phases: 2 | 4 | 6 | 7 (gemm_phases_arg);  band: 0 = derived from K.  Not for use while launches are in flight elsewhere.
 extern "C" void mapdit_gemm_tuning(int tile, int phases, long band) {
     GemmEnv& e = gemm_env();
     e.tile = tile;
-    e.phases = phases == 4 ? 4 : phases == 1 ? 1 : phases == 3 ? 3 : phases == 5 ? 5 : phases == 7 ? 7 : phases == 6 ? 6 : phases == 8 ? 8 : 2;
+    e.phases = gemm_phases_arg(phases);
     e.band = band;
 }
 
@@ -2489,10 +1805,22 @@ MD_NS_OPEN
 template <class Epi> constexpr bool kHasTail = false;
 template <> constexpr bool kHasTail<EpiStoreF32> = true;
 
+// The one place that turns `layout` into the operand kinds of a kernel template: f(ak, bk) is called with the (A, B) pair as two
+// std::integral_constant<int, OP_*> (ak.value / bk.value are template arguments at the call site; f is inlined, no indirection).
+template <class F>
+inline void with_operand_kinds(int layout, F&& f) {
+    using Row = std::integral_constant<int, OP_ROW>;
+    using Kmaj = std::integral_constant<int, OP_KMAJ>;
+    if (layout == MAPDIT_NT) f(Row(), Row());
+    else if (layout == MAPDIT_NN) f(Row(), Kmaj());
+    else f(Kmaj(), Kmaj());
+}
+
 template <class Epi>
 int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16_t* B, int ldb, Epi epi,
            hipStream_t st, int split_k = 1, int n_off = 0, bool force128 = false) {
-    const bool a_kmaj = layout == MAPDIT_TN, b_kmaj = layout != MAPDIT_NT;
+    bool a_kmaj = false, b_kmaj = false;
+    with_operand_kinds(layout, [&](auto ak, auto bk) { a_kmaj = ak.value == OP_KMAJ; b_kmaj = bk.value == OP_KMAJ; });
     // Round 4: a result whose width is an odd multiple of 128 (DiT-XL: 1152) on few enough rows that the 256^2 tiles of its first
     // N - 128 columns are ONE round of the chip (DiT-XL/2 at 64 samples: 64 x 4 = 256 tiles; with the half-empty fifth tile column it was
     // 320 tiles, which the tile rule gave to the 128^2 kernel): two launches, the 256^2 kernel on the first N - 128 columns and the 128^2
@@ -2568,104 +1896,41 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
             const int sg = gemm_env().stagger;
             p.stagger = sg >= 0 ? sg : (std::is_same<Epi, EpiResid>::value ? 2 : 0);
         }
-        auto go = [&](auto tail, auto ph) {
+        // Kernel family.  Default: the round-4 kernel (wave-private epilogue, next tile's prologue under it) where it measured faster -
+        // the epilogues that are arithmetic (SiLU, per-head normalisation, the saved-factor product): +2 ... +11 % - and the plain bf16
+        // store at short K (fill hidden: +1.5 %).  RESID stays on the shared-image kernel: its 32 bytes per chunk of residual
+        // stream need all 16 chunks of a thread in flight, which only fits in registers once the accumulators are dead (wave-
+        // private: 60 k cycles of epilogue per tile against ~15 k; tools/gemm_phases.py).  phases = 7 or 4 select the older kernel,
+        // 6 forces the round-4 one for every epilogue (but those with per-tile reductions, which exist in the shared-image kernel only).
+        bool use_w = false;
+        if constexpr (!kReduce<Epi>)
+            use_w = p.phases == 6 || (p.phases == 2 && kWaveEpilogue<Epi> && (kWaveEpilogueAnyK<Epi> || K / split_k <= 1024));
+        if (p.phases == 7 || p.phases == 6) p.phases = 2;       // (both only choose the kernel: its K loop is the two-phase one)
+        // The straight-line epilogue (FE) of the shared-image kernel where the launcher can promise what it assumes: every tile inside
+        // the result and, for RESID, inside one sample.  MAPDIT_GEMM_FE=0 keeps the guarded form (A/B).
+        bool fe = false;
+        if constexpr (kFastEpi<Epi>)
+            fe = gemm_env().fast_epi && M % BM2 == 0 && N % BN2 == 0 && epi.fast_ok();
+        auto go = [&](auto tail) {
             constexpr bool TAIL = decltype(tail)::value;
-            constexpr int PH = decltype(ph)::value;
-            if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma256_kernel<OP_ROW, OP_ROW, Epi, TAIL, PH>), dim3(grid), dim3(512), 0, st, p, epi);
-            else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_mfma256_kernel<OP_ROW, OP_KMAJ, Epi, TAIL, PH>), dim3(grid), dim3(512), 0, st, p, epi);
-            else hipLaunchKernelGGL((gemm_mfma256_kernel<OP_KMAJ, OP_KMAJ, Epi, TAIL, PH>), dim3(grid), dim3(512), 0, st, p, epi);
-        };
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-        using T1 = std::integral_constant<int, 1>;
-        using T3 = std::integral_constant<int, 3>;
-#endif
-        using T2 = std::integral_constant<int, 2>;
-        bool done = false;
-        if constexpr (!kReduce<Epi>) {
-            // default: the round-4 kernel (wave-private epilogue, next tile's prologue under it) where it measured faster - the
-            // epilogues that are arithmetic (SiLU, per-head normalisation, the saved-factor product): +2 ... +11 % - and the plain bf16
-            // store at short K (fill hidden: +1.5 %).  RESID stays on the shared-image kernel: its 32 bytes per chunk of residual
-            // stream need all 16 chunks of a thread in flight, which only fits in registers once the accumulators are dead (wave-
-            // private: 60 k cycles of epilogue per tile against ~15 k; tools/gemm_phases.py).  phases = 7 or 4 select the older kernel,
-            // 6 forces the round-4 one for every epilogue.
-            const bool use_w = p.phases == 6 || (p.phases == 2 && kWaveEpilogue<Epi> && (kWaveEpilogueAnyK<Epi> || K / split_k <= 1024));
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-            const bool deep = gemm_env().w3 && ((K + BKT - 1) / BKT) / split_k >= 4;          // every K range has at least four K-tiles
-#endif
-            if (use_w) {
-                p.phases = 2;
-                auto gow = [&](auto tail) {
-                    constexpr bool TAIL = decltype(tail)::value;
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-                    if (deep) {
-                        if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma256w3_kernel<OP_ROW, OP_ROW, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
-                        else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_mfma256w3_kernel<OP_ROW, OP_KMAJ, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
-                        else hipLaunchKernelGGL((gemm_mfma256w3_kernel<OP_KMAJ, OP_KMAJ, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
-                        return;
-                    }
-#endif
-                    if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma256w_kernel<OP_ROW, OP_ROW, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
-                    else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_mfma256w_kernel<OP_ROW, OP_KMAJ, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
-                    else hipLaunchKernelGGL((gemm_mfma256w_kernel<OP_KMAJ, OP_KMAJ, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
-                };
-                if constexpr (kHasTail<Epi>) {
-                    if (ktail) { gow(std::true_type()); done = true; }
+            with_operand_kinds(layout, [&](auto ak, auto bk) {
+                if constexpr (!kReduce<Epi>) {
+                    if (use_w) { hipLaunchKernelGGL((gemm_mfma256w_kernel<ak.value, bk.value, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi); return; }
                 }
-                if (!done) { gow(std::false_type()); done = true; }
-            }
-        }
-        if (p.phases == 7 || p.phases == 6) p.phases = 2;
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-        if constexpr (kDirectOuts<Epi> == 1) {
-            if (p.phases == 8 && !ktail && split_k == 1 && N % 128 == 0 && M % 256 == 0) {      // round 5: the 256x128 K-loop experiment
-                const int g8 = (M / 256) * (N / 128);
-                if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_x128_kernel<OP_ROW, OP_ROW, Epi>), dim3(g8), dim3(512), 0, st, p, epi);
-                else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_x128_kernel<OP_ROW, OP_KMAJ, Epi>), dim3(g8), dim3(512), 0, st, p, epi);
-                else hipLaunchKernelGGL((gemm_x128_kernel<OP_KMAJ, OP_KMAJ, Epi>), dim3(g8), dim3(512), 0, st, p, epi);
+                if constexpr (kFastEpi<Epi> && !TAIL) {
+                    if (fe) { hipLaunchKernelGGL((gemm_mfma256_kernel<ak.value, bk.value, Epi, false, true>), dim3(grid), dim3(512), 0, st, p, epi); return; }
+                }
+                hipLaunchKernelGGL((gemm_mfma256_kernel<ak.value, bk.value, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
+            });
+        };
+        if constexpr (kHasTail<Epi>) {
+            if (ktail) {
+                go(std::true_type());
                 MD_LAUNCH_CHECK();
                 return MAPDIT_OK;
             }
         }
-        if (p.phases == 8) p.phases = 2;                     // (the experiment applies to the plain 16-bit store only)
-        if constexpr (!kReduce<Epi>) {
-            if (p.phases == 5 && !ktail) {                 // the 4-wave kernel (one wave per SIMD): a rejected experiment, see its comment
-                if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_w4_kernel<OP_ROW, OP_ROW, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
-                else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_w4_kernel<OP_ROW, OP_KMAJ, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
-                else hipLaunchKernelGGL((gemm_w4_kernel<OP_KMAJ, OP_KMAJ, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
-                done = true;
-            }
-        }
-#endif
-        if constexpr (kHasTail<Epi>) {
-            if (ktail && !done) {
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-                if (p.phases == 1) go(std::true_type(), T1()); else if (p.phases == 3) go(std::true_type(), T3()); else
-#endif
-                go(std::true_type(), T2());
-                done = true;
-            }
-        }
-        if (!done) {
-            // The one-phase (1) and software-pipelined (3) K loops are measured-and-rejected experiments (profiles/r02_gemm_kloop_
-            // experiments.log): compiled only with -DMAPDIT_GEMM_EXPERIMENTS (tools/gemm_stamps.py builds do), never in the product.
-#ifdef MAPDIT_GEMM_EXPERIMENTS
-            if (p.phases == 1) go(std::false_type(), T1()); else if (p.phases == 3) go(std::false_type(), T3()); else
-#endif
-            {
-                // The straight-line epilogue (FE) where the launcher can promise what it assumes: every tile inside the result and, for
-                // RESID, inside one sample.  MAPDIT_GEMM_FE=0 keeps the guarded form (A/B).
-                bool fe = false;
-                if constexpr (kFastEpi<Epi>)
-                    fe = gemm_env().fast_epi && M % BM2 == 0 && N % BN2 == 0 && epi.fast_ok();
-                if (fe) {
-                    if constexpr (kFastEpi<Epi>) {
-                        if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma256_kernel<OP_ROW, OP_ROW, Epi, false, 2, true>), dim3(grid), dim3(512), 0, st, p, epi);
-                        else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_mfma256_kernel<OP_ROW, OP_KMAJ, Epi, false, 2, true>), dim3(grid), dim3(512), 0, st, p, epi);
-                        else hipLaunchKernelGGL((gemm_mfma256_kernel<OP_KMAJ, OP_KMAJ, Epi, false, 2, true>), dim3(grid), dim3(512), 0, st, p, epi);
-                    }
-                } else go(std::false_type(), T2());
-            }
-        }
+        go(std::false_type());
     } else if (mfma) {
         // Round 5: few 128^2 tiles (DiT-XL's 128-column strips: 128 or fewer workgroups on 256 CUs) -> 64-row tiles, twice the workgroups, the
         // same bits (gemm_mfma64_kernel).  For the epilogues the strips carry.  MAPDIT_GEMM_TILE64=0 switches it off (A/B).
@@ -2675,8 +1940,9 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
             if (t64_env && !a_kmaj && !ktail && split_k == 1 && t128 <= 160 && M >= 256) {
                 GemmP p{A, B, lda, ldb, M, N, K, cdiv(N, BN), 0, 1, 0, 4, n_off, 0};
                 p.tiles = cdiv(M, 64) * p.tiles_n;
-                if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma64_kernel<OP_ROW, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
-                else hipLaunchKernelGGL((gemm_mfma64_kernel<OP_KMAJ, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
+                with_operand_kinds(layout, [&](auto, auto bk) {       // (A is row-major here)
+                    hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
+                });
                 MD_LAUNCH_CHECK();
                 return MAPDIT_OK;
             }
@@ -2686,16 +1952,16 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
         const int grid = p.tiles * split_k;
         if constexpr (kHasTail<Epi>) {
             if (ktail) {
-                if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma_kernel<OP_ROW, OP_ROW, Epi, true>), dim3(grid), dim3(256), 0, st, p, epi);
-                else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_mfma_kernel<OP_ROW, OP_KMAJ, Epi, true>), dim3(grid), dim3(256), 0, st, p, epi);
-                else hipLaunchKernelGGL((gemm_mfma_kernel<OP_KMAJ, OP_KMAJ, Epi, true>), dim3(grid), dim3(256), 0, st, p, epi);
+                with_operand_kinds(layout, [&](auto ak, auto bk) {
+                    hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi, true>), dim3(grid), dim3(256), 0, st, p, epi);
+                });
                 MD_LAUNCH_CHECK();
                 return MAPDIT_OK;
             }
         }
-        if (layout == MAPDIT_NT) hipLaunchKernelGGL((gemm_mfma_kernel<OP_ROW, OP_ROW, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
-        else if (layout == MAPDIT_NN) hipLaunchKernelGGL((gemm_mfma_kernel<OP_ROW, OP_KMAJ, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
-        else hipLaunchKernelGGL((gemm_mfma_kernel<OP_KMAJ, OP_KMAJ, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
+        with_operand_kinds(layout, [&](auto ak, auto bk) {
+            hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
+        });
     } else {
         if (n_off != 0 || force128) {          // the scalar fallback indexes columns from 0: never the second half of a column split
             mapdit_set_error("gemm: internal: column-offset launch reached the non-MFMA path (M=%d N=%d K=%d)", M, N, K);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Sustained-throughput vs. clock for the 256x256 GEMM schedules: each variant runs back to back for SECONDS seconds (the chip's
 power management settles within that), then reports TFLOP/s over the last half and the in-kernel clock of the K loop
-(s_memtime / s_memrealtime stamps, instrumented library).   python tools/gemm_stamps.py --build; python tools/gemm_clock.py"""
+(s_memtime / s_memrealtime stamps, instrumented library).   python tools/gemm_stamps.py --build; python tools/gemm_clock.py
+The phases = 1 variant (one-phase K loop) was removed from gemm.hip (commit dcc272c is the last that holds it); the library maps
+the value to 2 now, so both passes time the shipped schedule."""
 import ctypes as C
 import os
 import subprocess

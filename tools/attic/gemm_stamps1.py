@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """In-kernel stamps of the ONE-phase K loop of the 256x256 GEMM (same instrumented build as tools/gemm_stamps.py):
 per K-tile, for a wave of each wave group: LOAD = {24 fragment reads + 8 LDS-DMA pieces issued | group 1's vmcnt(4) | lgkmcnt(0) +
-barrier}, MFMA = {64 MFMAs | vmcnt(0) + barrier}.      python tools/gemm_stamps.py --build ; python tools/gemm_stamps1.py [phases]"""
+barrier}, MFMA = {64 MFMAs | vmcnt(0) + barrier}.      python tools/gemm_stamps.py --build ; python tools/gemm_stamps1.py [phases]
+The one-phase loop was removed from gemm.hip (commit dcc272c is the last that holds it): phases takes 2 | 4 | 6 | 7 now, and the
+default of 1, like every other value, runs the shipped two-phase schedule."""
 import ctypes as C
 import os
 import sys

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-workgroup wall time of the 256x256 GEMM (instrumented library): every workgroup records s_memrealtime at entry / exit, its
 cycle count and its XCC id.  Prints the distribution per schedule: where a launch's time goes beyond (tiles / CUs) x tile time.
-    python tools/gemm_stamps.py --build ; python tools/gemm_wgtimes.py"""
+    python tools/gemm_stamps.py --build ; python tools/gemm_wgtimes.py
+The phases = 1 variant (one-phase K loop) was removed from gemm.hip (commit dcc272c is the last that holds it); the library maps
+the value to 2 now, so both passes record the shipped schedule."""
 import ctypes as C
 import os
 import sys

@@ -29,7 +29,7 @@ python -m mapdit_amd.train --synthetic --model DiT-B/2 --num-steps 300 --batch-s
 # round 2
 bash tools/collect_profiles.sh && python tools/summarise_profiles.py                # bench lines at 256/128/64/32, kernel stats, fc1 PMC traffic
 python tools/precision_rank.py                    > $out/precision_rank.log   # which bf16 roundings carry the logits error
-python tools/gemm_ablate.py --build && python tools/gemm_ablate.py > $out/gemm_ablate.log   # fill / K loop / epilogue per tile
+# (the K-loop ablation run, tools/gemm_ablate.py, was removed with the ablation builds of gemm.hip: commit dcc272c is the last that holds them)
 for t in mfma_issue store_rate load_rate; do hipcc --offload-arch=gfx950 -O3 tools/$t.hip -o tools/_stamps/$t && tools/_stamps/$t > $out/$t.log; done
 python tools/step_stress.py 2000 2                > $out/step_stress.log      # bit-reproducibility beside a second process on the GPU
 python tools/dp_repeat.py 4                       > $out/dp_repeat.log        # two-rank runs, bit for bit

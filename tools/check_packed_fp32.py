@@ -29,32 +29,43 @@ ALLOW = re.compile(r"^_ZN12_GLOBAL__N_1(?:3f16)?\d+gemm_(?:mfma(?:256w?)?|simple
 ALLOWED_OPS = {"v_pk_mul_f32", "v_pk_add_f32", "v_pk_fma_f32"}
 
 
-def packed_by_kernel(lib):
+SYMBOL = re.compile(r"^[0-9a-f]+ <(.+)>:$")
+
+
+def code_objects(lib):
+    """Unbundle the gfx950 code objects of a shared library: yields (path, `llvm-objdump -d` text) per code object, in a fixed
+    order.  The files live in a temporary directory that is removed when the generator is exhausted or closed
+    (tools/compare_device_code.py reads their notes as well)."""
     tmp = tempfile.mkdtemp(prefix="pkcheck_")
     try:
         so = os.path.join(tmp, "lib.so")
         shutil.copy(lib, so)
         subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", so], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        found, kernels = {}, 0
         for name in sorted(os.listdir(tmp)):
             if "amdgcn" not in name:
                 continue
-            dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", os.path.join(tmp, name)], check=True,
-                                 capture_output=True, text=True).stdout
-            cur = None
-            for line in dis.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    cur = m.group(1)
-                    kernels += 1
-                    continue
-                m = PACKED.search(line)
-                if m and cur:
-                    found.setdefault(cur, {}).setdefault(m.group(1), 0)
-                    found[cur][m.group(1)] += 1
-        return found, kernels
+            path = os.path.join(tmp, name)
+            yield path, subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", path], check=True,
+                                       capture_output=True, text=True).stdout
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+def packed_by_kernel(lib):
+    found, kernels = {}, 0
+    for _, dis in code_objects(lib):
+        cur = None
+        for line in dis.splitlines():
+            m = SYMBOL.match(line)
+            if m:
+                cur = m.group(1)
+                kernels += 1
+                continue
+            m = PACKED.search(line)
+            if m and cur:
+                found.setdefault(cur, {}).setdefault(m.group(1), 0)
+                found[cur][m.group(1)] += 1
+    return found, kernels
 
 
 def main():
