@@ -330,8 +330,9 @@ int mapdit_scale_copy(float* out, const float* x, long n, float alpha, void* str
 /* ------------------------------------------------------------------------------------------------------------
  * Cosine attention (src/layers/attention.py:37-51).  Head-major operands are [B*H][T][head_dim] bf16, row-major.
  * head_dim 64 with T in {64, 128, 256} - or any multiple of 256 (64x64 latents at patch 2: 1,024 tokens; the kernels then loop
- * over 256-token key / query tiles) - runs on the MFMA kernels, head_dim 72 (DiT-XL) with T in {64, 128, 256} too; any other
- * head_dim <= 96 with T <= 256 (patch-8 models: 16 tokens) is dispatched to the generic fp32 path with the same interface.
+ * over 256-token key / query tiles) - runs on the MFMA kernels, head_dim 72 (DiT-XL) with the same token counts too (multiples of 256
+ * up to 16,384: DiT-XL/2 on 64x64 latents); any other head_dim <= 96 with T <= 256 (patch-8 models: 16 tokens) is dispatched to the
+ * generic fp32 path with the same interface.
  * ------------------------------------------------------------------------------------------------------------ */
 /* qkv [B*T, 3*H*hd] -> qn, kn (cosine-normalised: q*sqrt(hd)/(|q|+eps)), v */
 int mapdit_qkv_split(const uint16_t* qkv, int B, int T, int H, int head_dim, uint16_t* qn, uint16_t* kn, uint16_t* v,
@@ -343,15 +344,22 @@ int mapdit_attn_cos_fwd(const uint16_t* qn, const uint16_t* kn, const uint16_t* 
                         int T, int H, int head_dim, void* stream);
 /* The same forward on UNNORMALISED q, k (head-major, as MAPDIT_EPI_QKV_HEADS_RAW writes them): each row is scaled by
  * sqrt(head_dim) / (|row| + 1e-4) and rounded to the operand format while it is staged (reference attention.py:38-43 = normalize of
- * q, k, then SDPA).  Nothing is kept for a backward pass: inference only.  head_dim 72, T in {64, 128, 256}. */
+ * q, k, then SDPA).  Nothing is kept for a backward pass: inference only.  head_dim 72, T in {64, 128, 256} or a multiple of 256 up to
+ * 16,384 (q, k are only read: every query-tile workgroup normalises the key tiles it stages for itself). */
 int mapdit_attn_cos_fwd_rawqk(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H,
                               int head_dim, void* stream);
 /* The training form of it (abi 4): q and k are overwritten IN PLACE by their normalised rows and the scales sqrt(head_dim) /
  * (|row| + 1e-4) are kept in scales [2][B*H][T] (q rows, then k rows) - what mapdit_attn_cos_bwd_fused needs.  With it the head_dim-72
  * models (DiT-XL) train without a split / normalise pass over the QKV result and without a merge pass over its gradient, like the
- * head_dim-64 models do through MAPDIT_EPI_QKV_HEADS (reference attention.py:37-47 and its autograd). */
+ * head_dim-64 models do through MAPDIT_EPI_QKV_HEADS (reference attention.py:37-47 and its autograd).  head_dim 72, T in {64, 128, 256}
+ * or a multiple of 256 up to 16,384; beyond 256 tokens it is mapdit_qk_cos_normalize followed by mapdit_attn_cos_fwd (the query tiles of a
+ * head share its key rows, so the attention kernel itself must not write them). */
 int mapdit_attn_cos_fwd_rawqk_save(uint16_t* q, uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, float* scales, int B, int T,
                                    int H, int head_dim, void* stream);
+/* The normalisation alone (added within abi 5: additive, no existing signature changed): raw head-major q, k [B*H][T][head_dim] are
+ * overwritten IN PLACE by q * s, k * s, s = sqrt(head_dim) / (|row| + 1e-4), rounded to the operand format, and s goes to scales
+ * [2][B*H][T] (q rows, then k rows).  Every workgroup reads and writes its own 256 rows only.  head_dim 72, any T. */
+int mapdit_qk_cos_normalize(uint16_t* q, uint16_t* k, float* scales, int B, int T, int H, int head_dim, void* stream);
 /* Plain scaled-dot-product attention (abi 5; README.md:58 --no-use-cosine-attention, PARITY UNPINNED: the snapshot always normalises q, k):
  * o = softmax(q k^T / sqrt(head_dim)) v on q, k as they are, the row maximum subtracted inside the softmax (the logits of unnormalised rows
  * are unbounded); lse = log sum exp of the scaled logits.  Same layouts and shape dispatch as mapdit_attn_cos_fwd, T <= 256.  Its backward IS
@@ -367,7 +375,8 @@ int mapdit_attn_cos_bwd(const uint16_t* qn, const uint16_t* kn, const uint16_t* 
                         int head_dim, void* stream);
 /* Same backward with the normalisation Jacobian of q^ = q * s, k^ = k * s (s = 8 / (|.| + 1e-4), attention.py:43 through
  * src/utils.py:19-23) and the head merge fused into the two passes: writes dqkv [B*T, 3*H*64] = grad of the QKV projection's
- * output directly.  scales = the fp32 [2][B*H][T] array MAPDIT_EPI_QKV_HEADS wrote.  head_dim 64, T in {64, 128, 256} or a multiple of 256. */
+ * output directly.  scales = the fp32 [2][B*H][T] array MAPDIT_EPI_QKV_HEADS wrote (head_dim 72: mapdit_attn_cos_fwd_rawqk_save /
+ * mapdit_qk_cos_normalize).  head_dim 64 or 72, T in {64, 128, 256} or a multiple of 256 up to 16,384. */
 int mapdit_attn_cos_bwd_fused(const uint16_t* qn, const uint16_t* kn, const uint16_t* v, const uint16_t* dO, const uint16_t* O,
                               const float* lse, float* delta, const float* scales, uint16_t* dqkv, int B, int T, int H,
                               int head_dim, void* stream);
@@ -632,6 +641,7 @@ int mapdit_attn_cos_fwd_rawqk_f16(const uint16_t* q, const uint16_t* k, const ui
                                   int head_dim, void* stream);
 int mapdit_attn_cos_fwd_rawqk_save_f16(uint16_t* q, uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, float* scales, int B, int T,
                                        int H, int head_dim, void* stream);
+int mapdit_qk_cos_normalize_f16(uint16_t* q, uint16_t* k, float* scales, int B, int T, int H, int head_dim, void* stream);
 int mapdit_attn_sdpa_fwd_f16(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H,
                              int head_dim, void* stream);
 int mapdit_heads_merge_bwd_f16(const uint16_t* dqn, const uint16_t* dkn, const uint16_t* dv, int B, int T, int H, int head_dim, uint16_t* dqkv,

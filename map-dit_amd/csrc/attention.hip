@@ -1104,8 +1104,8 @@ int MD_SYM(attn72_bwd)(const uint16_t*, const uint16_t*, const uint16_t*, const 
                       uint16_t*, uint16_t*, uint16_t*, int, int, int, void*);
 int MD_SYM(attn72_bwd_fused)(const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const float*, float*,
                             const float*, uint16_t*, int, int, int, void*);
-static bool mfma72_shape(int T, int head_dim) {
-    if (head_dim != 72 || !(T == 64 || T == 128 || T == 256)) return false;
+static bool mfma72_shape(int T, int head_dim) {           // (beyond 256 tokens: 256-token tiles, as for head_dim 64)
+    if (head_dim != 72 || !(T == 64 || T == 128 || (T >= 256 && T % 256 == 0 && T <= 16384))) return false;
     static const bool enabled = [] { const char* e = getenv("MAPDIT_ATTN72"); return !(e && e[0] == '0'); }();   // read once
     return enabled;
 }
@@ -1130,7 +1130,7 @@ int MD_SYM(attn_generic_fwd_max)(const uint16_t*, const uint16_t*, const uint16_
 extern "C" int MD_SYM(attn_sdpa_fwd)(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H,
                                     int head_dim, void* stream) {
     MD_CHECK(q && k && v && o && lse, "attn_sdpa_fwd: null argument");
-    if (mfma72_shape(T, head_dim)) return MD_SYM(attn72_fwd_max)(q, k, v, o, lse, B, T, H, stream);
+    if (mfma72_shape(T, head_dim) && T <= 256) return MD_SYM(attn72_fwd_max)(q, k, v, o, lse, B, T, H, stream);
     if (!(mfma_shape(T, head_dim) && T <= 256)) return MD_SYM(attn_generic_fwd_max)(q, k, v, o, lse, B, T, H, head_dim, stream);
     const float scale = 0.125f;
     hipStream_t st = (hipStream_t)stream;
@@ -1165,7 +1165,7 @@ extern "C" int MD_SYM(attn_cos_bwd_fused)(const uint16_t* qn, const uint16_t* kn
                                          uint16_t* dqkv, int B, int T, int H, int head_dim, void* stream) {
     MD_CHECK(qn && kn && v && dO && O && lse && delta && scales && dqkv, "attn_cos_bwd_fused: null argument");
     if (mfma72_shape(T, head_dim)) return MD_SYM(attn72_bwd_fused)(qn, kn, v, dO, O, lse, delta, scales, dqkv, B, T, H, stream);
-    MD_CHECK(mfma_shape(T, head_dim), "attn_cos_bwd_fused: head_dim=%d, T=%d unsupported (64 with 64, 128 or a multiple of 256 tokens; 72 with 64, 128, 256)", head_dim, T);
+    MD_CHECK(mfma_shape(T, head_dim), "attn_cos_bwd_fused: head_dim=%d, T=%d unsupported (64 or 72 with 64, 128 or a multiple of 256 tokens)", head_dim, T);
     const float scale = 0.125f;
     const float* sq = scales;
     const float* sk = scales + (size_t)B * H * T;

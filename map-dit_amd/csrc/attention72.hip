@@ -236,11 +236,18 @@ __device__ __forceinline__ bf16x8_t frag_tr_rows2(const char* tile, int d0, int 
 // (mapdit_attn_cos_bwd_fused, head_dim 72).  The separate split / normalise pass over a [M, 3D] QKV result is gone in training too.
 // MAXSUB (mapdit_attn_sdpa_fwd, head_dim 72: q, k stay unnormalised - README.md:58 off form, parity unpinned): the row maximum is found in a
 // first sweep of the S products and subtracted in the second; lse = max + log(sum).
-template <int T, bool RAW, bool SAVE = false, bool MAXSUB = false>
+// MULTI (heads of more than 256 tokens, a multiple of 256; T = 256 is then the tile): grid (Ttot / 256 query tiles, heads).  A workgroup owns
+// 256 queries and loops over the head's key tiles, restaging K and V; lsum and the output accumulators carry across the tiles with no
+// rescaling (|logit| <= sqrt(72) = 8.49: exp < 4.9e3 fits the 16-bit P operand, a row sum over 16,384 keys fits fp32 with room to spare).
+// Every workgroup of a head reads the same key rows, so MULTI never writes q or k back (no SAVE form: mapdit_qk_cos_normalize runs first
+// in training); the inference form (RAW) normalises each K tile privately in LDS, Ttot / 256 times per head.
+// MULTI = false leaves no trace of the tile loop in the code.
+template <int T, bool RAW, bool SAVE = false, bool MAXSUB = false, bool MULTI = false>
 __global__ __launch_bounds__(Geo<T>::NTH) void attn72_fwd_kernel(const bf16_t* qn, const bf16_t* kn,
                                                                 const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
                                                                 float* __restrict__ lse, int H, float scale, float* __restrict__ sq_out = nullptr,
                                                                 float* __restrict__ sk_out = nullptr) {
+    static_assert(!MULTI || (T == 256 && !SAVE && !MAXSUB), "tiled form: 256-token tiles, nothing written back, bounded logits");
     using G = Geo<T>;
     constexpr int TILE = T * RS2 + 64;                 // (+ 64: the reads past the last row stay inside the array)
     constexpr int SM = 2 * TILE;
@@ -249,21 +256,25 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_fwd_kernel(const bf16_t* q
     char* vs_ = smem + TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h2 = lane >> 5;
-    const size_t bh = blockIdx.x;
-    const int q0 = wave * 32;
-    // the head's K and V are contiguous [T][72] blocks: chunk i of the block goes to byte 16 i of its tile
+    const size_t bh = MULTI ? blockIdx.y : blockIdx.x;
+    const int Ttot = MULTI ? (int)gridDim.x * T : T;   // tokens per head
+    const int ntiles = MULTI ? (int)gridDim.x : 1;
+    const int q0 = (MULTI ? (int)blockIdx.x * T : 0) + wave * 32;
+    // the head's K and V are contiguous [Ttot][72] blocks: chunk i of a tile goes to byte 16 i of its LDS image
     constexpr int CHUNKS = T * CH, PER = (CHUNKS + G::NTH - 1) / G::NTH;
-    u32x4v kc[PER], vc[PER];
-    const u32x4v* ksrc = (const u32x4v*)(kn + bh * T * HD);
-    const u32x4v* vsrc = (const u32x4v*)(v + bh * T * HD);
+    u32x4v kc[PER], vc[PER];                           // single tile: its loads go first, ahead of the wave's own rows
+    const u32x4v* ksrc = (const u32x4v*)(kn + bh * Ttot * HD);
+    const u32x4v* vsrc = (const u32x4v*)(v + bh * Ttot * HD);
+    if (!MULTI) {
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int i = tid + k * G::NTH;
-        if (i < CHUNKS) { kc[k] = ksrc[i]; vc[k] = vsrc[i]; }
+        for (int k = 0; k < PER; ++k) {
+            const int i = tid + k * G::NTH;
+            if (i < CHUNKS) { kc[k] = ksrc[i]; vc[k] = vsrc[i]; }
+        }
     }
     bf16x8_t qf[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = frag_global(qn + (bh * T + q0 + r) * HD, ks, h2);
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = frag_global(qn + (bh * Ttot + q0 + r) * HD, ks, h2);
     if (RAW) {
         float ss = 0.f;
 #pragma unroll
@@ -284,10 +295,34 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_fwd_kernel(const bf16_t* q
             if (h2 == 0) sq_out[bh * T + q0 + r] = sc;
         }
     }
+    f32x16_t oa[DT] = {};
+    float lsum = 0.f, mrow = 0.f;
+    int kt0 = 0;                                       // key tiles (the staging registers of a tile live inside its iteration;
+    do {                                               //  do / while: with MULTI = false the compiler never sees a loop)
+    if (MULTI && kt0) __syncthreads();                 // every wave is done with the previous tile's images
+    if (MULTI) {                                       // K, then V, through the same staging registers: with both in flight beside the
+#pragma unroll                                         // carried accumulators the kernel went over 128 VGPRs (one workgroup per CU instead of two)
+        for (int w = 0; w < 2; ++w) {
+            const u32x4v* src = (w ? vsrc : ksrc) + (size_t)kt0 * CHUNKS;
+            char* dst = w ? vs_ : ks_;
+            u32x4v t_[PER];
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int i = tid + k * G::NTH;
-        if (i < CHUNKS) { *(u32x4v*)(ks_ + i * 16) = kc[k]; *(u32x4v*)(vs_ + i * 16) = vc[k]; }
+            for (int k = 0; k < PER; ++k) {
+                const int i = tid + k * G::NTH;
+                if (i < CHUNKS) t_[k] = src[i];
+            }
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int i = tid + k * G::NTH;
+                if (i < CHUNKS) *(u32x4v*)(dst + i * 16) = t_[k];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int i = tid + k * G::NTH;
+            if (i < CHUNKS) { *(u32x4v*)(ks_ + i * 16) = kc[k]; *(u32x4v*)(vs_ + i * 16) = vc[k]; }
+        }
     }
     if (tid < 4) { *(uint4*)(ks_ + T * RS2 + tid * 16) = make_uint4(0, 0, 0, 0); *(uint4*)(vs_ + T * RS2 + tid * 16) = make_uint4(0, 0, 0, 0); }
     __syncthreads();
@@ -324,8 +359,6 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_fwd_kernel(const bf16_t* q
         }
     }
 
-    f32x16_t oa[DT] = {};
-    float lsum = 0.f, mrow = 0.f;
     if (MAXSUB) {
         float mx = -3.0e38f;
         for (int kt = 0; kt < G::NT; ++kt) {
@@ -353,6 +386,7 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_fwd_kernel(const bf16_t* q
                 oa[dt] = MFMA32(pa, frag_tr_rows2(vs_, 32 * dt, 32 * kt + 16 * s2, lane), oa[dt]);
         }
     }
+    } while (MULTI && ++kt0 < ntiles);
     lsum += __shfl_xor(lsum, 32, 64);
     const int b = (int)(bh / H), hh = (int)(bh % H);
     const int D = H * HD;
@@ -361,12 +395,14 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_fwd_kernel(const bf16_t* q
 #pragma unroll
     for (int i = 0; i < 16; ++i) rs[i] = __shfl(inv_l, acc_row(i, lane), 64);
     __syncthreads();                                   // K / V tiles are dead: reuse them as store buffers
-    store_wave_tile(smem + wave * WT_BYTES, oa, rs, o + ((size_t)b * T + q0) * D + hh * HD, D, lane);
-    if (lane < 32) lse[bh * T + q0 + r] = mrow + __logf(lsum);
+    store_wave_tile(smem + wave * WT_BYTES, oa, rs, o + ((size_t)b * Ttot + q0) * D + hh * HD, D, lane);
+    if (lane < 32) lse[bh * Ttot + q0 + r] = mrow + __logf(lsum);
 }
 
 // ---- backward, pass A: dQ^ (wave owns 32 queries) ----------------------------------------------------------------
-template <int T>
+// MULTI: grid (Ttot / 256 query tiles, heads); q, dO, lse, delta of the 32 owned queries stay in registers, K, V and the transposed K image
+// are restaged per 256-key tile (the LDS footprint is the tile's).  A workgroup writes the delta of its own rows only.
+template <int T, bool MULTI = false>
 __global__ __launch_bounds__(Geo<T>::NTH) void attn72_bwd_dq_kernel(const bf16_t* __restrict__ qn, const bf16_t* __restrict__ kn,
                                                                    const bf16_t* __restrict__ v, const bf16_t* __restrict__ dO,
                                                                    const bf16_t* __restrict__ O, const float* __restrict__ lse,
@@ -383,32 +419,49 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_bwd_dq_kernel(const bf16_t
     char* kts_ = smem + 2 * T * RS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h2 = lane >> 5;
-    const size_t bh = blockIdx.x;
+    static_assert(!MULTI || T == 256, "tiled form: 256-token tiles");
+    const size_t bh = MULTI ? blockIdx.y : blockIdx.x;
+    const int Ttot = MULTI ? (int)gridDim.x * T : T;   // tokens per head
+    const int ntiles = MULTI ? (int)gridDim.x : 1;
     const int b = (int)(bh / H), hh = (int)(bh % H), D = H * HD;
-    const int q0 = wave * 32;
-    Staged<T, G::NTH> sk_, sv_;
-    sk_.load(kn + bh * T * HD, HD, tid);
-    sv_.load(v + bh * T * HD, HD, tid);
+    const int q0 = (MULTI ? (int)blockIdx.x * T : 0) + wave * 32;
+    Staged<T, G::NTH> sk_, sv_;                        // single tile: its loads go first
+    if (!MULTI) {
+        sk_.load(kn + bh * Ttot * HD, HD, tid);
+        sv_.load(v + bh * Ttot * HD, HD, tid);
+    }
     bf16x8_t qf[KS], dof[KS];
     float del_p = 0.f;                      // delta_q = rowsum(dO * O): this lane's share of the 72 features
-    const bf16_t* dorow = dO + ((size_t)b * T + q0 + r) * D + hh * HD;
-    const bf16_t* orow = O + ((size_t)b * T + q0 + r) * D + hh * HD;
+    const bf16_t* dorow = dO + ((size_t)b * Ttot + q0 + r) * D + hh * HD;
+    const bf16_t* orow = O + ((size_t)b * Ttot + q0 + r) * D + hh * HD;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        qf[ks] = frag_global(qn + (bh * T + q0 + r) * HD, ks, h2);
+        qf[ks] = frag_global(qn + (bh * Ttot + q0 + r) * HD, ks, h2);
         dof[ks] = frag_global(dorow, ks, h2);
         const bf16x8_t of = frag_global(orow, ks, h2);
 #pragma unroll
         for (int e = 0; e < 8; ++e) del_p += up16((bf16_t)dof[ks][e]) * up16((bf16_t)of[e]);
     }
-    const float lse_q = lse[bh * T + q0 + r];
-    sk_.template store<T>(ks_, kts_, 0, tid);
-    sv_.template store<T>(vs_, nullptr, 0, tid);
+    const float lse_q = lse[bh * Ttot + q0 + r];
+    if (!MULTI) {
+        sk_.template store<T>(ks_, kts_, 0, tid);
+        sv_.template store<T>(vs_, nullptr, 0, tid);
+    }
     const float del_q = del_p + __shfl_xor(del_p, 32, 64);
-    if (h2 == 0) delta[bh * T + q0 + r] = del_q;       // consumed by the dK/dV pass (launched after this kernel)
-    __syncthreads();
+    if (h2 == 0) delta[bh * Ttot + q0 + r] = del_q;    // consumed by the dK/dV pass (launched after this kernel)
 
     f32x16_t dq[DT] = {};
+    int kt0 = 0;                                       // key tiles
+    do {
+    if (MULTI) {
+        if (kt0) __syncthreads();                      // every wave is done with the previous tile's images
+        Staged<T, G::NTH> skt_, svt_;
+        skt_.load(kn + (bh * Ttot + (size_t)kt0 * T) * HD, HD, tid);
+        svt_.load(v + (bh * Ttot + (size_t)kt0 * T) * HD, HD, tid);
+        skt_.template store<T>(ks_, kts_, 0, tid);
+        svt_.template store<T>(vs_, nullptr, 0, tid);
+    }
+    __syncthreads();
 #pragma unroll 1
     for (int kt = 0; kt < G::NT; ++kt) {
         f32x16_t st = {}, dp = {};
@@ -430,20 +483,23 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_bwd_dq_kernel(const bf16_t
                 dq[dt] = MFMA32(a, frag_tr<T>(kts_, 32 * dt, 32 * kt + 16 * s2, lane), dq[dt]);
         }
     }
+    } while (MULTI && ++kt0 < ntiles);
     float one[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) one[i] = 1.f;
     __syncthreads();                                   // every wave is done with the K / V images: reuse them as store buffers
     if (dqkv) {
-        const float s_row = sq[bh * T + q0 + r];
-        store_wave_tile_jac72(smem + wave * WJ_BYTES, dq, dqkv + ((size_t)b * T + q0) * (3 * D) + hh * HD, 3 * D, qf, s_row, lane);
+        const float s_row = sq[bh * Ttot + q0 + r];
+        store_wave_tile_jac72(smem + wave * WJ_BYTES, dq, dqkv + ((size_t)b * Ttot + q0) * (3 * D) + hh * HD, 3 * D, qf, s_row, lane);
     } else {
-        store_wave_tile(smem + wave * WT_BYTES, dq, one, dqn + (bh * T + q0) * HD, HD, lane);
+        store_wave_tile(smem + wave * WT_BYTES, dq, one, dqn + (bh * Ttot + q0) * HD, HD, lane);
     }
 }
 
 // ---- backward, pass B: dK^, dV (wave owns 32 keys) ---------------------------------------------------------------
-template <int T>
+// MULTI: grid (Ttot / 256 key tiles, heads); k, v of the 32 owned keys stay in registers, Q, dO, their half-tile transposed images and the
+// lse / delta rows are restaged per 256-query tile; dK, dV accumulate across the tiles.
+template <int T, bool MULTI = false>
 __global__ __launch_bounds__(Geo<T>::NTH) void attn72_bwd_dkv_kernel(const bf16_t* __restrict__ qn, const bf16_t* __restrict__ kn,
                                                                     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dO,
                                                                     const float* __restrict__ lse, const float* __restrict__ delta,
@@ -462,24 +518,41 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_bwd_dkv_kernel(const bf16_
     float* del_s = lse_s + T;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h2 = lane >> 5;
-    const size_t bh = blockIdx.x;
+    static_assert(!MULTI || T == 256, "tiled form: 256-token tiles");
+    const size_t bh = MULTI ? blockIdx.y : blockIdx.x;
+    const int Ttot = MULTI ? (int)gridDim.x * T : T;   // tokens per head
+    const int ntiles = MULTI ? (int)gridDim.x : 1;
     const int b = (int)(bh / H), hh = (int)(bh % H), D = H * HD;
-    const int k0 = wave * 32;
-    Staged<T, G::NTH> sq_, sdo_;
-    sq_.load(qn + bh * T * HD, HD, tid);
-    sdo_.load(dO + (size_t)b * T * D + hh * HD, D, tid);
+    const int k0 = (MULTI ? (int)blockIdx.x * T : 0) + wave * 32;
+    Staged<T, G::NTH> sq_, sdo_;                       // single tile: its loads go first
+    if (!MULTI) {
+        sq_.load(qn + bh * Ttot * HD, HD, tid);
+        sdo_.load(dO + (size_t)b * Ttot * D + hh * HD, D, tid);
+    }
     bf16x8_t kf[KS], vf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        kf[ks] = frag_global(kn + (bh * T + k0 + r) * HD, ks, h2);
-        vf[ks] = frag_global(v + (bh * T + k0 + r) * HD, ks, h2);
+        kf[ks] = frag_global(kn + (bh * Ttot + k0 + r) * HD, ks, h2);
+        vf[ks] = frag_global(v + (bh * Ttot + k0 + r) * HD, ks, h2);
     }
-    for (int i = tid; i < T; i += G::NTH) { lse_s[i] = lse[bh * T + i]; del_s[i] = delta[bh * T + i]; }
-    sq_.template store<G::TH>(qs_, qts_, 0, tid);
-    sdo_.template store<G::TH>(dos_, dots_, 0, tid);
-    __syncthreads();
 
     f32x16_t dk[DT] = {}, dvv[DT] = {};
+    int qt0 = 0;                                       // query tiles
+    do {
+    if (MULTI) {
+        if (qt0) __syncthreads();                      // every wave is done with the previous tile's rows and images
+        for (int i = tid; i < T; i += G::NTH) { lse_s[i] = lse[bh * Ttot + qt0 * T + i]; del_s[i] = delta[bh * Ttot + qt0 * T + i]; }
+        Staged<T, G::NTH> sqt_, sdot_;                 // (this form sits at the 256-VGPR limit with 6 registers in scratch; staging
+        sqt_.load(qn + (bh * Ttot + (size_t)qt0 * T) * HD, HD, tid);      //  Q and dO one after the other through one register set did not change that)
+        sdot_.load(dO + ((size_t)b * Ttot + (size_t)qt0 * T) * D + hh * HD, D, tid);
+        sqt_.template store<G::TH>(qs_, qts_, 0, tid);
+        sdot_.template store<G::TH>(dos_, dots_, 0, tid);
+    } else {
+        for (int i = tid; i < T; i += G::NTH) { lse_s[i] = lse[bh * Ttot + i]; del_s[i] = delta[bh * Ttot + i]; }
+        sq_.template store<G::TH>(qs_, qts_, 0, tid);
+        sdo_.template store<G::TH>(dos_, dots_, 0, tid);
+    }
+    __syncthreads();
 #pragma unroll 1
     for (int half = 0; half < G::HALVES; ++half) {
         if (half > 0) {                                // second half of the queries: rebuild both images from the LDS rows
@@ -515,20 +588,62 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn72_bwd_dkv_kernel(const bf16_
             }
         }
     }
+    } while (MULTI && ++qt0 < ntiles);
     float one[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) one[i] = 1.f;
     __syncthreads();                                   // Q / dO tiles are dead: reuse them as store buffers
     if (dqkv) {                                        // k section with the Jacobian of k^, v section as is: [B*T][3 H*72]
-        const float s_row = sk[bh * T + k0 + r];
-        bf16_t* dst = dqkv + ((size_t)b * T + k0) * (3 * D) + D + hh * HD;
+        const float s_row = sk[bh * Ttot + k0 + r];
+        bf16_t* dst = dqkv + ((size_t)b * Ttot + k0) * (3 * D) + D + hh * HD;
         store_wave_tile_jac72(smem + wave * WJ_BYTES, dk, dst, 3 * D, kf, s_row, lane);
         store_wave_tile(smem + wave * WJ_BYTES, dvv, one, dst + D, 3 * D, lane);
         return;
     }
     char* wbuf = smem + wave * WT_BYTES;
-    store_wave_tile(wbuf, dk, one, dkn + (bh * T + k0) * HD, HD, lane);
-    store_wave_tile(wbuf, dvv, one, dv + (bh * T + k0) * HD, HD, lane);
+    store_wave_tile(wbuf, dk, one, dkn + (bh * Ttot + k0) * HD, HD, lane);
+    store_wave_tile(wbuf, dvv, one, dv + (bh * Ttot + k0) * HD, HD, lane);
+}
+
+// ---- cosine normalisation of raw head-major q, k in place (training beyond 256 tokens) ------------------------------------------
+// The training forward of <= 256 tokens normalises q and k in place while it stages them, which is sound only because a head's key rows
+// belong to one workgroup.  With query tiles, Ttot / 256 workgroups read the same key rows, so this pass runs first: one workgroup per
+// 256 rows of q (blockIdx.y = 0) or k (1), staged through LDS as the forward stages K (16-byte chunks in, one row per thread, chunks out),
+// s = sqrt(72) / (|row| + eps) to scales [2][rows].  A workgroup reads and writes its own rows only.
+constexpr int NRM_ROWS = 256;
+__global__ __launch_bounds__(NRM_ROWS) void qk_normalize72_kernel(bf16_t* __restrict__ q, bf16_t* __restrict__ k, float* __restrict__ scales,
+                                                                  long rows) {
+    __shared__ __attribute__((aligned(16))) char tile[NRM_ROWS * RS2];
+    const int tid = threadIdx.x;
+    const long row0 = (long)blockIdx.x * NRM_ROWS;
+    const int nrows = rows - row0 < NRM_ROWS ? (int)(rows - row0) : NRM_ROWS;
+    u32x4v* g = (u32x4v*)((blockIdx.y ? k : q) + row0 * HD);
+    float* sc_out = scales + (blockIdx.y ? rows : 0) + row0;
+    for (int i = tid; i < nrows * CH; i += NRM_ROWS) *(u32x4v*)(tile + i * 16) = g[i];
+    __syncthreads();
+    if (tid < nrows) {                                     // (rows 36 dwords apart: conflict-free 16-byte accesses)
+        char* row = tile + tid * RS2;
+        u32x4v c9[CH];
+        float ss = 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            c9[c] = *(const u32x4v*)(row + c * 16);
+            const uint32_t w[4] = {c9[c].x, c9[c].y, c9[c].z, c9[c].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float a = lo16(w[e]), b2 = hi16(w[e]); ss += a * a + b2 * b2; }
+        }
+        const float sc = sqrtf((float)HD) / (sqrtf(ss) + NORM_EPS);
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            u32x4v u = c9[c];
+            u.x = pack16(lo16(u.x) * sc, hi16(u.x) * sc); u.y = pack16(lo16(u.y) * sc, hi16(u.y) * sc);
+            u.z = pack16(lo16(u.z) * sc, hi16(u.z) * sc); u.w = pack16(lo16(u.w) * sc, hi16(u.w) * sc);
+            *(u32x4v*)(row + c * 16) = u;
+        }
+        sc_out[tid] = sc;
+    }
+    __syncthreads();
+    for (int i = tid; i < nrows * CH; i += NRM_ROWS) g[i] = *(const u32x4v*)(tile + i * 16);
 }
 
 // ---- head split / merge around the attention for head_dim 72 ---------------------------------------------------------
@@ -647,20 +762,34 @@ int MD_SYM(qkv_merge_bwd72)(const uint16_t* qkv, int B, int T, int H, const uint
     return MAPDIT_OK;
 }
 
-#define ATTN72_DISPATCH(T_, CALL)                                                       \
+// TT = the tile of keys / queries a workgroup stages at a time: the whole head up to 256 tokens, 256 of them beyond (T % 256 == 0);
+// GRID = one workgroup per head, or (tiles, heads).  ATTN72_DISPATCH_ONE: kernels without a tiled form.
+constexpr int T_MAX72 = 16384;
+#define ATTN72_DISPATCH_ONE(T_, CALL)                                                   \
     switch (T_) {                                                                       \
-        case 64: { constexpr int TT = 64; CALL; break; }                                \
-        case 128: { constexpr int TT = 128; CALL; break; }                              \
-        case 256: { constexpr int TT = 256; CALL; break; }                              \
+        case 64: { constexpr int TT = 64; constexpr bool MT = false; const dim3 GRID(B * H); CALL; break; }   \
+        case 128: { constexpr int TT = 128; constexpr bool MT = false; const dim3 GRID(B * H); CALL; break; } \
+        case 256: { constexpr int TT = 256; constexpr bool MT = false; const dim3 GRID(B * H); CALL; break; } \
         default: mapdit_set_error("attention72: T=%d unsupported (64, 128, 256)", T_); return MAPDIT_ERR_ARG; \
     }
+#define ATTN72_DISPATCH(T_, CALL)                                                       \
+    switch ((T_) > 256 && (T_) % 256 == 0 && (T_) <= T_MAX72 ? 512 : (T_)) {            \
+        case 64: { constexpr int TT = 64; constexpr bool MT = false; const dim3 GRID(B * H); CALL; break; }   \
+        case 128: { constexpr int TT = 128; constexpr bool MT = false; const dim3 GRID(B * H); CALL; break; } \
+        case 256: { constexpr int TT = 256; constexpr bool MT = false; const dim3 GRID(B * H); CALL; break; } \
+        case 512: { constexpr int TT = 256; constexpr bool MT = true; const dim3 GRID((T_) / 256, B * H); CALL; break; } \
+        default: mapdit_set_error("attention72: T=%d unsupported (64, 128, 256 or a multiple of 256 up to 16384)", T_); return MAPDIT_ERR_ARG; \
+    }
+#define ATTN72_CHECK_GRID(B_, H_) MD_CHECK((long)(B_) * (H_) <= 65535 || T <= 256, "attention72: %ld heads unsupported beyond 256 tokens (<= 65535)", (long)(B_) * (H_))
 
 // Internal entry points (dispatched to from mapdit_attn_cos_fwd / _bwd for head_dim 72).
 int MD_SYM(attn72_fwd)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H,
                       void* stream) {
     const float scale = 1.f / sqrtf((float)HD);
     hipStream_t st = (hipStream_t)stream;
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, false>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, qn, kn, v, o, lse, H, scale));
+    ATTN72_CHECK_GRID(B, H);
+    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, false, false, false, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, qn, kn, v, o, lse, H, scale,
+                                          (float*)nullptr, (float*)nullptr));
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }
@@ -668,8 +797,8 @@ int MD_SYM(attn72_fwd)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v
 int MD_SYM(attn72_fwd_max)(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H, void* stream) {
     const float scale = 1.f / sqrtf((float)HD);
     hipStream_t st = (hipStream_t)stream;
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, false, false, true>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, q, k, v, o, lse, H, scale,
-                                          (float*)nullptr, (float*)nullptr));
+    ATTN72_DISPATCH_ONE(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, false, false, true, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, q, k, v, o, lse, H, scale,
+                                              (float*)nullptr, (float*)nullptr));
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }
@@ -680,22 +809,45 @@ extern "C" int MD_SYM(attn_cos_fwd_rawqk)(const uint16_t* q, const uint16_t* k, 
     MD_CHECK(head_dim == HD, "attn_cos_fwd_rawqk: head_dim=%d unsupported (72)", head_dim);
     const float scale = 1.f / sqrtf((float)HD);
     hipStream_t st = (hipStream_t)stream;
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, true>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, q, k, v, o, lse, H, scale));
+    ATTN72_CHECK_GRID(B, H);
+    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, true, false, false, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, q, k, v, o, lse, H, scale,
+                                          (float*)nullptr, (float*)nullptr));
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+// Cosine normalisation of raw head-major q, k [B*H][T][72] in place, scales s = sqrt(72) / (|row| + eps) to [2][B*H][T]: the first step
+// of the training forward beyond 256 tokens (any T).
+extern "C" int MD_SYM(qk_cos_normalize)(uint16_t* q, uint16_t* k, float* scales, int B, int T, int H, int head_dim, void* stream) {
+    MD_CHECK(q && k && scales && B > 0 && H > 0 && T > 0, "qk_cos_normalize: null/empty argument");
+    MD_CHECK(head_dim == HD, "qk_cos_normalize: head_dim=%d unsupported (72)", head_dim);
+    const long rows = (long)B * H * T;
+    MD_CHECK((rows + NRM_ROWS - 1) / NRM_ROWS <= 0x7fffffffL, "qk_cos_normalize: %ld rows unsupported", rows);
+    hipLaunchKernelGGL(qk_normalize72_kernel, dim3((unsigned)((rows + NRM_ROWS - 1) / NRM_ROWS), 2), dim3(NRM_ROWS), 0, (hipStream_t)stream, q, k,
+                       scales, rows);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }
 
 // Training forward on raw head-major q, k (MAPDIT_EPI_QKV_HEADS_RAW): normalises them in place and keeps the scales [2][B*H][T].
+// Up to 256 tokens the attention kernel does that while it stages them (a head's rows belong to one workgroup); beyond, where the query tiles
+// of a head share its key rows, mapdit_qk_cos_normalize runs first and the tiled kernel only reads.
 extern "C" int MD_SYM(attn_cos_fwd_rawqk_save)(uint16_t* q, uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, float* scales, int B,
                                               int T, int H, int head_dim, void* stream) {
     MD_CHECK(q && k && v && o && lse && scales && B > 0 && H > 0, "attn_cos_fwd_rawqk_save: null/empty argument");
     MD_CHECK(head_dim == HD, "attn_cos_fwd_rawqk_save: head_dim=%d unsupported (72)", head_dim);
     const float scale = 1.f / sqrtf((float)HD);
     hipStream_t st = (hipStream_t)stream;
+    if (T > 256) {
+        MD_CHECK(T % 256 == 0 && T <= T_MAX72, "attn_cos_fwd_rawqk_save: T=%d unsupported (64, 128, 256 or a multiple of 256 up to 16384)", T);
+        int rc = MD_SYM(qk_cos_normalize)(q, k, scales, B, T, H, head_dim, stream);
+        if (rc != MAPDIT_OK) return rc;
+        return MD_SYM(attn72_fwd)(q, k, v, o, lse, B, T, H, stream);
+    }
     float* sq = scales;
     float* sk = scales + (size_t)B * H * T;
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, true, true>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, q, k, v, o, lse, H, scale,
-                                          sq, sk));
+    ATTN72_DISPATCH_ONE(T, hipLaunchKernelGGL((attn72_fwd_kernel<TT, true, true, false, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, q, k, v, o, lse, H, scale,
+                                              sq, sk));
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }
@@ -707,10 +859,11 @@ int MD_SYM(attn72_bwd_fused)(const uint16_t* qn, const uint16_t* kn, const uint1
     hipStream_t st = (hipStream_t)stream;
     const float* sq = scales;
     const float* sk = scales + (size_t)B * H * T;
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dq_kernel<TT>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, O, lse,
+    ATTN72_CHECK_GRID(B, H);
+    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dq_kernel<TT, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, O, lse,
                                           delta, (bf16_t*)nullptr, H, scale, sq, dqkv));
     MD_LAUNCH_CHECK();
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dkv_kernel<TT>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, lse,
+    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dkv_kernel<TT, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, lse,
                                           delta, (bf16_t*)nullptr, (bf16_t*)nullptr, H, scale, sk, dqkv));
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
@@ -720,11 +873,12 @@ int MD_SYM(attn72_bwd)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v
                       const float* lse, float* delta, uint16_t* dqn, uint16_t* dkn, uint16_t* dv, int B, int T, int H, void* stream) {
     const float scale = 1.f / sqrtf((float)HD);
     hipStream_t st = (hipStream_t)stream;
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dq_kernel<TT>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, O, lse,
-                                          delta, dqn, H, scale));
+    ATTN72_CHECK_GRID(B, H);
+    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dq_kernel<TT, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, O, lse,
+                                          delta, dqn, H, scale, (const float*)nullptr, (bf16_t*)nullptr));
     MD_LAUNCH_CHECK();
-    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dkv_kernel<TT>), dim3(B * H), dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, lse,
-                                          delta, dkn, dv, H, scale));
+    ATTN72_DISPATCH(T, hipLaunchKernelGGL((attn72_bwd_dkv_kernel<TT, MT>), GRID, dim3(Geo<TT>::NTH), 0, st, qn, kn, v, dO, lse,
+                                          delta, dkn, dv, H, scale, (const float*)nullptr, (bf16_t*)nullptr));
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }

@@ -419,10 +419,11 @@ int check_cfg(const mapdit_config_t* c) {
     MD_CHECK(c->input_size % c->patch == 0, "engine: input_size %% patch != 0");
     const int g = c->input_size / c->patch, T = g * g;
     // up to 256 tokens: any count (MFMA attention for 64 / 128 / 256 tokens at head_dim 64 or 72, the generic kernels otherwise);
-    // beyond (64x64 latents at patch 2 = 1,024): the MFMA attention kernels loop over 256-token tiles - head_dim 64, bf16 / fp16
+    // beyond (64x64 latents at patch 2 = 1,024): the MFMA attention kernels loop over 256-token tiles - head_dim 64 or 72, bf16 / fp16
     const int hd_ = c->hidden / c->num_heads;
-    MD_CHECK(T >= 1 && (T <= 256 || (T % 256 == 0 && T <= 16384 && hd_ == 64 && c->precision != MAPDIT_PREC_BF16X3)),
-             "engine: %d tokens per sample unsupported (<= 256; a multiple of 256 with head_dim 64 in bf16 / f16 precision)", T);
+    MD_CHECK(T >= 1 && (T <= 256 || (T % 256 == 0 && T <= 16384 && (hd_ == 64 || hd_ == 72) && c->precision != MAPDIT_PREC_BF16X3)),
+             "engine: %d tokens per sample unsupported (<= 256; a multiple of 256 up to 16384 with head_dim 64 or 72 in bf16 / f16 precision; "
+             "head_dim=%d, precision=%d)", T, hd_, c->precision);
     MD_CHECK(!(c->mp_off & MAPDIT_OFF_NO_LAYERNORM) || (!c->rotation && c->hidden <= 2048),
              "engine: the LayerNorm form (no-layernorm off) is built for the AdaLN modulation and hidden <= 2048");
     MD_CHECK(!(c->mp_off & MAPDIT_OFF_COSINE_ATTN) || (T <= 256 && hd_ % 8 == 0),
@@ -451,7 +452,8 @@ void init_dims(mapdit_engine* e) {
     {
         const char* a = getenv("MAPDIT_ATTN72");
         const char* r = getenv("MAPDIT_ATTN72_RAW");
-        e->raw72 = !(a && a[0] == '0') && !(r && r[0] == '0') && e->hd == 72 && (e->T == 64 || e->T == 128 || e->T == 256) &&
+        // (beyond 256 tokens the same path: the training forward normalises q, k by a pass of its own first - mapdit_attn_cos_fwd_rawqk_save)
+        e->raw72 = !(a && a[0] == '0') && !(r && r[0] == '0') && e->hd == 72 && (e->T == 64 || e->T == 128 || (e->T >= 256 && e->T % 256 == 0)) &&
                    e->cfg.precision != MAPDIT_PREC_BF16X3;
     }
     e->M_max = c.max_batch * e->T;

@@ -82,6 +82,8 @@ def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--data-path", type=str, default=None)
     p.add_argument("--synthetic", action="store_true", help="N(0,1) 4x32x32 latents and uniform labels instead of a dataset")
+    p.add_argument("--synthetic-input-size", type=int, default=32,
+                   help="side of the --synthetic latents (64: 512x512 images, 1,024 tokens per sample at patch 2)")
     p.add_argument("--results-dir", type=str, required=True)
     p.add_argument("--model", type=str, choices=list(DIT_MODELS.keys()), default="DiT-XS/2")
     p.add_argument("--num-classes", type=int, default=1000)
@@ -134,7 +136,7 @@ def main(argv=None):
     per_rank = hi - lo
 
     if args.synthetic:
-        args.in_channels, args.input_size = 4, 32
+        args.in_channels, args.input_size = 4, int(args.synthetic_input_size)
         args.stats_mean, args.stats_std = [0.0] * 4, [1.0] * 4
         loader = None
     else:
@@ -184,7 +186,7 @@ def main(argv=None):
         if loader is None:
             g = torch.Generator(device=dev).manual_seed(args.seed + 1 + rank)
             while True:
-                yield (torch.randn(per_rank, 4, 32, 32, device=dev, generator=g),
+                yield (torch.randn(per_rank, 4, args.input_size, args.input_size, device=dev, generator=g),
                        torch.randint(0, args.num_classes, (per_rank,), device=dev, generator=g))
         epoch = 0
         while True:

@@ -24,16 +24,17 @@ def main():
     ap.add_argument("--model", default="DiT-XL/2")
     ap.add_argument("--n", type=int, default=128, help="images per batch (the CFG batch is 2n rows)")
     ap.add_argument("--steps", type=int, default=50, help="timed denoise steps (of the 250-step schedule)")
+    ap.add_argument("--input-size", type=int, default=32, help="side of the latents (64: 1,024 tokens per sample at patch 2)")
     ap.add_argument("--cfg-scale", type=float, default=1.5)
     ap.add_argument("--precision", choices=["bf16", "f16"], default="bf16")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    model = DIT_MODELS[args.model](in_channels=4, input_size=32, num_classes=1000).to(dev).eval().requires_grad_(False)
+    model = DIT_MODELS[args.model](in_channels=4, input_size=args.input_size, num_classes=1000).to(dev).eval().requires_grad_(False)
     model.gemm_precision = args.precision
     d = create_diffusion("250")
     n = args.n
-    z = torch.randn(n, 4, 32, 32, device=dev)
+    z = torch.randn(n, 4, args.input_size, args.input_size, device=dev)
     z = torch.cat([z, z], 0)
     y = torch.cat([torch.randint(0, 1000, (n,), device=dev), torch.full((n,), 1000, device=dev)])
     kw = dict(y=y, cfg_scale=args.cfg_scale)
