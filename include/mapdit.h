@@ -466,6 +466,26 @@ int mapdit_obj_loss_bwd(const float* G, const float* g_loss, const float* g_mse,
 int mapdit_obj_step(const float* model_out, const float* x, const float* noise, const int64_t* t, const float* tab,
                     const float* otab, int nsteps, int mean_type, int var_type, int clip_denoised, int mode, float eta,
                     float* sample, float* pred_xstart, int N, int per_sample, void* stream);
+/* The sampler hooks of the reference (denoised_fn, cond_fn), additive within abi 5.  mapdit_obj_xstart writes the raw x0 prediction
+ * of p_mean_variance (:317-322: model_out for START_X, else sqrt_recip_acp x - sqrt_recipm1_acp model_out), unclipped: what a
+ * denoised_fn is handed before the step is finished. */
+int mapdit_obj_xstart(const float* model_out, const float* x, const int64_t* t, const float* tab, int nsteps, int mean_type,
+                      int var_type, float* xstart, int N, int per_sample, void* stream);
+/* mapdit_obj_step with three more nullable pointers of x's shape.  xstart_in (what denoised_fn returned) replaces the kernel's own
+ * x0 prediction; clip_denoised is applied after it (process_xstart, :310-315).  cond_grad is cond_fn's gradient.  Mode 0 applies
+ * condition_mean (:346-356): mean += variance * cond_grad, pred_xstart unchanged, the noise term (none at t = 0) added after it;
+ * variance = exp(model log-variance), but for FIXED_SMALL at t = 0, where the reference's posterior_variance is 0 (its clipped
+ * log repeats entry 1).  Modes 1 and 2 apply condition_score (:358-374): eps = (sqrt_recip_acp x - x0) / sqrt_recipm1_acp -
+ * sqrt(1 - acp) cond_grad, x0 = sqrt_recip_acp x - sqrt_recipm1_acp eps (not clipped again; this is pred_xstart; computed as
+ * x0 += sqrt_recipm1_acp sqrt(1 - acp) cond_grad, which spares the round trip's cancellation), and the DDIM
+ * update re-derives eps from that x0.  `mean` receives the (conditioned) posterior mean coef1 x0 + coef2 x.  With both hook
+ * pointers null the outputs equal mapdit_obj_step's.  At least one of sample / pred_xstart / mean is given; sample may be null
+ * when only the other two are wanted (condition_score on its own; mode 1 then needs no noise).  model_out may be null when
+ * xstart_in is given and the step does not read the learned variance (mode 0 with LEARNED_RANGE and noise or cond_grad does). */
+int mapdit_obj_step_guided(const float* model_out, const float* x, const float* noise, const int64_t* t, const float* tab,
+                           const float* otab, int nsteps, int mean_type, int var_type, int clip_denoised, int mode, float eta,
+                           const float* xstart_in, const float* cond_grad, float* sample, float* pred_xstart, float* mean, int N,
+                           int per_sample, void* stream);
 /* _vb_terms_bpd (:682-713) and calc_bpd_loop's per-timestep terms (:805-858): vb (bits; decoder NLL at t = 0, KL otherwise),
  * xstart_mse and, when noise is given, mse of the eps re-derived from pred_xstart.  Each lands at [n * ld + (col_from_t ?
  * nsteps - 1 - t[n] : 0)]: col_from_t = 1 with ld = nsteps fills the column of [N][nsteps] arrays that calc_bpd_loop's loop order

@@ -149,6 +149,8 @@ _SIGS = {
     "mapdit_obj_loss_fwd": [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp],
     "mapdit_obj_loss_bwd": [vp, vp, vp, vp, vp, ci, ci, ci, vp],
     "mapdit_obj_step": [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, ci, ci, vp],
+    "mapdit_obj_xstart": [vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp],
+    "mapdit_obj_step_guided": [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, ci, vp],
     "mapdit_obj_vb_terms": [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp],
     "mapdit_prior_bpd": [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp],
     "mapdit_engine_create": [C.POINTER(Config), ci, vp, C.c_size_t, vp, C.POINTER(vp)],

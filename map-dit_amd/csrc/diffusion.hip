@@ -411,6 +411,84 @@ __global__ void obj_step_kernel(const float* __restrict__ mo, const float* __res
     if (xstart) xstart[i] = xs;
 }
 
+// The raw x0 prediction of p_mean_variance (:317-322), before process_xstart: what a denoised_fn hook is handed.
+__global__ void obj_xstart_kernel(const float* __restrict__ mo, const float* __restrict__ x, const long* __restrict__ t,
+                                  const float* __restrict__ tab, int nsteps, int mean_type, int var_type,
+                                  float* __restrict__ xstart, long total, int per) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long n = i / per, e = i % per;
+    const long tt = MAPDIT_CHECKED_INDEX(diffusion, t[n], nsteps, MAPDIT_DEVERR_TIMESTEP);
+    const long ostride = var_type == OBJ_LEARNED_RANGE ? 2 * (long)per : (long)per;
+    const float m = mo[n * ostride + e];
+    xstart[i] = mean_type == OBJ_START_X ? m : tab[2 * nsteps + tt] * x[i] - tab[3 * nsteps + tt] * m;
+}
+
+// obj_step_kernel with the sampler hooks of the reference folded in.  xstart_in (what denoised_fn returned) replaces the kernel's own
+// x0 prediction and is clipped after it, as process_xstart does (:310-315).  cond_grad = cond_fn's gradient: p_sample applies
+// condition_mean (:346-356: mean += variance x grad, pred_xstart unchanged, the noise added after it); the DDIM modes apply
+// condition_score (:358-374: eps moved by -sqrt(1 - acp) x grad, x0 re-derived from it and NOT clipped again: x0 moves by
+// sqrt_recipm1_acp x sqrt(1 - acp) x grad), and the DDIM update then re-derives eps from that x0 as the reference does.  `mean` receives the (conditioned) posterior mean; `sample` may be null
+// when only pred_xstart / mean are wanted.  mo may be null when nothing is read from it (see mapdit_obj_step_guided).
+__global__ void obj_step_guided_kernel(const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ noise,
+                                       const long* __restrict__ t, const float* __restrict__ tab, const float* __restrict__ otab,
+                                       int nsteps, int mean_type, int var_type, int clip, int mode, float eta,
+                                       const float* __restrict__ xstart_in, const float* __restrict__ cond_grad,
+                                       float* __restrict__ sample, float* __restrict__ xstart, float* __restrict__ mean, long total,
+                                       int per) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long n = i / per, e = i % per;
+    const long tt = MAPDIT_CHECKED_INDEX(diffusion, t[n], nsteps, MAPDIT_DEVERR_TIMESTEP);
+    const bool learned = var_type == OBJ_LEARNED_RANGE;
+    const long ostride = learned ? 2 * (long)per : (long)per;
+    const float x_t = x[i];
+    const ObjCoef c = obj_coef(tab, otab, nsteps, tt);
+    float xs;
+    if (xstart_in) {
+        xs = xstart_in[i];
+    } else {
+        const float m = mo[n * ostride + e];
+        xs = mean_type == OBJ_START_X ? m : c.ra * x_t - c.rm1 * m;
+    }
+    if (clip) xs = fminf(fmaxf(xs, -1.f), 1.f);
+    float out = 0.f, mu;
+    if (mode == OBJ_STEP_PSAMPLE) {
+        mu = c.c1 * xs + c.c2 * x_t;
+        const bool draw = noise && tt != 0;
+        if (cond_grad || draw) {
+            float dlv_dv;
+            const float lv = obj_logvar(var_type, c, learned ? mo[n * ostride + per + e] : 0.f, &dlv_dv);
+            // p_mean_variance's "variance" is exp(log-variance) except for FIXED_SMALL at t = 0: posterior_variance[0] = 0, while
+            // its clipped log repeats entry 1 (:162-166, 302-305)
+            if (cond_grad) mu += (var_type == OBJ_FIXED_SMALL && tt == 0 ? 0.f : expf(lv)) * cond_grad[i];
+            out = draw ? expf(0.5f * lv) * noise[i] : 0.f;
+        }
+        out += mu;
+    } else {
+        // condition_score: eps = (ra x - x0) / rm1 - sqrt(1 - acp) grad, x0 = ra x - rm1 eps.  Written as the shift of x0 it amounts
+        // to: the round trip through eps costs |ra x| / |x0| roundings (1e-5 of a clipped x0 at the last timestep), and a zero
+        // gradient has to leave the unguided step as it is
+        if (cond_grad) xs += c.rm1 * sqrtf(1.f - otab[tt]) * cond_grad[i];
+        mu = c.c1 * xs + c.c2 * x_t;
+        if (sample) {
+            const float eps = (c.ra * x_t - xs) / c.rm1;          // _predict_eps_from_xstart
+            if (mode == OBJ_STEP_DDIM_REVERSE) {
+                const float abn = otab[2 * nsteps + tt];
+                out = xs * sqrtf(abn) + sqrtf(1.f - abn) * eps;
+            } else {
+                const float ab = otab[tt], abp = otab[nsteps + tt];
+                const float sigma = eta * sqrtf((1.f - abp) / (1.f - ab)) * sqrtf(1.f - ab / abp);
+                out = xs * sqrtf(abp) + sqrtf(1.f - abp - sigma * sigma) * eps;
+                if (tt != 0) out += sigma * noise[i];
+            }
+        }
+    }
+    if (sample) sample[i] = out;
+    if (xstart) xstart[i] = xs;
+    if (mean) mean[i] = mu;
+}
+
 // _vb_terms_bpd (:682-713) plus calc_bpd_loop's per-timestep MSEs (:829-842), one block per sample: vb (bits), xstart_mse and,
 // given the noise, mse of the re-derived eps.  Outputs land at [n * ld + (col_from_t ? nsteps - 1 - t[n] : 0)]: calc_bpd_loop
 // stacks its terms in loop order, t = T-1 first.
@@ -519,6 +597,38 @@ extern "C" int mapdit_obj_step(const float* model_out, const float* x, const flo
     const long total = (long)N * per_sample;
     hipLaunchKernelGGL(obj_step_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, model_out, x, noise, (const long*)t,
                        tab, otab, nsteps, mean_type, var_type, clip_denoised, mode, eta, sample, pred_xstart, total, per_sample);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_obj_xstart(const float* model_out, const float* x, const int64_t* t, const float* tab, int nsteps, int mean_type,
+                                 int var_type, float* xstart, int N, int per_sample, void* stream) {
+    MD_CHECK(model_out && x && t && tab && xstart && N > 0 && per_sample > 0 && nsteps > 0, "obj_xstart: null/empty argument");
+    MD_CHECK(obj_types_ok(mean_type, var_type), "obj_xstart: bad objective");
+    const long total = (long)N * per_sample;
+    hipLaunchKernelGGL(obj_xstart_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, model_out, x, (const long*)t, tab,
+                       nsteps, mean_type, var_type, xstart, total, per_sample);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_obj_step_guided(const float* model_out, const float* x, const float* noise, const int64_t* t, const float* tab,
+                                      const float* otab, int nsteps, int mean_type, int var_type, int clip_denoised, int mode,
+                                      float eta, const float* xstart_in, const float* cond_grad, float* sample, float* pred_xstart,
+                                      float* mean, int N, int per_sample, void* stream) {
+    MD_CHECK(x && t && tab && otab && (sample || pred_xstart || mean) && N > 0 && per_sample > 0 && nsteps > 0,
+             "obj_step_guided: null/empty argument");
+    MD_CHECK(obj_types_ok(mean_type, var_type) && mode >= OBJ_STEP_PSAMPLE && mode <= OBJ_STEP_DDIM_REVERSE,
+             "obj_step_guided: bad objective/mode");
+    // the model output is read for the x0 prediction (no xstart_in) and for the learned variance of a p_sample step
+    const bool reads_var = mode == OBJ_STEP_PSAMPLE && var_type == OBJ_LEARNED_RANGE && (cond_grad || noise);
+    MD_CHECK(model_out || (xstart_in && !reads_var), "obj_step_guided: this step reads the model output (null)");
+    MD_CHECK(mode != OBJ_STEP_DDIM || noise || !sample, "obj_step_guided: the DDIM step needs the noise tensor");
+    MD_CHECK(mode != OBJ_STEP_DDIM_REVERSE || eta == 0.f, "obj_step_guided: the reverse ODE is deterministic (eta must be 0)");
+    const long total = (long)N * per_sample;
+    hipLaunchKernelGGL(obj_step_guided_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, model_out, x, noise,
+                       (const long*)t, tab, otab, nsteps, mean_type, var_type, clip_denoised, mode, eta, xstart_in, cond_grad, sample,
+                       pred_xstart, mean, total, per_sample);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }

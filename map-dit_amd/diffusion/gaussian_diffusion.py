@@ -11,7 +11,16 @@ Built: every objective ``create_diffusion`` can produce — mean type EPSILON / 
 FIXED_SMALL / FIXED_LARGE, loss MSE / RESCALED_MSE / KL / RESCALED_KL.  The default (EPSILON, LEARNED_RANGE, MSE) runs the
 kernels it always ran (``mapdit_loss_fwd`` / ``mapdit_psample_step`` / ``mapdit_ddim_step``); the others run the
 generalised ``mapdit_obj_*`` kernels.  ``ModelMeanType.PREVIOUS_X`` and ``ModelVarType.LEARNED`` (never produced by
-``create_diffusion``) exist for API parity and raise NotImplementedError when exercised.
+``create_diffusion``) exist for API parity and raise NotImplementedError when exercised; for PREVIOUS_X there is nothing to match
+(the reference's ``p_mean_variance`` has no branch for it and would read the x_{t-1} prediction as eps).
+
+The sampler hooks: every reverse-process method takes ``denoised_fn`` (applied to the raw x0 prediction, before
+``clip_denoised``) and, but for ``p_mean_variance``, ``cond_fn(x, t, **model_kwargs)`` (the gradient of a conditional log
+probability; under ``SpacedDiffusion`` it sees the timesteps of the base schedule, as the model does).  A hooked step runs
+``mapdit_obj_step_guided`` - ``condition_mean`` folded into ``p_sample``, ``condition_score`` into the DDIM steps - after
+``mapdit_obj_xstart`` when ``denoised_fn`` has to see the raw prediction: at most two diffusion kernels between the model's output
+and the sample, and no torch pointwise op or host synchronisation besides the user's callables.  Without hooks every method runs
+the kernel it ran before.  ``condition_mean`` / ``condition_score`` are public, with the reference's semantics.
 """
 import enum
 import math
@@ -212,6 +221,9 @@ class GaussianDiffusion:
                 and self.loss_type == LossType.MSE)
 
     def _supported(self):
+        if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+            raise NotImplementedError("ModelMeanType.PREVIOUS_X is not built: the reference's p_mean_variance has no branch for it "
+                                      "(it would read the x_{t-1} prediction as eps), so there is no behaviour to match")
         if self.model_mean_type not in _MEAN_CODE or self.model_var_type not in _VAR_CODE or self.loss_type not in _LOSS_CODE:
             raise NotImplementedError("built: mean EPSILON / START_X, variance LEARNED_RANGE / FIXED_SMALL / FIXED_LARGE (every "
                                       "objective create_diffusion() produces); "
@@ -331,6 +343,66 @@ class GaussianDiffusion:
                              mode, float(eta), sample.data_ptr(), xstart.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
         return sample, xstart
 
+    def _hooks(self, model_output, x, t, denoised_fn, cond_fn, model_kwargs):
+        """What the hooks hand the guided kernel: denoised_fn(raw x0 prediction) (mapdit_obj_xstart feeds it) and
+        cond_fn(x, t, **model_kwargs), t mapped to the base schedule under SpacedDiffusion -> (xstart_in, cond_grad), None where
+        the hook is not given."""
+        xin = grad = None
+        if denoised_fn is not None:
+            mean_type, var_type, _ = self._kinds()
+            mo = self._prep(model_output)
+            raw = torch.empty_like(x)
+            with torch.cuda.device(x.device):
+                L.lib().obj_xstart(mo.data_ptr(), x.data_ptr(), t.data_ptr(), self._tables(x.device).data_ptr(), self.num_timesteps,
+                                   mean_type, var_type, raw.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
+            xin = self._prep(denoised_fn(raw))
+            assert xin.shape == x.shape, (tuple(xin.shape), tuple(x.shape))
+        if cond_fn is not None:
+            grad = self._cond_grad(cond_fn, x, t, model_kwargs)
+        return xin, grad
+
+    def _cond_grad(self, cond_fn, x, t, model_kwargs):
+        grad = self._prep(self._wrap_model(cond_fn)(x, t, **(model_kwargs or {})))
+        assert grad.shape == x.shape, (tuple(grad.shape), tuple(x.shape))
+        return grad
+
+    def _guided_step(self, model_output, x, t, noise, clip_denoised, mode, eta=0.0, xstart_in=None, cond_grad=None, sample=True,
+                     mean=False):
+        """mapdit_obj_step_guided -> (sample, pred_xstart, mean); sample / mean are None unless asked for.  The default objective
+        runs it as mean type 0, variance type 0."""
+        mean_type, var_type, _ = self._kinds()
+        mo = None if model_output is None else self._prep(model_output)
+        out_s = torch.empty_like(x) if sample else None
+        out_m = torch.empty_like(x) if mean else None
+        xstart = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.lib().obj_step_guided(L.ptr(mo), x.data_ptr(), L.ptr(noise), t.data_ptr(), self._tables(x.device).data_ptr(),
+                                    self._obj_tables(x.device).data_ptr(), self.num_timesteps, mean_type, var_type,
+                                    int(bool(clip_denoised)), mode, float(eta), L.ptr(xstart_in), L.ptr(cond_grad), L.ptr(out_s),
+                                    xstart.data_ptr(), L.ptr(out_m), x.shape[0], x[0].numel(), L.cur_stream())
+        return out_s, xstart, out_m
+
+    def condition_mean(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """reference gaussian_diffusion.py:346-356 -> mean + variance * cond_fn(x, t, **model_kwargs) (Sohl-Dickstein et al. 2015).
+        p_sample does not come through here: mapdit_obj_step_guided applies the same shift inside the step."""
+        x = self._prep(x)
+        t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        grad = self._cond_grad(cond_fn, x, t, model_kwargs)
+        return torch.addcmul(p_mean_var["mean"].float(), p_mean_var["variance"], grad)
+
+    def condition_score(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """reference gaussian_diffusion.py:358-374 -> a copy of p_mean_var with pred_xstart and mean as they would have been, had the
+        model's score been conditioned by cond_fn (Song et al. 2020).  The DDIM steps apply the same in their own launch."""
+        self._supported()
+        x = self._prep(x)
+        t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        grad = self._cond_grad(cond_fn, x, t, model_kwargs)
+        _, xstart, mean = self._guided_step(None, x, t, None, False, _STEP_DDIM, xstart_in=self._prep(p_mean_var["pred_xstart"]),
+                                            cond_grad=grad, sample=False, mean=True)
+        out = p_mean_var.copy()
+        out["pred_xstart"], out["mean"] = xstart, mean
+        return out
+
     def _step_math(self, model_output, x, t, noise, clip_denoised):
         if not self._is_default():
             return self._obj_step(model_output, x, t, noise, clip_denoised, _STEP_PSAMPLE)
@@ -346,15 +418,21 @@ class GaussianDiffusion:
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """reference gaussian_diffusion.py:254-332 (mean = the p_sample kernel with zero noise)."""
         self._supported()
-        if denoised_fn is not None:
-            raise NotImplementedError("denoised_fn is not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         B, C = x.shape[:2]
         assert t.shape == (B,)
+
+        def hooked(model_output):          # pred_xstart = clip(denoised_fn(raw x0)) and the posterior mean built from it
+            xin, _ = self._hooks(model_output, x, t, denoised_fn, None, None)
+            mean, xstart, _ = self._guided_step(model_output, x, t, None, clip_denoised, _STEP_PSAMPLE, xstart_in=xin)
+            return mean, xstart
         if not self._is_default():
             model_output = self._model_output(model, x, t, model_kwargs)
-            mean, xstart = self._obj_step(model_output, x, t, None, clip_denoised, _STEP_PSAMPLE)
+            if denoised_fn is not None:
+                mean, xstart = hooked(model_output)
+            else:
+                mean, xstart = self._obj_step(model_output, x, t, None, clip_denoised, _STEP_PSAMPLE)
             if self.model_var_type == ModelVarType.LEARNED_RANGE:
                 frac = (model_output[:, C:].float() + 1) / 2
                 log_var = (frac * self._extract("_log_betas", t, x.shape)
@@ -370,7 +448,10 @@ class GaussianDiffusion:
                     "model_output": model_output}
         model_output = model(x, t, **(model_kwargs or {}))
         assert model_output.shape == (B, C * 2, *x.shape[2:])
-        mean, xstart = self._step_math(model_output, x, t, torch.zeros_like(x), clip_denoised)
+        if denoised_fn is not None:
+            mean, xstart = hooked(model_output)
+        else:
+            mean, xstart = self._step_math(model_output, x, t, torch.zeros_like(x), clip_denoised)
         tab = self._tables(x.device)
         n = self.num_timesteps
         frac = (model_output[:, C:].float() + 1) / 2
@@ -382,12 +463,15 @@ class GaussianDiffusion:
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None):
         """reference gaussian_diffusion.py:376-417."""
         self._supported()
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn are not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         model_output = (self._wrap_model(model)(x, t, **(model_kwargs or {})) if self._is_default()
                         else self._model_output(model, x, t, model_kwargs))
+        if denoised_fn is not None or cond_fn is not None:
+            xin, grad = self._hooks(model_output, x, t, denoised_fn, cond_fn, model_kwargs)
+            noise = torch.randn_like(x)
+            sample, xstart, _ = self._guided_step(model_output, x, t, noise, clip_denoised, _STEP_PSAMPLE, xstart_in=xin, cond_grad=grad)
+            return {"sample": sample, "pred_xstart": xstart}
         noise = torch.randn_like(x)
         sample, xstart = self._step_math(model_output, x, t, noise, clip_denoised)
         return {"sample": sample, "pred_xstart": xstart}
@@ -408,12 +492,15 @@ class GaussianDiffusion:
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
         """reference gaussian_diffusion.py:513-567."""
         self._supported()
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn are not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         model_output = (self._wrap_model(model)(x, t, **(model_kwargs or {})) if self._is_default()
                         else self._model_output(model, x, t, model_kwargs))
+        if denoised_fn is not None or cond_fn is not None:
+            xin, grad = self._hooks(model_output, x, t, denoised_fn, cond_fn, model_kwargs)
+            noise = torch.randn_like(x)
+            sample, xstart, _ = self._guided_step(model_output, x, t, noise, clip_denoised, _STEP_DDIM, eta, xstart_in=xin, cond_grad=grad)
+            return {"sample": sample, "pred_xstart": xstart}
         noise = torch.randn_like(x)
         sample, xstart = self._ddim_math(model_output, x, t, noise, clip_denoised, eta, False)
         return {"sample": sample, "pred_xstart": xstart}
@@ -422,12 +509,14 @@ class GaussianDiffusion:
         """reference gaussian_diffusion.py:569-605: x_{t+1} along the deterministic reverse ODE."""
         assert eta == 0.0, "Reverse ODE only for deterministic path"
         self._supported()
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn are not built")
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         model_output = (self._wrap_model(model)(x, t, **(model_kwargs or {})) if self._is_default()
                         else self._model_output(model, x, t, model_kwargs))
+        if denoised_fn is not None or cond_fn is not None:
+            xin, grad = self._hooks(model_output, x, t, denoised_fn, cond_fn, model_kwargs)
+            sample, xstart, _ = self._guided_step(model_output, x, t, None, clip_denoised, _STEP_DDIM_REVERSE, xstart_in=xin, cond_grad=grad)
+            return {"sample": sample, "pred_xstart": xstart}
         sample, xstart = self._ddim_math(model_output, x, t, None, clip_denoised, 0.0, True)
         return {"sample": sample, "pred_xstart": xstart}
 

@@ -69,6 +69,14 @@ class SpacedDiffusion(GaussianDiffusion):
     def training_losses(self, model, *args, **kwargs):
         return super().training_losses(self._wrap_model(model), *args, **kwargs)
 
+    def condition_mean(self, cond_fn, *args, **kwargs):
+        """reference respace.py:99-100: cond_fn sees the timesteps of the base schedule."""
+        return super().condition_mean(self._wrap_model(cond_fn), *args, **kwargs)
+
+    def condition_score(self, cond_fn, *args, **kwargs):
+        """reference respace.py:102-103."""
+        return super().condition_score(self._wrap_model(cond_fn), *args, **kwargs)
+
     def _scale_timesteps(self, t):
         return t
 

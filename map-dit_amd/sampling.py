@@ -100,9 +100,14 @@ class GraphedSampler:
         return out
 
 
-def p_sample_loop_graphed(diffusion, model, shape, noise=None, clip_denoised=False, model_kwargs=None, device=None):
+def p_sample_loop_graphed(diffusion, model, shape, noise=None, clip_denoised=False, model_kwargs=None, device=None, *,
+                          denoised_fn=None, cond_fn=None):
     """Drop-in for ``diffusion.p_sample_loop(model.forward[_with_cfg], shape, noise, clip_denoised, model_kwargs=...)``
-    with the loop body replayed from a hipGraph.  ``model`` is the DiT module itself."""
+    with the loop body replayed from a hipGraph.  ``model`` is the DiT module itself.  The sampler hooks are user callables, which
+    a captured graph cannot hold: they are refused here and run through ``diffusion.p_sample_loop``."""
+    if denoised_fn is not None or cond_fn is not None:
+        raise NotImplementedError("denoised_fn / cond_fn are not built for the captured sampler (a user callable cannot run inside "
+                                  "a hipGraph): use diffusion.p_sample_loop")
     kw = dict(model_kwargs or {})
     y = kw.pop("y")
     cfg = kw.pop("cfg_scale", None)
