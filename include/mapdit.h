@@ -400,6 +400,11 @@ int mapdit_attn_generic_bwd(const uint16_t* qn, const uint16_t* kn, const uint16
  * a + b (the off form of README.md:65 --use-mp-pos-enc; unpinned). */
 int mapdit_patch_embed_fwd(const float* x, const float* w_eff, const float* pos, float* out, uint16_t* patches,
                            int ldp, int N, int C, int S, int p, int D, float out_scale, void* stream);
+/* Gradient of patch_embed_fwd with respect to x: dx [N,C,S,S] fp32 = scale * (dx0 [N*T][ldx] 16-bit) (w_eff [D][P+1], columns < P), un-patchified
+ * with the forward's index rule.  One pass over dx0 on the MFMA, fp32 accumulation, w_eff rounded to the operand type; every element
+ * of dx is written once (no atomics, no zero fill needed).  D % 32 == 0, dx0 rows 16-byte aligned; any C, any N*T. */
+int mapdit_patch_embed_bwd_x(const uint16_t* dx0, int ldx, const float* w_eff, float* dx, int N, int C, int S, int p, int D, float scale,
+                             void* stream);
 int mapdit_fourier_fwd(const int64_t* t, const float* scale, const float* shift, uint16_t* out, int n, int F,
                        void* stream);
 /* Labels outside [0, table_rows) and timesteps outside [0, nsteps) never index memory: the kernels clamp them and record a
@@ -422,6 +427,8 @@ int mapdit_final_out_bwd(const float* dout, const float* lin, int ldl, const flo
                          float grad_scale, int N, int C, int S, int p, void* stream);
 /* DiT.forward_with_cfg tail (src/dit.py:113-118). */
 int mapdit_cfg_combine(const float* model_out, float* out, int n_total, int C, int HW, float cfg_scale, void* stream);
+/* Its backward (out of place): g = dout[n] + dout[n + half] on the first C channels, din[n] = s g, din[n + half] = (1 - s) g; the rest passes through. */
+int mapdit_cfg_combine_bwd(const float* dout, float* din, int n_total, int C, int HW, float cfg_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Gaussian diffusion pointwise math (diffusion/gaussian_diffusion.py, diffusion/diffusion_utils.py).
@@ -589,6 +596,13 @@ int mapdit_engine_weight_image(mapdit_engine_t* e, int pidx, void** img, void** 
 int mapdit_engine_jacobian_shard(mapdit_engine_t* e, void* stream);
 int mapdit_engine_set_loss_scale(mapdit_engine_t* e, float loss_scale);
 int mapdit_engine_loss_scale(mapdit_engine_t* e, float* out);
+/* Input-latent gradient (additive within abi 5).  One-shot, like the block fences: the next backward that reaches stage depth+1 writes
+ * dx [N, C, S, S] fp32 = d loss / d x of the saved forward (overwrite; mapdit_patch_embed_bwd_x on the gradient of the patch embedding
+ * output, scale = c5 / loss scale), then forgets the pointer.  dx = NULL clears it.  input_only != 0: that backward computes the
+ * activation-gradient chain alone - no weight-gradient GEMM, no weight-norm Jacobian, no conditioning-path tail - and writes NO bound
+ * gradient buffer (none needs to be bound); what the fused kernels cannot skip (gain partials, MPScale reference sums) lands in scratch.
+ * Refused while a staged backward is in progress; a forward drops a request no backward consumed (call it between forward and backward). */
+int mapdit_engine_set_input_grad(mapdit_engine_t* e, float* dx, int input_only);
 
 /* Measurement hook: bracket every launch of one kernel family with HIP events on the launch stream.
  * MAPDIT_PROF_FC1_FWD = the block-MLP fc1 GEMM (gemm NT + SILU2 epilogue, [N*T, 4D] = [N*T, D] x [4D, D]^T). */
@@ -683,6 +697,8 @@ int mapdit_attn_generic_bwd_f16(const uint16_t* qn, const uint16_t* kn, const ui
                                 int head_dim, void* stream);
 int mapdit_patch_embed_fwd_f16(const float* x, const float* w_eff, const float* pos, float* out, uint16_t* patches,
                                int ldp, int N, int C, int S, int p, int D, float out_scale, void* stream);
+int mapdit_patch_embed_bwd_x_f16(const uint16_t* dx0, int ldx, const float* w_eff, float* dx, int N, int C, int S, int p, int D, float scale,
+                                 void* stream);
 int mapdit_cond_combine_fwd_f16(const float* temb, const float* table, const int64_t* y, float* c, uint16_t* c_silu,
                                 uint16_t* c_f16, int n, int D, int table_rows, void* stream);
 int mapdit_cond_combine_bwd_f16(const float* c, const float* dcs, const float* dcd, const int64_t* y, uint16_t* dtemb,

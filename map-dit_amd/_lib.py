@@ -129,6 +129,7 @@ _SIGS = {
     "mapdit_attn_generic_fwd": [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp],
     "mapdit_attn_generic_bwd": [vp] * 10 + [ci, ci, ci, ci, vp],
     "mapdit_patch_embed_fwd": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp],
+    "mapdit_patch_embed_bwd_x": [vp, ci, vp, vp, ci, ci, ci, ci, ci, cf, vp],
     "mapdit_fourier_fwd": [vp, vp, vp, vp, ci, ci, vp],
     "mapdit_cond_combine_fwd": [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp],
     "mapdit_cond_combine_bwd": [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp],
@@ -141,6 +142,7 @@ _SIGS = {
     "mapdit_final_out_fwd": [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp],
     "mapdit_final_out_bwd": [vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, cf, ci, ci, ci, ci, vp],
     "mapdit_cfg_combine": [vp, vp, ci, ci, ci, cf, vp],
+    "mapdit_cfg_combine_bwd": [vp, vp, ci, ci, ci, cf, vp],
     "mapdit_q_sample": [vp, vp, vp, vp, ci, vp, ci, ci, vp],
     "mapdit_loss_fwd": [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp],
     "mapdit_loss_bwd": [vp, vp, vp, vp, vp, ci, ci, vp],
@@ -165,6 +167,7 @@ _SIGS = {
     "mapdit_engine_jacobian_shard": [vp, vp],
     "mapdit_engine_set_loss_scale": [vp, cf],
     "mapdit_engine_loss_scale": [vp, C.POINTER(cf)],
+    "mapdit_engine_set_input_grad": [vp, vp, ci],
     "mapdit_engine_profile_begin": [vp, ci, ci],
     "mapdit_engine_profile_begin_strided": [vp, ci, ci, ci],
     "mapdit_engine_profile_end": [vp, C.POINTER(ci), C.POINTER(C.c_double)],
@@ -173,7 +176,7 @@ _SIGS = {
 # IEEE fp16 operand forms: same signatures (mapdit.h, "16-bit operand format")
 for _n in ("weightnorm_fwd", "weightnorm_fwd_batch", "modulate_fwd", "resid_mod_bwd", "rot_modulate_fwd", "qkv_split",
            "qkv_merge_bwd", "attn_cos_fwd", "attn_cos_fwd_rawqk", "attn_cos_fwd_rawqk_save", "qk_cos_normalize", "attn_cos_bwd", "attn_cos_bwd_fused", "attn_sdpa_fwd", "heads_merge_bwd", "ln_modulate_fwd", "ln_bwd_merge", "qkv_split_generic", "qkv_merge_bwd_generic",
-           "attn_generic_fwd", "attn_generic_bwd", "patch_embed_fwd", "cond_combine_fwd", "cond_combine_bwd", "final_out_bwd"):
+           "attn_generic_fwd", "attn_generic_bwd", "patch_embed_fwd", "patch_embed_bwd_x", "cond_combine_fwd", "cond_combine_bwd", "final_out_bwd"):
     _SIGS[f"mapdit_{_n}_f16"] = _SIGS[f"mapdit_{_n}"]
 for _b, _h in (("gemm_bf16", "gemm_f16"), ("gemm_group_tn_bf16", "gemm_group_tn_f16"), ("f32_to_bf16", "f32_to_f16"), ("f32_to_bf16_2d", "f32_to_f16_2d"),
                ("mpsilu_to_bf16", "mpsilu_to_f16")):

@@ -91,6 +91,76 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_kernel(const float* __res
     }
 }
 
+// ---- gradient of the above with respect to the latents -------------------------------------------------------------
+// dx0 [M][ldx] 16-bit = grad wrt the patch embedding output (what the x_embedder weight gradient multiplies from the left), w [D][P+1] fp32;
+// dx [N,C,S,S] fp32 = scale * (dx0 W)[m][j] scattered with the forward's index rule (the ones column j = P and pos_embed take no gradient).
+// One pass over dx0, the only large operand: a block owns 128 token rows (a wave 32 = two MFMA row tiles) and 16 CT patch columns, walks D in
+// chunks of 128 - the chunk's dx0 fragments are loaded HBM -> registers first (one 16-byte load per lane and MFMA), the chunk of W is
+// rounded to the operand type and staged transposed ([j][k]: an MFMA B fragment is one 16-byte LDS read) while those loads are in
+// flight - and accumulates in fp32 on v_mfma_f32_16x16x32.  Every element of dx has exactly one (m, j): plain stores, no atomics, no
+// [M, P] intermediate.  P > 64 (patch 8): blockIdx.y walks the column groups, dx0 is read once per group (16 tokens per sample: not hot).
+template <int CT>
+__global__ __launch_bounds__(256) void patch_embed_bwd_x_kernel(const bf16_t* __restrict__ dx0, int ldx, const float* __restrict__ w,
+                                                              float* __restrict__ dx, int C, int S, int p, int D, long M, float scale) {
+    constexpr int KC = 128, LDW = KC + 8, NJ = 16 * CT;     // (LDW: 272-byte rows, 16-byte aligned, consecutive rows 4 banks apart)
+    __shared__ __attribute__((aligned(16))) bf16_t wt[NJ * LDW];
+    const int P = p * p * C, P1 = P + 1, grid = S / p, T = grid * grid;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 15, q = lane >> 4;
+    const long m0 = (long)blockIdx.x * 128 + wave * 32;
+    const int j0 = blockIdx.y * NJ;
+    f32x4_t acc[2][CT];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < D; k0 += KC) {
+        const int kc = D - k0 < KC ? D - k0 : KC;            // a multiple of 32 (checked by the entry point)
+        bf16x8_t a[2][KC / 32];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int ks = 0; ks < KC / 32; ++ks) {
+                const long m = m0 + rt * 16 + r;
+                a[rt][ks] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+                if (m < M && ks * 32 < kc) a[rt][ks] = *(const bf16x8_t*)(dx0 + (size_t)m * ldx + k0 + ks * 32 + q * 8);
+            }
+        __syncthreads();                                     // the previous chunk's fragment reads are done
+        for (int i = threadIdx.x; i < NJ * kc; i += 256) {
+            const int j = i % NJ, kk = i / NJ;
+            wt[j * LDW + kk] = j0 + j < P ? cvt16(w[(size_t)(k0 + kk) * P1 + j0 + j]) : (bf16_t)0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < KC / 32; ++ks) {
+            if (ks * 32 >= kc) break;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const bf16x8_t b = *(const bf16x8_t*)(wt + (ct * 16 + r) * LDW + ks * 32 + q * 8);
+                acc[0][ct] = MFMA16(a[0][ks], b, acc[0][ct]);
+                acc[1][ct] = MFMA16(a[1][ks], b, acc[1][ct]);
+            }
+        }
+    }
+    // accumulator element i of a lane: token row 4 q + i of the tile, patch column r
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int j = j0 + ct * 16 + r;
+        if (j >= P) continue;
+        const int c = j % C, p2 = (j / C) % p, p1 = j / (C * p);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const long m = m0 + rt * 16 + q * 4 + i;
+                if (m >= M) continue;
+                const long n = m / T;
+                const int t = (int)(m % T), hy = t / grid, wx = t % grid;
+                dx[(((size_t)n * C + c) * S + hy * p + p1) * S + wx * p + p2] = scale * acc[rt][ct][i];
+            }
+    }
+}
+
 // ---- timestep Fourier features (reference src/blocks/timestep_embedder.py:18-21) ---------------------------------
 __global__ void fourier_kernel(const long* __restrict__ t, const float* __restrict__ scale, const float* __restrict__ shift,
                                bf16_t* __restrict__ out, int n, int F) {
@@ -236,6 +306,19 @@ __global__ void cfg_combine_kernel(const float* __restrict__ in, float* __restri
     const float cond = in[(long)nc * per + e], unc = in[(long)(nc + half) * per + e];
     out[i] = unc + s * (cond - unc);
 }
+// Its backward: both halves of `out` carry the same combination on the first C channels, so with g = dout[n] + dout[n + half] the conditional
+// row takes s g and the unconditional row (1 - s) g; the remaining channels pass through.
+__global__ void cfg_combine_bwd_kernel(const float* __restrict__ dout, float* __restrict__ din, int n_total, int C, int HW, float s) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)2 * C * HW;
+    if (i >= (long)n_total * per) return;
+    const int n = (int)(i / per);
+    const long e = i % per;
+    if (e >= (long)C * HW) { din[i] = dout[i]; return; }
+    const int half = n_total / 2, nc = n % half;
+    const float g = dout[(long)nc * per + e] + dout[(long)(nc + half) * per + e];
+    din[i] = n < half ? s * g : (1.f - s) * g;
+}
 
 MD_NS_CLOSE
 
@@ -258,6 +341,28 @@ extern "C" int MD_SYM(patch_embed_fwd)(const float* x, const float* w_eff, const
         hipLaunchKernelGGL(patch_embed_fwd_kernel<64>, dim3(cdiv(M, 64), D / 64), dim3(256), shm64, (hipStream_t)stream, x, w_eff,
                            pos, out, patches, ldp, C, S, p, D, M, c5);
     }
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(patch_embed_bwd_x)(const uint16_t* dx0, int ldx, const float* w_eff, float* dx, int N, int C, int S, int p, int D,
+                                        float scale, void* stream) {
+    MD_CHECK(dx0 && w_eff && dx, "patch_embed_bwd_x: null argument");
+    MD_CHECK(N > 0 && C > 0 && p > 0 && S > 0 && S % p == 0, "patch_embed_bwd_x: N=%d C=%d S=%d p=%d unsupported", N, C, S, p);
+    MD_CHECK(D > 0 && D % 32 == 0, "patch_embed_bwd_x: D=%d must be a multiple of 32 (the MFMA's reduction length)", D);
+    MD_CHECK(ldx >= D && ldx % 8 == 0 && ((uintptr_t)dx0 & 15) == 0, "patch_embed_bwd_x: dx0 rows must be 16-byte aligned (ldx=%d)", ldx);
+    const long P = (long)p * p * C;
+    MD_CHECK(P <= 4096, "patch_embed_bwd_x: patch dim %ld too large", P);
+    const long M = (long)N * (S / p) * (S / p);
+    MD_CHECK(M <= ((long)1 << 37), "patch_embed_bwd_x: %ld tokens unsupported (grid size)", M);
+    const dim3 block(256);
+    if (P <= 16)
+        hipLaunchKernelGGL(patch_embed_bwd_x_kernel<1>, dim3(cdiv(M, 128), 1), block, 0, (hipStream_t)stream, dx0, ldx, w_eff, dx, C, S, p, D, M, scale);
+    else if (P <= 32)
+        hipLaunchKernelGGL(patch_embed_bwd_x_kernel<2>, dim3(cdiv(M, 128), 1), block, 0, (hipStream_t)stream, dx0, ldx, w_eff, dx, C, S, p, D, M, scale);
+    else
+        hipLaunchKernelGGL(patch_embed_bwd_x_kernel<4>, dim3(cdiv(M, 128), cdiv(P, 64)), block, 0, (hipStream_t)stream, dx0, ldx, w_eff, dx, C, S, p, D, M,
+                           scale);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }
@@ -323,6 +428,15 @@ extern "C" int mapdit_cfg_combine(const float* model_out, float* out, int n_tota
     const long total = (long)n_total * 2 * C * HW;
     hipLaunchKernelGGL(cfg_combine_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, model_out, out, n_total, C,
                        HW, cfg_scale);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_cfg_combine_bwd(const float* dout, float* din, int n_total, int C, int HW, float cfg_scale, void* stream) {
+    MD_CHECK(dout && din && dout != din && n_total > 0 && n_total % 2 == 0, "cfg_combine_bwd: batch must be even and non-empty, out of place");
+    const long total = (long)n_total * 2 * C * HW;
+    hipLaunchKernelGGL(cfg_combine_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dout, din, n_total, C, HW,
+                       cfg_scale);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }

@@ -90,6 +90,11 @@ struct mapdit_engine {
     float lscale = 1.f, ginv = 1.f;       // fp16 backward: loss scale of the running backward and its inverse (1 otherwise)
     int last_N = 0;
     int next_stage = 0;                   // backward stage expected next (stages run in order)
+    // mapdit_engine_set_input_grad, one-shot: the backward that reaches stage L+1 writes d loss / d x there; ig_only = that backward runs the
+    // activation-gradient chain alone (no dW GEMM, no weight-norm Jacobian, no conditioning tail, no bound gradient buffer written: the gain
+    // and MPScale-reference sums the fused kernels cannot skip land in the first floats of dcd, which an input-only backward does not use)
+    float* ig_dx = nullptr;
+    bool ig_only = false;
     bool have_saved = false;
     std::vector<float*> params, grads;
     // weight images
@@ -771,6 +776,7 @@ int dw_group_flush(mapdit_engine* e, int K, void* st) {
 }
 
 int linear_dw(mapdit_engine* e, int pidx, const bf16_t* dy, int ld_dy, const bf16_t* x, int ld_x, int K, float alpha, void* st) {
+    if (e->ig_only) return MAPDIT_OK;                      // input-only backward: no weight gradient
     const WeightImg& w = e->wimg[pidx];
     if (pidx >= MAPDIT_NUM_GLOBAL && e->grads[pidx]) {
         const int which = (pidx - MAPDIT_NUM_GLOBAL) % MAPDIT_NUM_BLOCK;
@@ -1071,6 +1077,18 @@ extern "C" int mapdit_engine_set_block_fences(mapdit_engine_t* e, void* const* e
     return MAPDIT_OK;
 }
 
+// One-shot (consumed by the backward that reaches stage L+1): that backward writes d loss / d x [N,C,S,S] to dx; input_only = it computes
+// nothing else (mapdit.h).  Between the stages of a staged backward the request cannot change: stage 0 already ran with or without it.
+extern "C" int mapdit_engine_set_input_grad(mapdit_engine_t* e, float* dx, int input_only) {
+    MD_CHECK(e, "engine_set_input_grad: null argument");
+    MD_CHECK(e->train, "engine_set_input_grad: a training engine (the inference engine keeps no activations)");
+    MD_CHECK(e->next_stage == 0, "engine_set_input_grad: a staged backward is in progress");
+    MD_CHECK(dx || !input_only, "engine_set_input_grad: input_only without a dx buffer");
+    e->ig_dx = dx;
+    e->ig_only = dx && input_only;
+    return MAPDIT_OK;
+}
+
 // 16-bit image (and, for a conditioning weight, its [hi | lo | hi] split image with 3 x cols columns) of a linear's effective weight:
 // what the host all-gathers when the weight passes are sharded.  sharded = the rows are split over the ranks of mapdit_engine_set_shard.
 extern "C" int mapdit_engine_weight_image(mapdit_engine_t* e, int pidx, void** img, void** img3, int* rows, int* cols, int* sharded) {
@@ -1193,6 +1211,8 @@ static int forward_precise(mapdit_engine* e, const float* x, const int64_t* t, c
     e->last_N = N;
     e->next_stage = 0;
     e->have_saved = save != 0;
+    e->ig_dx = nullptr;                   // an unconsumed input-gradient request belonged to the previous forward's backward
+    e->ig_only = false;
     return MAPDIT_OK;
 }
 
@@ -1206,7 +1226,11 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
     hipStream_t hs = (hipStream_t)st;
     auto& px = e->px;
     auto& pg = e->pg;
-    auto G = [&](int idx) { return e->grads[idx]; };
+    const bool io = e->ig_only;           // input-only: see mapdit_engine_backward_stages
+    auto G = [&](int idx) -> float* {
+        if (!io) return e->grads[idx];
+        return e->dcd + (idx == MAPDIT_P_MS_REF ? 0 : idx == MAPDIT_P_SS_REF ? NSCALE : 2 * NSCALE);
+    };
     const int NONE = MAPDIT_SPLIT_OP_NONE, SILU = MAPDIT_SPLIT_OP_MPSILU;
     // dx[rows, w.cols] (+)= dy[rows, w.rows] W
     auto lin_dx = [&](const float* dy, int ld_dy, int rows, int widx, float* dx, int ldx, int acc) -> int {
@@ -1216,6 +1240,7 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
     };
     // grad W_idx = weight-norm Jacobian of dy^T op(x), reduction over `rows` tokens / samples
     auto lin_dw = [&](int widx, const float* dy, int ld_dy, const float* x, int ld_x, int opx, int rows) -> int {
+        if (io) return MAPDIT_OK;
         const WeightImg& w = e->wimg[widx];
         TRY(mapdit_split3_stack(dy, ld_dy, pg.AsT, w.rows, rows, w.rows, MAPDIT_SPLIT_A, NONE, st));
         TRY(mapdit_split3_stack(x, ld_x, pg.BsT, w.cols, rows, w.cols, MAPDIT_SPLIT_B, opx, st));
@@ -1239,9 +1264,9 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
     };
 
     if (stage_from == 0) {
-        hipError_t he = hipMemsetAsync(e->dcs, 0, (size_t)N * D * 4, hs);
+        hipError_t he = io ? hipSuccess : hipMemsetAsync(e->dcs, 0, (size_t)N * D * 4, hs);
         if (he == hipSuccess) he = hipMemsetAsync(e->dcd, 0, (size_t)N * D * 4, hs);
-        if (he == hipSuccess) he = hipMemsetAsync(e->dtable, 0, (size_t)c.table_rows * D * 4, hs);
+        if (he == hipSuccess && !io) he = hipMemsetAsync(e->dtable, 0, (size_t)c.table_rows * D * 4, hs);
         MD_CHECK(he == hipSuccess, "engine_backward: memset failed: %s", hipGetErrorString(he));
         MD_CHECK(G(MAPDIT_P_MS_REF) && G(MAPDIT_P_SS_REF), "engine_backward: gradient buffers not bound");
         // final layer (final_layer.py:53-59, dit.py:96-101)
@@ -1251,6 +1276,7 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
         for (int w = 0; w < 2; ++w) {
             const int pi = w == 0 ? MAPDIT_P_MS_LIN : MAPDIT_P_SS_LIN;
             const float* da = pg.da + (size_t)w * N * NSCALE;
+            if (io) break;
             TRY(lin_dx(da, NSCALE, N, pi, e->dcd, D, 1));
             TRY(lin_dw(pi, da, NSCALE, e->c, D, NONE, N));
         }
@@ -1259,7 +1285,7 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
         float* dmod_last = e->dmod + (size_t)(L - 1) * 6 * D;
         TRY(rmb(nullptr, e->X[2 * L], e->fmod, e->fmod + D, 2 * D, MAPDIT_P_F_GAIN, e->dfmod, e->dfmod + D, 2 * D, e->pblk[L - 1].y2,
                 e->mod_all + (size_t)(L - 1) * 6 * D + 5 * D, dmod_last + 5 * D, e->DXa));
-        TRY(lin_dx(e->dfmod, 2 * D, N, MAPDIT_P_F_MOD, e->dcs, D, 1));
+        if (!io) TRY(lin_dx(e->dfmod, 2 * D, N, MAPDIT_P_F_MOD, e->dcs, D, 1));
         TRY(lin_dw(MAPDIT_P_F_MOD, e->dfmod, 2 * D, e->c, D, SILU, N));
     }
     // blocks, last to first.  Invariant: DXa = d/d X[2i+2]; pg.dy = grad of the MLP branch output y2_i
@@ -1294,11 +1320,21 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
                     e->DXa));
         // modulation linear of this block: its six gradient chunks are complete now
         TRY(lin_dw(imod, dmod, ldm, e->c, D, SILU, N));
-        TRY(lin_dx(dmod, ldm, N, imod, e->dcs, D, 1));
+        if (!io) TRY(lin_dx(dmod, ldm, N, imod, e->dcs, D, 1));
     }
     e->next_stage = stage_to + 1;
     if (stage_to < L + 1) return MAPDIT_OK;
     // patch embedding: x0 = (x_embedder(patches) + pos) * C5; DXa = d/d X[0]
+    if (e->ig_dx) {                       // d loss / d x, requested for this backward (one-shot): the fp32 form
+        TRY(mapdit_patch_embed_bwd_x32(e->DXa, D, e->wx_eff, e->ig_dx, N, c.in_channels, c.input_size, c.patch, D, e->c5, st));
+        e->ig_dx = nullptr;
+    }
+    if (io) {
+        e->ig_only = false;
+        e->have_saved = false;
+        e->next_stage = 0;
+        return MAPDIT_OK;
+    }
     {
         const float c5 = 0.70710678118654752f;
         const long slab = (long)D * e->ldp;
@@ -1476,6 +1512,8 @@ extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const i
     e->last_N = N;
     e->next_stage = 0;
     e->have_saved = save != 0;
+    e->ig_dx = nullptr;                   // an unconsumed input-gradient request belonged to the previous forward's backward
+    e->ig_only = false;
     return MAPDIT_OK;
 }
 
@@ -1551,7 +1589,11 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     const int M = N * T, P2 = 2 * e->P;
     hipStream_t hs = (hipStream_t)st;
     auto W = [&](int idx) { return e->wimg[idx].img; };
-    auto G = [&](int idx) { return e->grads[idx]; };
+    const bool io = e->ig_only;           // input-only: the dX chain alone; the sums the fused kernels cannot skip go to scratch (head of dcd)
+    auto G = [&](int idx) -> float* {
+        if (!io) return e->grads[idx];
+        return e->dcd + (idx == MAPDIT_P_MS_REF ? 0 : idx == MAPDIT_P_SS_REF ? NSCALE : 2 * NSCALE);
+    };
     if (stage_from == 0) {
     e->dw_pending.clear();
     // fp16: the whole backward runs on gradients multiplied by a power of two (mapdit_config_t.loss_scale) so that the 16-bit
@@ -1563,11 +1605,11 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
                                        : exp2f(floorf(log2f((float)N * c.in_channels * c.input_size * c.input_size)) - 5.f);
     }
     e->ginv = 1.f / e->lscale;
-    hipError_t he = hipMemsetAsync(e->dcs, 0, (size_t)N * D * 4, hs);
+    hipError_t he = io ? hipSuccess : hipMemsetAsync(e->dcs, 0, (size_t)N * D * 4, hs);
     if (he == hipSuccess) he = hipMemsetAsync(e->dcd, 0, (size_t)N * D * 4, hs);
-    if (he == hipSuccess) he = hipMemsetAsync(e->dtable, 0, (size_t)c.table_rows * D * 4, hs);
-    if (he == hipSuccess && G(MAPDIT_P_MS_REF)) he = hipMemsetAsync(G(MAPDIT_P_MS_REF), 0, NSCALE * 4, hs);
-    if (he == hipSuccess && G(MAPDIT_P_SS_REF)) he = hipMemsetAsync(G(MAPDIT_P_SS_REF), 0, NSCALE * 4, hs);
+    if (he == hipSuccess && !io) he = hipMemsetAsync(e->dtable, 0, (size_t)c.table_rows * D * 4, hs);
+    if (he == hipSuccess && !io && G(MAPDIT_P_MS_REF)) he = hipMemsetAsync(G(MAPDIT_P_MS_REF), 0, NSCALE * 4, hs);
+    if (he == hipSuccess && !io && G(MAPDIT_P_SS_REF)) he = hipMemsetAsync(G(MAPDIT_P_SS_REF), 0, NSCALE * 4, hs);
     MD_CHECK(he == hipSuccess, "engine_backward: memset failed: %s", hipGetErrorString(he));
     MD_CHECK(G(MAPDIT_P_MS_REF) && G(MAPDIT_P_SS_REF), "engine_backward: gradient buffers not bound");
 
@@ -1578,6 +1620,7 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     for (int w = 0; w < 2; ++w) {
         const int pi = w == 0 ? MAPDIT_P_MS_LIN : MAPDIT_P_SS_LIN;
         const bf16_t* da = e->da_bf + (size_t)w * N * NSCALE;
+        if (io) break;                    // (the MPScale angles depend on the conditioning vector only: nothing of theirs is on the dX chain)
         TRY(gemm16(e, MAPDIT_NN, N, D, NSCALE, da, NSCALE, W(pi), D, epi_f32(e->dcd, D, 1.f, 1), st));
         TRY(linear_dw(e, pi, da, NSCALE, e->c_bf, D, N, 1.f, st));
     }
@@ -1594,9 +1637,11 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
         a.n_samples = N; a.T = T; a.D = D; a.ca = e->ca; a.cb = e->cb_mlp;      // (the residual above the final layer: block L-1's MLP branch)
         TRY(dx_resid_mod_bwd(e, M, e->ldl, e->dlin, e->ldl, W(MAPDIT_P_F_LIN), a, G(MAPDIT_P_F_GAIN), st));
     }
+    if (!io) {                            // (the modulation gradients feed the conditioning path only)
     TRY(to16(e, e->dfmod, e->dmod_bf, (long)N * 2 * D, 1.f, st));
     TRY(gemm16(e, MAPDIT_NN, N, D, 2 * D, e->dmod_bf, 2 * D, W(MAPDIT_P_F_MOD), D, epi_f32(e->dcs, D, sa, 1), st));
     TRY(linear_dw(e, MAPDIT_P_F_MOD, e->dmod_bf, 2 * D, e->c_silu, D, N, sa, st));
+    }
     }   // stage 0
     const float sa = e->s_act;
 
@@ -1665,6 +1710,7 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
         }
         // modulation linear of this block (its six gradient chunks are complete now): dW here, so the block's gradient
         // slice is final when its stage ends (the DP reducer relies on that); d c_silu for all blocks in one GEMM below
+        if (io) continue;                 // (input-only: the modulation gradients have no consumer on the dX chain)
         TRY(to16_2d(e, dmod, ldm, e->dmod_bf + (size_t)i * e->MW, ldm, N, e->MW, 1.f, st));
         TRY(linear_dw(e, pidx_block(i, MAPDIT_B_MOD), e->dmod_bf + (size_t)i * e->MW, ldm, e->c_silu, D, N, sa, st));
         if (i == 0) {
@@ -1682,6 +1728,16 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     e->next_stage = stage_to + 1;
     if (stage_to < L + 1) return side_join(e, st);         // the stages' gradients are final in the caller's stream order
     // ---- patch embedding: x0 = (x_embedder(patches) + pos) * C5 -----------------------------------------------------
+    if (e->ig_dx) {                       // d loss / d x = un-patchify(c5 dx0 W_eff): requested for this backward (one-shot)
+        TRY(DT_FN(e, mapdit_patch_embed_bwd_x)(e->dx0_bf, D, e->wx_eff, e->ig_dx, N, c.in_channels, c.input_size, c.patch, D, e->c5 * e->ginv, st));
+        e->ig_dx = nullptr;
+    }
+    if (io) {
+        e->ig_only = false;
+        e->have_saved = false;
+        e->next_stage = 0;
+        return side_join(e, st);
+    }
     {
         const float c5 = e->c5;
         const long slab = (long)D * e->ldp;

@@ -421,6 +421,23 @@ __global__ void patchify32_kernel(const float* __restrict__ x, float* __restrict
     patches[i] = v;
 }
 // out[i] = alpha * in[i]  /  out[i] += in[i]
+// d loss / d x of the patch embedding, the fp32 form (parity instrument): one thread per (token, patch column), plain fp32 FMAs over D in
+// index order, scattered with patchify32's index rule.  dx0 [M][ldx] fp32, w [D][P+1] fp32.
+__global__ void patch_embed_bwd_x32_kernel(const float* __restrict__ dx0, int ldx, const float* __restrict__ w, float* __restrict__ dx, int C,
+                                           int S, int p, int D, long M, float scale) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int P = p * p * C, P1 = P + 1, grid = S / p, T = grid * grid;
+    if (i >= M * P) return;
+    const long m = i / P;
+    const int j = (int)(i % P);
+    float a = 0.f;
+    for (int d = 0; d < D; ++d) a += dx0[(size_t)m * ldx + d] * w[(size_t)d * P1 + j];
+    const long n = m / T;
+    const int t = (int)(m % T), hy = t / grid, wx = t % grid;
+    const int c = j % C, p2 = (j / C) % p, p1 = j / (C * p);
+    dx[(((size_t)n * C + c) * S + hy * p + p1) * S + wx * p + p2] = scale * a;
+}
+
 __global__ void axpby32_kernel(const float* __restrict__ in, float* __restrict__ out, long n, float alpha, int accumulate) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = accumulate ? out[i] + alpha * in[i] : alpha * in[i];
@@ -497,6 +514,12 @@ int mapdit_patchify32(const float* x, float* patches, int ldp, int N, int C, int
     MD_CHECK(x && patches && N > 0, "patchify32: bad argument");
     const long M = (long)N * (S / p) * (S / p);
     P32_LAUNCH(patchify32_kernel, M * ldp, x, patches, ldp, C, S, p, M);
+}
+int mapdit_patch_embed_bwd_x32(const float* dx0, int ldx, const float* w_eff, float* dx, int N, int C, int S, int p, int D, float scale,
+                               void* stream) {
+    MD_CHECK(dx0 && w_eff && dx && N > 0 && C > 0 && p > 0 && S % p == 0 && D > 0 && ldx >= D, "patch_embed_bwd_x32: bad argument");
+    const long M = (long)N * (S / p) * (S / p);
+    P32_LAUNCH(patch_embed_bwd_x32_kernel, M * p * p * C, dx0, ldx, w_eff, dx, C, S, p, D, M, scale);
 }
 int mapdit_axpby32(const float* in, float* out, long n, float alpha, int accumulate, void* stream) {
     MD_CHECK(in && out && n > 0, "axpby32: bad argument");

@@ -230,7 +230,10 @@ class _Runtime:
 
 class _DiTFunction(torch.autograd.Function):
     """Autograd node for the whole network.  Parameter gradients are written by the engine straight into the
-    module's flat gradient buffer (``p.grad`` are views of it), so they are not returned to autograd."""
+    module's flat gradient buffer (``p.grad`` are views of it), so they are not returned to autograd.  With
+    ``model.input_gradients`` the gradient with respect to the latents ``x`` IS returned to autograd (the engine writes it
+    behind block 0's backward, mapdit_engine_set_input_grad); when no parameter requires grad the backward is input-only:
+    the activation-gradient chain alone, ``p.grad`` and the flat gradient buffer untouched."""
 
     @staticmethod
     def forward(ctx, model, rt, x, t, y_eff, anchor):
@@ -239,6 +242,8 @@ class _DiTFunction(torch.autograd.Function):
                               L.cur_stream())
         rt.generation += 1
         ctx.model, ctx.rt, ctx.generation = model, rt, rt.generation
+        ctx.x_shape = x.shape
+        ctx.params_need_grad = rt.params_need_grad
         return out
 
     @staticmethod
@@ -250,9 +255,17 @@ class _DiTFunction(torch.autograd.Function):
             raise L.MapditError("backward through a stale forward: the engine keeps the saved activations of the most recent "
                                 "training forward only (one outstanding forward per model; run backward before the next forward)")
         dout = dout.contiguous().float()
+        dx = torch.empty(ctx.x_shape, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        if dx is not None and not ctx.params_need_grad:
+            # input-only: frozen weights, dL/dx alone - no parameter gradient is computed, p.grad and the flat buffer stay as they are
+            rt.lib.engine_set_input_grad(rt.handle, dx.data_ptr(), 1)      # one-shot; a request left behind by a failed backward dies with the next forward
+            rt.lib.engine_backward(rt.handle, dout.data_ptr(), L.cur_stream())
+            return None, None, dx, None, None, None
         accumulate = model._attach_grads()
         keep = model._gflat.clone() if accumulate else None
         rt.bind(model)
+        if dx is not None:
+            rt.lib.engine_set_input_grad(rt.handle, dx.data_ptr(), 0)       # one-shot: consumed by the last stage below
         hook = getattr(model, "_stage_hook", None)
         if hook is None:
             rt.lib.engine_backward(rt.handle, dout.data_ptr(), L.cur_stream())
@@ -264,7 +277,29 @@ class _DiTFunction(torch.autograd.Function):
                 hook(stage)
         if keep is not None:
             model._gflat.add_(keep)
-        return None, None, None, None, None, None
+        return None, None, dx, None, None, None
+
+
+class _CfgCombineFunction(torch.autograd.Function):
+    """forward_with_cfg's tail under autograd: mapdit_cfg_combine and its backward kernel."""
+
+    @staticmethod
+    def forward(ctx, model_out, channels, hw, cfg_scale):
+        model_out = model_out.contiguous()
+        out = torch.empty_like(model_out)
+        with torch.cuda.device(model_out.device):
+            L.lib().cfg_combine(model_out.data_ptr(), out.data_ptr(), model_out.shape[0], channels, hw, cfg_scale, L.cur_stream())
+        ctx.args = (channels, hw, cfg_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        channels, hw, cfg_scale = ctx.args
+        dout = dout.contiguous().float()
+        din = torch.empty_like(dout)
+        with torch.cuda.device(dout.device):
+            L.lib().cfg_combine_bwd(dout.data_ptr(), din.data_ptr(), dout.shape[0], channels, hw, cfg_scale, L.cur_stream())
+        return din, None, None, None
 
 
 def _strip_compile_prefix(state_dict, prefix, *args):
@@ -333,6 +368,10 @@ class DiT(nn.Module):
         # forward and backward (several times slower).  See mapdit.h.
         self.gemm_precision = "f16"
         self._loss_scale = 0.0        # "f16" only: power-of-two loss scale of the backward (0 = chosen from the batch size)
+        # Opt-in (not part of the state dict): True = forward(x.requires_grad_()) is differentiable in x - train() and eval() alike it
+        # then takes the saved-activation path and backward returns dL/dx to autograd (input-only when no parameter requires grad).
+        # False (the default): such a call is refused, as the engine has always done.
+        self.input_gradients = False
         self._pflat = None            # flat fp32 storage behind every parameter (views)
         self._gflat = None            # flat gradient buffer, p.grad are views of it
         self._gviews = None
@@ -493,9 +532,9 @@ class DiT(nn.Module):
             L.lib().device_error_poll(L.cur_stream())
 
     def _check_inputs(self, x, t, y):
-        if x.requires_grad and torch.is_grad_enabled():
-            raise L.MapditError("gradients with respect to the input latents are not produced by the engine (no reference script "
-                                "uses them); detach x, or differentiate through a copy of the model in the reference framework")
+        if x.requires_grad and torch.is_grad_enabled() and not getattr(self, "input_gradients", False):
+            raise L.MapditError("gradients with respect to the input latents are not produced unless asked for (no reference script "
+                                "uses them): set model.input_gradients = True, or detach x")
         assert x.dim() == 4 and x.shape[1] == self.in_channels and x.shape[2] == x.shape[3] == self.input_size, \
             f"x must be [N,{self.in_channels},{self.input_size},{self.input_size}], got {tuple(x.shape)}"
         assert t.shape == (x.shape[0],) and y.shape == (x.shape[0],)
@@ -511,10 +550,13 @@ class DiT(nn.Module):
     @torch.compiler.disable
     def forward(self, x, t, y):
         """x [N,C,H,W], t [N], y [N] -> [N,2C,H,W]   (reference src/dit.py:70-105)."""
+        x_in = x
         x, t, y = self._check_inputs(x, t, y)
         if self.training and self.class_dropout_prob > 0:
             y = self.y_embedder.token_drop(y)                                   # label_embedder.py:19-34
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # (x.requires_grad passes _check_inputs with model.input_gradients only: the saved forward then serves dL/dx)
+        params_need_grad = any(p.requires_grad for p in self.parameters())
+        need_grad = torch.is_grad_enabled() and (params_need_grad or x_in.requires_grad)
         if not need_grad and getattr(self, "_shard_stale", False):
             raise L.MapditError("sharded weight passes (--grad-comm zero1w): this rank holds stale master rows of the other ranks after an "
                                 "optimiser step - call reducer.gather_state() before an inference forward, a checkpoint or an EMA snapshot")
@@ -535,6 +577,7 @@ class DiT(nn.Module):
                     rt.lib.engine_prepare_weights(rt.handle, 0, L.cur_stream())
                     rt.weights_key = key
             if need_grad:
+                rt.params_need_grad = params_need_grad       # (False: x alone requires grad - the backward will be input-only)
                 return _DiTFunction.apply(self, rt, x, t, y, self._anchor())
             out = torch.empty(x.shape[0], 2 * self.in_channels, self.input_size, self.input_size, device=x.device)
             rt.lib.engine_forward(rt.handle, x.data_ptr(), t.data_ptr(), y.data_ptr(), x.shape[0], 0, out.data_ptr(),
@@ -554,8 +597,10 @@ class DiT(nn.Module):
         half = x[: len(x) // 2]
         combined = torch.cat([half, half], dim=0)
         model_out = self.forward(combined, t, y)
-        out = torch.empty_like(model_out)
         hw = self.input_size * self.input_size
+        if torch.is_grad_enabled() and model_out.requires_grad:      # differentiable tail: gradients reach x and the parameters
+            return _CfgCombineFunction.apply(model_out, self.in_channels, hw, float(cfg_scale))
+        out = torch.empty_like(model_out)
         with torch.cuda.device(model_out.device):
             L.lib().cfg_combine(model_out.data_ptr(), out.data_ptr(), model_out.shape[0], self.in_channels, hw,
                                 float(cfg_scale), L.cur_stream())
@@ -576,6 +621,7 @@ class DiT(nn.Module):
             p_new.requires_grad_(p_old.requires_grad)
         new.train(self.training)
         new.gemm_precision, new._loss_scale = self.gemm_precision, self.loss_scale
+        new.input_gradients = getattr(self, "input_gradients", False)
         return new
 
     def __getstate__(self):
