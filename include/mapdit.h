@@ -545,7 +545,16 @@ typedef struct {
                        * divided by it again before it is written.  A finite power of two (anything else is refused: the division
                        * must be exact), or 0 = chosen per backward from the batch:
                        * 2^(floor(log2(N * C * S * S)) - 5), i.e. |dout| ~ 1/(N C S S) of a mean-reduced loss becomes ~1/32. */
+    int recompute;    /* Activation recompute of a training engine (additive within abi 5; a zero-initialised struct = none; ignored for
+                       * train == 0).  A plain engine keeps 40 * hidden bytes per token row and block for the backward.
+                       *   MAPDIT_RECOMPUTE_MLP    the two [rows, mlp_hidden] MLP tensors (activation and its derivative factor) exist once; a
+                       *                           block's backward stage first re-issues its fc1 GEMM on the saved modulated input: 24 * hidden
+                       *   MAPDIT_RECOMPUTE_BLOCK  a block keeps its two residual checkpoints, its modulated input and its MLP branch output
+                       *                           (12 * hidden); everything else exists once and the block's backward stage first re-issues the
+                       *                           block's forward - the very launches of the forward, so every gradient is bit-identical
+                       * to the plain engine's.  Not with MAPDIT_PREC_BF16X3, not with the LayerNorm form (MAPDIT_OFF_NO_LAYERNORM). */
 } mapdit_config_t;
+enum { MAPDIT_RECOMPUTE_NONE = 0, MAPDIT_RECOMPUTE_MLP = 1, MAPDIT_RECOMPUTE_BLOCK = 2 };
 /* MAPDIT_PREC_F16: the MAPDIT_PREC_BF16 engine with IEEE fp16 in place of bf16 for every GEMM / attention operand (weight images,
  * activations, activation gradients): same kernels, same MFMA rate, fp32 accumulation, fp32 residual stream and master weights,
  * fp32-accurate conditioning path.  10 mantissa bits instead of 7: forward logits within 1e-3 of the fp32 reference on every named
@@ -563,7 +572,8 @@ enum { MAPDIT_B_QKV = 0, MAPDIT_B_PROJ, MAPDIT_B_FC1, MAPDIT_B_FC2, MAPDIT_B_MOD
 
 typedef struct mapdit_engine mapdit_engine_t;
 
-/* Bytes of device workspace the engine needs (train != 0: activations of every block are kept for backward). */
+/* Bytes of device workspace the engine needs (train != 0: activations of every block are kept for backward, less what
+ * mapdit_config_t.recompute regenerates). */
 size_t mapdit_engine_workspace_bytes(const mapdit_config_t* cfg, int train);
 /* `workspace` must stay alive and 256-byte aligned; the engine zero-fills the parts it relies on being zero. */
 int mapdit_engine_create(const mapdit_config_t* cfg, int train, void* workspace, size_t workspace_bytes, void* stream,
@@ -576,7 +586,8 @@ int mapdit_engine_prepare_weights(mapdit_engine_t* e, int forced, void* stream);
 /* out [N, 2C, S, S] = DiT(x, t, y_eff); y_eff already has label drop applied.  save != 0 keeps activations. */
 int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const int64_t* t, const int64_t* y_eff, int N, int save,
                           float* out, void* stream);
-/* Backward of the last saved forward: writes d loss / d parameter into every bound grad pointer (overwrite). */
+/* Backward of the last saved forward: writes d loss / d parameter into every bound grad pointer (overwrite).  A bf16 / f16 engine
+ * reads the saved forward without changing it: the backward may be run again over the same forward (another dout). */
 int mapdit_engine_backward(mapdit_engine_t* e, const float* dout, void* stream);
 /* The same in pieces, for overlapping the data-parallel gradient reduction with backward: stage 0 = final layer,
  * stage k in 1..depth = block depth-k, stage depth+1 = patch embedding + conditioning path.  Stages must be run in
@@ -621,6 +632,8 @@ int mapdit_engine_profile_end(mapdit_engine_t* e, int* count, double* total_ms);
 enum { MAPDIT_PEEK_G_FOUR = 0, MAPDIT_PEEK_G_TEMB, MAPDIT_PEEK_G_C, MAPDIT_PEEK_G_MOD_ALL, MAPDIT_PEEK_G_X0, MAPDIT_PEEK_G_XMODF,
        MAPDIT_PEEK_G_LIN, MAPDIT_PEEK_B_XM, MAPDIT_PEEK_B_QKV, MAPDIT_PEEK_B_QN, MAPDIT_PEEK_B_KN, MAPDIT_PEEK_B_V, MAPDIT_PEEK_B_O,
        MAPDIT_PEEK_B_XM2, MAPDIT_PEEK_B_HACT, MAPDIT_PEEK_B_XMID, MAPDIT_PEEK_B_XOUT, MAPDIT_PEEK_COUNT };
+/* Under mapdit_config_t.recompute the per-block ids whose buffer exists once for all blocks are refused (MLP: B_HACT; BLOCK: B_QKV, B_QN,
+ * B_KN, B_V, B_O, B_XM2, B_HACT too); B_XM, B_XMID, B_XOUT and the G_* ids answer as ever. */
 int mapdit_engine_peek(mapdit_engine_t* e, int what, int block, void** ptr, long* elems, int* ld, int* dtype);
 
 /* ------------------------------------------------------------------------------------------------------------

@@ -96,6 +96,10 @@ struct mapdit_engine {
     float* ig_dx = nullptr;
     bool ig_only = false;
     bool have_saved = false;
+    // mapdit_config_t.recompute of a 16-bit training engine (0 otherwise).  blk[] keeps one entry per block at every level: a buffer that
+    // exists once (MLP: hact, hdact; BLOCK: everything but xm and y2) is carved with block 0 and every other entry points at it, and block
+    // i's backward stage starts by putting block i back into it (recompute_block).
+    int rc = MAPDIT_RECOMPUTE_NONE;
     std::vector<float*> params, grads;
     // weight images
     std::vector<WeightImg> wimg;          // indexed like the parameter table (linears only)
@@ -256,23 +260,29 @@ size_t carve(mapdit_engine* e, void* base) {
     // bf16 activations of the fast path (a bf16x3 engine keeps fp32 ones instead: px / pblk below)
     const int nb = precise ? 0 : (e->train ? L : 1);
     e->blk.assign(nb, BlockBufs());
+    e->rc = e->train && !precise ? c.recompute : MAPDIT_RECOMPUTE_NONE;
     for (int i = 0; i < nb; ++i) {
         BlockBufs& b = e->blk[i];
+        // activation recompute: what the level regenerates exists once, carved with block 0 (mapdit_engine::rc).  Per block stay xm (it comes
+        // out of the PREVIOUS block's fc2 epilogue) and y2: the last residual / modulate pass of block i + 1's stage reads it while the
+        // shared set holds block i + 1.
+        const bool one_mlp = i > 0 && e->rc >= MAPDIT_RECOMPUTE_MLP, one_blk = i > 0 && e->rc == MAPDIT_RECOMPUTE_BLOCK;
+        const BlockBufs& s = e->blk[0];
         b.xm = cv.take<bf16_t>(M * D);
         // the fused QKV epilogue never writes qkv; nor does the head_dim-72 path without split / merge passes (raw72: q, k, v head-major
         // straight from the GEMM) - DiT-XL/2: 113 MB x 28 blocks at 64 samples that were carved and never touched
-        b.qkv = (e->generic_attn && !e->raw72 && !e->sdpa) ? cv.take<bf16_t>(M * 3 * D) : nullptr;
-        b.qks = ((e->generic_attn && !e->raw72) || e->sdpa) ? nullptr : cv.take<float>((size_t)2 * N * c.num_heads * T);
-        b.qn = cv.take<bf16_t>(M * D);
-        b.kn = cv.take<bf16_t>(M * D);
-        b.v = cv.take<bf16_t>(M * D);
-        b.o = cv.take<bf16_t>(M * D);
-        b.y = e->train ? cv.take<bf16_t>(M * D) : nullptr;
-        b.xm2 = cv.take<bf16_t>(M * D);
-        b.hdact = e->train ? cv.take<bf16_t>(M * Hm) : nullptr;
-        b.hact = cv.take<bf16_t>(M * Hm);
+        b.qkv = one_blk ? s.qkv : (e->generic_attn && !e->raw72 && !e->sdpa) ? cv.take<bf16_t>(M * 3 * D) : nullptr;
+        b.qks = one_blk ? s.qks : ((e->generic_attn && !e->raw72) || e->sdpa) ? nullptr : cv.take<float>((size_t)2 * N * c.num_heads * T);
+        b.qn = one_blk ? s.qn : cv.take<bf16_t>(M * D);
+        b.kn = one_blk ? s.kn : cv.take<bf16_t>(M * D);
+        b.v = one_blk ? s.v : cv.take<bf16_t>(M * D);
+        b.o = one_blk ? s.o : cv.take<bf16_t>(M * D);
+        b.y = one_blk ? s.y : e->train ? cv.take<bf16_t>(M * D) : nullptr;
+        b.xm2 = one_blk ? s.xm2 : cv.take<bf16_t>(M * D);
+        b.hdact = one_mlp ? s.hdact : e->train ? cv.take<bf16_t>(M * Hm) : nullptr;
+        b.hact = one_mlp ? s.hact : cv.take<bf16_t>(M * Hm);
         b.y2 = e->train ? cv.take<bf16_t>(M * D) : nullptr;
-        b.lse = cv.take<float>((size_t)N * c.num_heads * T);
+        b.lse = one_blk ? s.lse : cv.take<float>((size_t)N * c.num_heads * T);
     }
     e->patches = e->train && !precise ? cv.take<bf16_t>(M * e->ldp) : nullptr;
     e->fmod = cv.take<float>((size_t)N * 2 * D);
@@ -406,7 +416,7 @@ bool loss_scale_ok(float s) {
     return frexpf(s, &ex) == 0.5f;
 }
 
-int check_cfg(const mapdit_config_t* c) {
+int check_cfg(const mapdit_config_t* c, int train) {
     MD_CHECK(c, "engine: null config");
     MD_CHECK(c->depth > 0 && c->hidden > 0 && c->max_batch > 0, "engine: empty config");
     MD_CHECK(c->precision == MAPDIT_PREC_BF16 || c->precision == MAPDIT_PREC_BF16X3 || c->precision == MAPDIT_PREC_F16,
@@ -436,6 +446,13 @@ int check_cfg(const mapdit_config_t* c) {
     MD_CHECK(c->mlp_hidden % 64 == 0, "engine: mlp_hidden=%d must be a multiple of 64", c->mlp_hidden);
     MD_CHECK(c->patch * c->patch * c->in_channels <= 256 && (c->patch * c->patch * c->in_channels) % 4 == 0,
              "engine: patch dim %d unsupported", c->patch * c->patch * c->in_channels);
+    MD_CHECK(c->recompute == MAPDIT_RECOMPUTE_NONE || c->recompute == MAPDIT_RECOMPUTE_MLP || c->recompute == MAPDIT_RECOMPUTE_BLOCK,
+             "engine: unknown activation recompute level %d (0 none, 1 mlp, 2 block)", c->recompute);
+    if (train && c->recompute != MAPDIT_RECOMPUTE_NONE) {   // (an inference engine keeps no activations: the field is not looked at)
+        MD_CHECK(c->precision != MAPDIT_PREC_BF16X3, "engine: activation recompute is not built for the bf16x3 engine (its fp32 activations are a set of their own)");
+        MD_CHECK(!(c->mp_off & MAPDIT_OFF_NO_LAYERNORM),
+                 "engine: activation recompute is not built for the LayerNorm form (no-layernorm off keeps a normalised copy per site)");
+    }
     return MAPDIT_OK;
 }
 
@@ -855,7 +872,7 @@ extern "C" int mapdit_device_error_poll(void* stream) {
 }
 
 extern "C" size_t mapdit_engine_workspace_bytes(const mapdit_config_t* cfg, int train) {
-    if (check_cfg(cfg) != MAPDIT_OK) return 0;
+    if (check_cfg(cfg, train) != MAPDIT_OK) return 0;
     mapdit_engine tmp;
     tmp.cfg = *cfg;
     tmp.train = train;
@@ -877,7 +894,7 @@ static void side_release(mapdit_engine* e) {
 
 extern "C" int mapdit_engine_create(const mapdit_config_t* cfg, int train, void* workspace, size_t workspace_bytes, void* stream,
                                     mapdit_engine_t** out) {
-    TRY(check_cfg(cfg));
+    TRY(check_cfg(cfg, train));
     MD_CHECK(workspace && out, "engine_create: null argument");
     MD_CHECK(((uintptr_t)workspace & 255) == 0, "engine_create: workspace must be 256-byte aligned");
     mapdit_engine* e = new mapdit_engine();
@@ -1358,6 +1375,113 @@ static int backward_precise(mapdit_engine* e, const float* dout, int stage_from,
     return MAPDIT_OK;
 }
 
+namespace {
+
+// The (scale, shift) rows of a branch's modulate and the gain it blends them with (br 0 = attention branch, 1 = MLP branch).  Rotation
+// modulation: the A / B coefficient rows of y[j] = A x[j] + B x[j ^ 1] (mapdit_rot_coef_fwd: one pass over [samples, L * 2 * D], one
+// sincos per pair), read by the same fused epilogues in their rot form - slot (block, branch) at column (2 * block + branch) * D.
+const float* mod_scale(const mapdit_engine* e, int i, int br) {
+    return e->rot ? e->rotA + (size_t)(2 * i + br) * e->D : e->mod_all + (size_t)i * e->MW + (br ? e->o_scm : e->o_sca);
+}
+const float* mod_shift(const mapdit_engine* e, int i, int br) {
+    return e->rot ? e->rotB + (size_t)(2 * i + br) * e->D : e->mod_all + (size_t)i * e->MW + (br ? e->o_shm : e->o_sha);
+}
+const float* mod_gain(const mapdit_engine* e, int pidx) { return e->rot ? e->zero_gain : e->params[pidx]; }
+
+// LayerNorm form: site j = X[j] -> LN -> modulate -> the branch's operand, one launch after the GEMM that wrote X[j] (whose epilogue then
+// writes no modulated output)
+int ln_site(mapdit_engine* e, int save, int N, int j, const float* xj, const float* sh, const float* sc, int ld, const float* gain, bf16_t* dst,
+            void* st) {
+    return DT_FN(e, mapdit_ln_modulate_fwd)(xj, sh, sc, ld, gain, save ? e->XH[j] : nullptr, save ? e->rstd[j] : nullptr, dst, N, e->T, e->D, st);
+}
+
+// fc1 of block i's MLP on its modulated input xm2: the activation and, for a saved forward, its derivative factor.  The forward and the
+// backward stage of a MAPDIT_RECOMPUTE_MLP engine (hact / hdact exist once) issue this one launch.
+int fc1_forward(mapdit_engine* e, int i, int M, int save, void* st) {
+    const BlockBufs& b = e->blk[save ? i : 0];
+    const bool timed = e->prof_which == MAPDIT_PROF_FC1_FWD && e->prof_used < e->prof_start.size() && (e->prof_seen++ % e->prof_stride) == 0;
+    if (timed) (void)hipEventRecord(e->prof_start[e->prof_used], (hipStream_t)st);
+    TRY(gemm16(e, MAPDIT_NT, M, e->Hm, e->D, b.xm2, e->D, e->wimg[pidx_block(i, MAPDIT_B_FC1)].img, e->D,
+               epi_silu2_grad(save ? b.hdact : nullptr, b.hact, e->Hm), st));
+    if (timed) (void)hipEventRecord(e->prof_stop[e->prof_used++], (hipStream_t)st);
+    return MAPDIT_OK;
+}
+
+// Block i of the 16-bit forward: from its modulated input blk[i].xm and the residual checkpoint X[2i] to X[2i+1], X[2i+2] and the
+// modulated input of what follows (block i + 1's xm, or the final layer's xmodf).  mapdit_engine_forward runs it block by block; the
+// backward stage of a MAPDIT_RECOMPUTE_BLOCK engine runs it again for its block - the same launches with the same arguments, so the
+// activations come back bit for bit (every kernel is deterministic) and the RESID epilogues rewrite X[2i+1], X[2i+2] and the next xm
+// with the bits they already hold.
+int block_forward(mapdit_engine* e, int i, int N, int save, void* st) {
+    const mapdit_config_t& c = e->cfg;
+    const int D = e->D, T = e->T, Hm = e->Hm, L = c.depth, H = e->heads, M = N * T, ldm = e->ldm;
+    auto W = [&](int idx) { return e->wimg[idx].img; };
+    const int rot = e->rot ? 1 : 0;
+    const int ldn = e->rot ? e->ldc : ldm;
+    BlockBufs& b = e->blk[save ? i : 0];
+    const float* mod = e->mod_all + (size_t)i * e->MW;
+    float* xin = e->X[save ? 2 * i : (2 * i) % 3];
+    float* xmid = e->X[save ? 2 * i + 1 : (2 * i + 1) % 3];
+    float* xout = e->X[save ? 2 * i + 2 : (2 * i + 2) % 3];
+    const float* gmlp = mod_gain(e, pidx_block(i, MAPDIT_B_GAIN_MLP));
+    // attention branch (dit_block.py:35); b.xm = modulate(xin, shift_msa, scale_msa, gain_msa) is already there
+    // inference at head_dim 72 (DiT-XL sampling): the GEMM epilogue writes q, k, v head-major and the attention kernel normalises
+    // q, k while it stages them - no split / normalise pass over the QKV result (219 us of a 2.4 ms block at 256 x 256 tokens)
+    const bool raw72 = e->raw72;
+    if (raw72 || e->sdpa) {      // (sdpa: README.md:58 off form - q, k stay as the projection gave them, for any head_dim % 8 == 0)
+        mapdit_epilogue_t ep;
+        memset(&ep, 0, sizeof(ep));
+        ep.kind = MAPDIT_EPI_QKV_HEADS_RAW;
+        ep.out = b.qn; ep.out2 = b.kn; ep.out3 = b.v;
+        ep.rows_per_sample = T; ep.ld2 = e->hd;
+        ep.alpha = 1.f;
+        TRY(gemm16(e, MAPDIT_NT, M, 3 * D, D, b.xm, D, W(pidx_block(i, MAPDIT_B_QKV)), D, ep, st));
+    } else if (e->generic_attn) {
+        TRY(gemm16(e, MAPDIT_NT, M, 3 * D, D, b.xm, D, W(pidx_block(i, MAPDIT_B_QKV)), D, epi_bf16(b.qkv, 3 * D), st));
+        TRY(DT_FN(e, mapdit_qkv_split)(b.qkv, N, T, H, e->hd, b.qn, b.kn, b.v, st));
+    } else {   // head split + cosine normalisation of q, k in the GEMM epilogue (attention.py:38-43)
+        mapdit_epilogue_t ep;
+        memset(&ep, 0, sizeof(ep));
+        ep.kind = MAPDIT_EPI_QKV_HEADS;
+        ep.out = b.qn; ep.out2 = b.kn; ep.out3 = b.v; ep.out4 = b.qks;
+        ep.rows_per_sample = T;
+        ep.alpha = 1.f;
+        TRY(gemm16(e, MAPDIT_NT, M, 3 * D, D, b.xm, D, W(pidx_block(i, MAPDIT_B_QKV)), D, ep, st));
+    }
+    if (e->sdpa) TRY(DT_FN(e, mapdit_attn_sdpa_fwd)(b.qn, b.kn, b.v, b.o, b.lse, N, T, H, e->hd, st));
+    else if (raw72 && save) TRY(DT_FN(e, mapdit_attn_cos_fwd_rawqk_save)(b.qn, b.kn, b.v, b.o, b.lse, b.qks, N, T, H, e->hd, st));
+    else if (raw72) TRY(DT_FN(e, mapdit_attn_cos_fwd_rawqk)(b.qn, b.kn, b.v, b.o, b.lse, N, T, H, e->hd, st));
+    else TRY(DT_FN(e, mapdit_attn_cos_fwd)(b.qn, b.kn, b.v, b.o, b.lse, N, T, H, e->hd, st));
+    TRY(gemm16(e, MAPDIT_NT, M, D, D, b.o, D, W(pidx_block(i, MAPDIT_B_PROJ)), D,
+             epi_resid(e->ca, e->cb_attn, save ? b.y : nullptr, xin, xmid, mod + e->o_ga, ldm, T, D, e->ln ? nullptr : b.xm2, mod_shift(e, i, 1),
+                       mod_scale(e, i, 1), ldn, gmlp, rot), st));
+    if (e->ln) TRY(ln_site(e, save, N, 2 * i + 1, xmid, mod_shift(e, i, 1), mod_scale(e, i, 1), ldn, gmlp, b.xm2, st));
+    // MLP branch (dit_block.py:36); b.xm2 = modulate(xmid, shift_mlp, scale_mlp, gain_mlp) came out of the epilogue above
+    TRY(fc1_forward(e, i, M, save, st));
+    bf16_t* xm_next = i + 1 < L ? e->blk[save ? i + 1 : 0].xm : e->xmodf;
+    TRY(gemm16(e, MAPDIT_NT, M, D, Hm, b.hact, Hm, W(pidx_block(i, MAPDIT_B_FC2)), Hm,
+             i + 1 < L ? epi_resid(e->ca, e->cb_mlp, save ? b.y2 : nullptr, xmid, xout, mod + e->o_gm, ldm, T, D, e->ln ? nullptr : xm_next,
+                                   mod_shift(e, i + 1, 0), mod_scale(e, i + 1, 0), ldn, mod_gain(e, pidx_block(i + 1, MAPDIT_B_GAIN_MSA)), rot)
+                       : epi_resid(e->ca, e->cb_mlp, save ? b.y2 : nullptr, xmid, xout, mod + e->o_gm, ldm, T, D, e->ln ? nullptr : xm_next, e->fmod,
+                                   e->fmod + D, 2 * D, e->params[MAPDIT_P_F_GAIN]), st));
+    if (e->ln) {
+        if (i + 1 < L) TRY(ln_site(e, save, N, 2 * i + 2, xout, mod_shift(e, i + 1, 0), mod_scale(e, i + 1, 0), ldn, mod_gain(e, pidx_block(i + 1, MAPDIT_B_GAIN_MSA)), xm_next, st));
+        else TRY(ln_site(e, save, N, 2 * L, xout, e->fmod, e->fmod + D, 2 * D, e->params[MAPDIT_P_F_GAIN], xm_next, st));
+    }
+    return MAPDIT_OK;
+}
+
+// Start of block i's backward stage in a recomputing engine: the buffers that exist once hold whichever block wrote them last, so put
+// block i back before anything reads them.  Only what the forward itself launched is launched (no kernel or tile choice of its own): that is
+// what makes the gradients bit-identical to the plain engine's.  What the re-run reads is per block at either level (xm, X[2i]; xm2).
+int recompute_block(mapdit_engine* e, int i, void* st) {
+    if (e->rc == MAPDIT_RECOMPUTE_BLOCK) return block_forward(e, i, e->last_N, 1, st);
+    if (e->rc == MAPDIT_RECOMPUTE_MLP) return fc1_forward(e, i, e->last_N * e->T, 1, st);
+    return MAPDIT_OK;
+}
+
+}  // namespace
+
 extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const int64_t* t, const int64_t* y_eff, int N, int save,
                                      float* out, void* st) {
     MD_CHECK(e && x && t && y_eff && out, "engine_forward: null argument");
@@ -1365,7 +1489,7 @@ extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const i
     MD_CHECK(!save || e->train, "engine_forward: save requested on an inference-only engine");
     const mapdit_config_t& c = e->cfg;
     if (c.precision == MAPDIT_PREC_BF16X3) return forward_precise(e, x, t, y_eff, N, save, out, st);
-    const int D = e->D, T = e->T, Hm = e->Hm, L = c.depth, H = e->heads;
+    const int D = e->D, T = e->T, L = c.depth;
     const int M = N * T;
     auto W = [&](int idx) { return e->wimg[idx].img; };
 
@@ -1404,9 +1528,7 @@ extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const i
     TRY(mapdit_split3(e->c, D, e->cp.As, N, D, MAPDIT_SPLIT_A, MAPDIT_SPLIT_OP_MPSILU, st));
     TRY(gemm(MAPDIT_NT, N, ldm, 3 * D, e->cp.As, 3 * D, e->cp.img3[pidx_block(0, MAPDIT_B_MOD)], 3 * D, epi_f32(e->mod_all, ldm, sa), st));
     TRY(gemm(MAPDIT_NT, N, 2 * D, 3 * D, e->cp.As, 3 * D, e->cp.img3[MAPDIT_P_F_MOD], 3 * D, epi_f32(e->fmod, 2 * D, sa), st));
-    // The (scale, shift) rows of a branch's modulate and the gain it blends them with.  Rotation modulation: the A / B coefficient
-    // rows of y[j] = A x[j] + B x[j ^ 1] (mapdit_rot_coef_fwd: one pass over [samples, L * 2 * D], one sincos per pair), read by the
-    // same fused epilogues in their rot form - slot (block, branch) at column (2 * block + branch) * D.
+    // rotation modulation: the A / B coefficient rows of every (block, branch), read through mod_scale / mod_shift
     if (e->rot) {
         if (2 * L <= MAPDIT_ROT_MAX_SLOTS) {               // every (block, branch) in one launch (2 L tiny launches before: ADVICE r03)
             int th[MAPDIT_ROT_MAX_SLOTS], sc[MAPDIT_ROT_MAX_SLOTS];
@@ -1426,79 +1548,13 @@ extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const i
             }
         }
     }
-    const int rot = e->rot ? 1 : 0;
-    const int ldn = e->rot ? e->ldc : ldm;
-    auto sc_of = [&](int i, int br) -> const float* {       // br 0 = attention branch, 1 = MLP branch
-        return e->rot ? e->rotA + (size_t)(2 * i + br) * D : e->mod_all + (size_t)i * e->MW + (br ? e->o_scm : e->o_sca);
-    };
-    auto sh_of = [&](int i, int br) -> const float* {
-        return e->rot ? e->rotB + (size_t)(2 * i + br) * D : e->mod_all + (size_t)i * e->MW + (br ? e->o_shm : e->o_sha);
-    };
-    auto gain_of = [&](int pidx) -> const float* { return e->rot ? e->zero_gain : e->params[pidx]; };
-    // LayerNorm form: site j = X[j] -> LN -> modulate -> the branch's operand, one launch after the GEMM that wrote X[j] (whose epilogue then
-    // writes no modulated output)
-    auto ln_site = [&](int j, const float* xj, const float* sh, const float* sc, int ld, const float* gain, bf16_t* dst) -> int {
-        return DT_FN(e, mapdit_ln_modulate_fwd)(xj, sh, sc, ld, gain, save ? e->XH[j] : nullptr, save ? e->rstd[j] : nullptr, dst, N, T, D, st);
-    };
-    if (e->ln) TRY(ln_site(0, e->X[0], sh_of(0, 0), sc_of(0, 0), ldm, gain_of(pidx_block(0, MAPDIT_B_GAIN_MSA)), e->blk[0].xm));
-    else if (e->rot) TRY(DT_FN(e, mapdit_rot_modulate_fwd)(e->X[0], sc_of(0, 0), sh_of(0, 0), ldn, e->blk[0].xm, N, T, D, st));
-    else TRY(DT_FN(e, mapdit_modulate_fwd)(e->X[0], sh_of(0, 0), sc_of(0, 0), ldm, gain_of(pidx_block(0, MAPDIT_B_GAIN_MSA)), e->blk[0].xm,
-                                           N, T, D, st));
+    const float* gain0 = mod_gain(e, pidx_block(0, MAPDIT_B_GAIN_MSA));
+    if (e->ln) TRY(ln_site(e, save, N, 0, e->X[0], mod_shift(e, 0, 0), mod_scale(e, 0, 0), ldm, gain0, e->blk[0].xm, st));
+    else if (e->rot) TRY(DT_FN(e, mapdit_rot_modulate_fwd)(e->X[0], mod_scale(e, 0, 0), mod_shift(e, 0, 0), e->ldc, e->blk[0].xm, N, T, D, st));
+    else TRY(DT_FN(e, mapdit_modulate_fwd)(e->X[0], mod_shift(e, 0, 0), mod_scale(e, 0, 0), ldm, gain0, e->blk[0].xm, N, T, D, st));
     for (int i = 0; i < L; ++i) {
         if (i > 0 && !fences.empty()) HIP_TRY(hipStreamWaitEvent((hipStream_t)st, fences[i], 0), "engine_forward: block fence");
-        BlockBufs& b = e->blk[save ? i : 0];
-        const float* mod = e->mod_all + (size_t)i * e->MW;
-        float* xin = e->X[save ? 2 * i : (2 * i) % 3];
-        float* xmid = e->X[save ? 2 * i + 1 : (2 * i + 1) % 3];
-        float* xout = e->X[save ? 2 * i + 2 : (2 * i + 2) % 3];
-        const float* gmlp = gain_of(pidx_block(i, MAPDIT_B_GAIN_MLP));
-        // attention branch (dit_block.py:35); b.xm = modulate(xin, shift_msa, scale_msa, gain_msa) is already there
-        // inference at head_dim 72 (DiT-XL sampling): the GEMM epilogue writes q, k, v head-major and the attention kernel normalises
-        // q, k while it stages them - no split / normalise pass over the QKV result (219 us of a 2.4 ms block at 256 x 256 tokens)
-        const bool raw72 = e->raw72;
-        if (raw72 || e->sdpa) {      // (sdpa: README.md:58 off form - q, k stay as the projection gave them, for any head_dim % 8 == 0)
-            mapdit_epilogue_t ep;
-            memset(&ep, 0, sizeof(ep));
-            ep.kind = MAPDIT_EPI_QKV_HEADS_RAW;
-            ep.out = b.qn; ep.out2 = b.kn; ep.out3 = b.v;
-            ep.rows_per_sample = T; ep.ld2 = e->hd;
-            ep.alpha = 1.f;
-            TRY(gemm16(e, MAPDIT_NT, M, 3 * D, D, b.xm, D, W(pidx_block(i, MAPDIT_B_QKV)), D, ep, st));
-        } else if (e->generic_attn) {
-            TRY(gemm16(e, MAPDIT_NT, M, 3 * D, D, b.xm, D, W(pidx_block(i, MAPDIT_B_QKV)), D, epi_bf16(b.qkv, 3 * D), st));
-            TRY(DT_FN(e, mapdit_qkv_split)(b.qkv, N, T, H, e->hd, b.qn, b.kn, b.v, st));
-        } else {   // head split + cosine normalisation of q, k in the GEMM epilogue (attention.py:38-43)
-            mapdit_epilogue_t ep;
-            memset(&ep, 0, sizeof(ep));
-            ep.kind = MAPDIT_EPI_QKV_HEADS;
-            ep.out = b.qn; ep.out2 = b.kn; ep.out3 = b.v; ep.out4 = b.qks;
-            ep.rows_per_sample = T;
-            ep.alpha = 1.f;
-            TRY(gemm16(e, MAPDIT_NT, M, 3 * D, D, b.xm, D, W(pidx_block(i, MAPDIT_B_QKV)), D, ep, st));
-        }
-        if (e->sdpa) TRY(DT_FN(e, mapdit_attn_sdpa_fwd)(b.qn, b.kn, b.v, b.o, b.lse, N, T, H, e->hd, st));
-        else if (raw72 && save) TRY(DT_FN(e, mapdit_attn_cos_fwd_rawqk_save)(b.qn, b.kn, b.v, b.o, b.lse, b.qks, N, T, H, e->hd, st));
-        else if (raw72) TRY(DT_FN(e, mapdit_attn_cos_fwd_rawqk)(b.qn, b.kn, b.v, b.o, b.lse, N, T, H, e->hd, st));
-        else TRY(DT_FN(e, mapdit_attn_cos_fwd)(b.qn, b.kn, b.v, b.o, b.lse, N, T, H, e->hd, st));
-        TRY(gemm16(e, MAPDIT_NT, M, D, D, b.o, D, W(pidx_block(i, MAPDIT_B_PROJ)), D,
-                 epi_resid(e->ca, e->cb_attn, save ? b.y : nullptr, xin, xmid, mod + e->o_ga, ldm, T, D, e->ln ? nullptr : b.xm2, sh_of(i, 1), sc_of(i, 1), ldn,
-                           gmlp, rot), st));
-        if (e->ln) TRY(ln_site(2 * i + 1, xmid, sh_of(i, 1), sc_of(i, 1), ldn, gmlp, b.xm2));
-        // MLP branch (dit_block.py:36); b.xm2 = modulate(xmid, shift_mlp, scale_mlp, gain_mlp) came out of the epilogue above
-        const bool timed = e->prof_which == MAPDIT_PROF_FC1_FWD && e->prof_used < e->prof_start.size() && (e->prof_seen++ % e->prof_stride) == 0;
-        if (timed) (void)hipEventRecord(e->prof_start[e->prof_used], (hipStream_t)st);
-        TRY(gemm16(e, MAPDIT_NT, M, Hm, D, b.xm2, D, W(pidx_block(i, MAPDIT_B_FC1)), D, epi_silu2_grad(save ? b.hdact : nullptr, b.hact, Hm), st));
-        if (timed) (void)hipEventRecord(e->prof_stop[e->prof_used++], (hipStream_t)st);
-        TRY(gemm16(e, MAPDIT_NT, M, D, Hm, b.hact, Hm, W(pidx_block(i, MAPDIT_B_FC2)), Hm,
-                 i + 1 < L ? epi_resid(e->ca, e->cb_mlp, save ? b.y2 : nullptr, xmid, xout, mod + e->o_gm, ldm, T, D,
-                                       e->ln ? nullptr : e->blk[save ? i + 1 : 0].xm,
-                                       sh_of(i + 1, 0), sc_of(i + 1, 0), ldn, gain_of(pidx_block(i + 1, MAPDIT_B_GAIN_MSA)), rot)
-                           : epi_resid(e->ca, e->cb_mlp, save ? b.y2 : nullptr, xmid, xout, mod + e->o_gm, ldm, T, D, e->ln ? nullptr : e->xmodf, e->fmod,
-                                       e->fmod + D, 2 * D, e->params[MAPDIT_P_F_GAIN]), st));
-        if (e->ln) {
-            if (i + 1 < L) TRY(ln_site(2 * i + 2, xout, sh_of(i + 1, 0), sc_of(i + 1, 0), ldn, gain_of(pidx_block(i + 1, MAPDIT_B_GAIN_MSA)), e->blk[save ? i + 1 : 0].xm));
-            else TRY(ln_site(2 * L, xout, e->fmod, e->fmod + D, 2 * D, e->params[MAPDIT_P_F_GAIN], e->xmodf));
-        }
+        TRY(block_forward(e, i, N, save, st));
     }
     float* xL = e->X[save ? 2 * L : (2 * L) % 3];
     // final layer                                                       (final_layer.py:53-59, dit.py:96-101)
@@ -1526,6 +1582,13 @@ extern "C" int mapdit_engine_peek(mapdit_engine_t* e, int what, int block, void*
     MD_CHECK(!per_block || (block >= 0 && block < e->cfg.depth), "engine_peek: block %d outside 0..%d", block, e->cfg.depth - 1);
     const long N = e->last_N, M = N * e->T, D = e->D;
     const BlockBufs* b = per_block ? &e->blk[block] : nullptr;
+    {   // activation recompute: a buffer that exists once holds whichever block wrote it last, not `block`
+        const bool once_mlp = what == MAPDIT_PEEK_B_HACT;
+        const bool once_blk = once_mlp || what == MAPDIT_PEEK_B_QKV || what == MAPDIT_PEEK_B_QN || what == MAPDIT_PEEK_B_KN || what == MAPDIT_PEEK_B_V ||
+                              what == MAPDIT_PEEK_B_O || what == MAPDIT_PEEK_B_XM2;
+        MD_CHECK(!((e->rc == MAPDIT_RECOMPUTE_BLOCK && once_blk) || (e->rc == MAPDIT_RECOMPUTE_MLP && once_mlp)),
+                 "engine_peek: id %d is not kept per block under activation recompute level %d", what, e->rc);
+    }
     void* p = nullptr;
     long n = 0;
     int l = (int)D, dt = 1;
@@ -1649,6 +1712,7 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     for (int i = L - 1; i >= 0; --i) {
         const int stage = L - i;
         if (stage < stage_from || stage > stage_to) continue;
+        TRY(recompute_block(e, i, st));                       // (activation recompute: block i back into the buffers that exist once)
         const BlockBufs& b = e->blk[i];
         float* dmod = e->dmod + (size_t)i * e->MW;            // [N][L*MW] like mod_all
         const float* mod = e->mod_all + (size_t)i * e->MW;
@@ -1734,8 +1798,7 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     }
     if (io) {
         e->ig_only = false;
-        e->have_saved = false;
-        e->next_stage = 0;
+        e->next_stage = 0;                // (the saved forward stays: a backward reads it and changes none of it - it may run again)
         return side_join(e, st);
     }
     {
@@ -1759,7 +1822,6 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     // (plain SiLU: temb = 0.596 W2 mp_silu(h1) - the factor reaches both weight gradients of the timestep MLP; dh1 itself has no other use)
     TRY(linear_dw(e, MAPDIT_P_T2, e->dtemb_bf, D, e->h1_act, D, N, sa, st));
     TRY(linear_dw(e, MAPDIT_P_T0, e->dh1_bf, D, e->four, FOURIER, N, sa, st));
-    e->have_saved = false;
-    e->next_stage = 0;
+    e->next_stage = 0;                    // (the saved forward stays, as above)
     return side_join(e, st);
 }

@@ -183,9 +183,10 @@ def get_2d_sincos_pos_embed(embed_dim: int, grid_size: int) -> np.ndarray:
 class _Runtime:
     """Owns a mapdit engine handle and its workspace tensor."""
 
-    def __init__(self, model: "DiT", max_batch: int, train: bool, precision: str = "bf16"):
+    def __init__(self, model: "DiT", max_batch: int, train: bool, precision: str = "bf16", recompute: str = "none"):
         lib = L.lib()
         self.lib, self.train, self.max_batch, self.precision = lib, train, max_batch, precision
+        self.recompute = recompute if train else "none"      # (an inference engine keeps no activations)
         self.device = model.pos_embed.device
         rows = model.y_embedder.embedding.weight.shape[0]
         self.cfg = L.Config(depth=len(model.blocks), hidden=model.hidden_size, patch=model.patch_size,
@@ -193,7 +194,8 @@ class _Runtime:
                             mlp_hidden=model.blocks[0].mlp.hidden_dim, table_rows=rows, max_batch=max_batch,
                             precision=L.PRECISIONS[precision], rotation=int(getattr(model, "rotation_modulation", False)),
                             mp_off=sum(bit for name, bit in L.MP_OFF.items() if not getattr(model, name, True)),
-                            loss_scale=float(getattr(model, "loss_scale", 0.0)) if precision == "f16" else 0.0)
+                            loss_scale=float(getattr(model, "loss_scale", 0.0)) if precision == "f16" else 0.0,
+                            recompute=L.RECOMPUTE[self.recompute])
         need = lib.engine_workspace_bytes(C.byref(self.cfg), int(train))
         if need == 0:
             raise L.MapditError(f"unsupported DiT configuration: {lib.last_error().decode()}")
@@ -372,6 +374,10 @@ class DiT(nn.Module):
         # then takes the saved-activation path and backward returns dL/dx to autograd (input-only when no parameter requires grad).
         # False (the default): such a call is refused, as the engine has always done.
         self.input_gradients = False
+        # Opt-in (not part of the state dict): "mlp" / "block" = the training engine keeps 24 / 12 instead of 40 x hidden bytes per token
+        # row and block and re-runs the block's fc1 GEMM / the block's forward at the start of its backward stage (mapdit_config_t.recompute);
+        # gradients are bit-identical to "none".  Inference runtimes are not affected.
+        self._activation_recompute = "none"
         self._pflat = None            # flat fp32 storage behind every parameter (views)
         self._gflat = None            # flat gradient buffer, p.grad are views of it
         self._gviews = None
@@ -461,12 +467,17 @@ class DiT(nn.Module):
         precision = getattr(self, "gemm_precision", "f16")
         if precision not in L.PRECISIONS:
             raise L.MapditError(f"gemm_precision must be one of {sorted(L.PRECISIONS)}, got {precision!r}")
+        # The recompute level belongs to a training runtime's identity like its precision does, but a slot holds ONE level: a runtime of
+        # another level is dropped first (two training workspaces alive would save nothing).  The slot names themselves stay
+        # (precision, train): the benchmark, the reducers and _peek look runtimes up by them.
+        recompute = self.activation_recompute if train else "none"
         slot = train if precision == "bf16" else (precision, train)
         rt = self._rt.get(slot)
-        if rt is None or rt.max_batch < batch or rt.device != self._pflat.device:
+        if rt is None or rt.max_batch < batch or rt.device != self._pflat.device or rt.recompute != recompute:
             if rt is not None:
                 del self._rt[slot]
-            rt = _Runtime(self, max(batch, 1), train, precision)
+                rt = None             # (the old workspace goes before the new one is allocated)
+            rt = _Runtime(self, max(batch, 1), train, precision, recompute)
             self._rt[slot] = rt
         rt.bind(self)
         # data parallelism with sharded weight passes (parallel.ShardedPassReducer): the training engine works on this rank's rows
@@ -492,6 +503,18 @@ class DiT(nn.Module):
         for slot, rt in getattr(self, "_rt", {}).items():
             if rt.precision == "f16" and rt.train:
                 rt.lib.engine_set_loss_scale(rt.handle, value)
+
+    # Activation recompute of the training engine: "none" (default) | "mlp" | "block" (mapdit_config_t.recompute).  Takes effect with
+    # the next training forward, which rebuilds the training runtime at the new level.
+    @property
+    def activation_recompute(self) -> str:
+        return self.__dict__.get("_activation_recompute", "none")      # (objects pickled before the attribute existed)
+
+    @activation_recompute.setter
+    def activation_recompute(self, value):
+        if value not in L.RECOMPUTE:
+            raise ValueError(f"activation_recompute must be one of {list(L.RECOMPUTE)}, got {value!r}")
+        self._activation_recompute = value
 
     def effective_loss_scale(self) -> float:
         """The loss scale the most recent fp16 backward ran with (the automatic choice resolved); 1.0 before any backward."""
@@ -622,6 +645,7 @@ class DiT(nn.Module):
         new.train(self.training)
         new.gemm_precision, new._loss_scale = self.gemm_precision, self.loss_scale
         new.input_gradients = getattr(self, "input_gradients", False)
+        new.activation_recompute = self.activation_recompute
         return new
 
     def __getstate__(self):

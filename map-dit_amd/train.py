@@ -107,6 +107,10 @@ def build_parser():
                    help="data-parallel gradient exchange: per-stage all-reduce overlapped with backward (default), or "
                         "reduce-scatter + sharded optimiser + all-gather (zero1), or sharded weight passes - forced weight norm, imaging, "
                         "Jacobian, Adam / EMA on 1/world of the rows, 16-bit images all-gathered (zero1w; -bf16: 16-bit gradient exchange)")
+    p.add_argument("--activation-recompute", choices=["none", "mlp", "block"], default="none",
+                   help="keep fewer activations for the backward and regenerate them block by block (bit-identical gradients): mlp = a "
+                        "block's fc1 GEMM is issued again (24 instead of 40 x hidden bytes per token and block), block = the block's whole "
+                        "forward (12); f16 / bf16 precisions")
     for f in MP_FLAGS:
         p.add_argument(f"--use-{f}", dest="use_" + f.replace("-", "_"), action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--use-rotation-modulation", action=argparse.BooleanOptionalAction, default=False,
@@ -126,6 +130,8 @@ def main(argv=None):
                                   + ", ".join("--no-use-" + f for f in BUILT_OFF_FORMS))
     if args.precision == "bf16x3" and any(not getattr(args, "use_" + f.replace("-", "_")) for f in BUILT_OFF_FORMS):
         raise NotImplementedError("the --no-use-* off forms are built for the f16 / bf16 engines, not for --precision bf16x3")
+    if args.activation_recompute != "none" and (args.precision == "bf16x3" or not args.use_no_layernorm):
+        raise NotImplementedError("--activation-recompute is built for the f16 / bf16 engines without the LayerNorm form (--no-use-no-layernorm)")
     if not args.use_no_layernorm and args.use_rotation_modulation:
         raise NotImplementedError("--no-use-no-layernorm (the LayerNorm form) is built for the AdaLN modulation, not with --use-rotation-modulation")
     rank, world, local = parallel.init_from_env()
@@ -166,6 +172,7 @@ def main(argv=None):
     diffusion = create_diffusion(timestep_respacing="")
     model = get_model(args).to(dev).train()
     model.gemm_precision = args.precision
+    model.activation_recompute = args.activation_recompute
     log(f"model parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad):,}")
     if args.ema_snapshot_every is None:
         args.ema_snapshot_every = args.num_steps // 250
