@@ -556,11 +556,60 @@ __global__ __launch_bounds__(256) void prior_bpd_kernel(const float* __restrict_
     }
 }
 
+// One step of the multistep DPM-Solver++ (Lu et al. 2022, Algorithm 2) in data-prediction form: D = the x0 prediction at timestep
+// tau[step] (p_mean_variance's, or xstart_in; clipped on request), sample = c_x x + c_0 D + c_1 hist, hist <- D.  The three
+// coefficients of row `step` of ctab are built on the host (mapdit.h); row 0 is (0, 1, 0): the last step returns the x0 prediction.
+// sample may alias x and hist is read before it is written, each by the thread that owns the element: none of the three is
+// __restrict__.
+__global__ void dpm_step_kernel(const float* __restrict__ mo, const float* x, float* hist, const long* __restrict__ step,
+                                const float* __restrict__ ctab, const long* __restrict__ tau, int K, const float* __restrict__ tab,
+                                int nsteps, int mean_type, int var_type, int clip, const float* __restrict__ xstart_in, float* sample,
+                                float* __restrict__ xstart, long total, int per) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long n = i / per, e = i % per;
+    const long k = MAPDIT_CHECKED_INDEX(diffusion, step[n], K, MAPDIT_DEVERR_TIMESTEP);
+    const long tt = MAPDIT_CHECKED_INDEX(diffusion, tau[k], nsteps, MAPDIT_DEVERR_TIMESTEP);
+    const float cx = ctab[3 * k], c0 = ctab[3 * k + 1], c1 = ctab[3 * k + 2];
+    const float x_t = x[i];
+    float d;
+    if (xstart_in) {
+        d = xstart_in[i];
+    } else {
+        const long ostride = var_type == OBJ_LEARNED_RANGE ? 2 * (long)per : (long)per;
+        const float m = mo[n * ostride + e];
+        d = mean_type == OBJ_START_X ? m : tab[2 * nsteps + tt] * x_t - tab[3 * nsteps + tt] * m;
+    }
+    if (clip) d = fminf(fmaxf(d, -1.f), 1.f);
+    const float prev = hist[i];
+    sample[i] = cx * x_t + c0 * d + c1 * prev;
+    hist[i] = d;
+    if (xstart) xstart[i] = d;
+}
+
 bool obj_types_ok(int mean_type, int var_type) {
     return (mean_type == OBJ_EPSILON || mean_type == OBJ_START_X) && var_type >= OBJ_LEARNED_RANGE && var_type <= OBJ_FIXED_LARGE;
 }
 
 }  // namespace
+
+extern "C" int mapdit_dpm_step(const float* model_out, const float* x, float* hist, const int64_t* step, const float* ctab,
+                               const int64_t* tau, int K, const float* tab, int nsteps, int mean_type, int var_type, int clip_denoised,
+                               const float* xstart_in, float* sample, float* pred_xstart, int N, int per_sample, void* stream) {
+    MD_CHECK(x && hist && step && ctab && tau && tab && sample && N > 0 && per_sample > 0 && nsteps > 0 && K > 0,
+             "dpm_step: null/empty argument");
+    MD_CHECK(obj_types_ok(mean_type, var_type), "dpm_step: bad objective");
+    MD_CHECK(model_out || xstart_in, "dpm_step: this step reads the model output (null)");
+    MD_CHECK(hist != x && hist != sample && hist != xstart_in && sample != xstart_in &&
+                 (!pred_xstart || (pred_xstart != sample && pred_xstart != hist && pred_xstart != x && pred_xstart != xstart_in)),
+             "dpm_step: overlapping arguments (only sample may alias x)");
+    const long total = (long)N * per_sample;
+    hipLaunchKernelGGL(dpm_step_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, model_out, x, hist, (const long*)step,
+                       ctab, (const long*)tau, K, tab, nsteps, mean_type, var_type, clip_denoised, xstart_in, sample, pred_xstart, total,
+                       per_sample);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
 
 extern "C" int mapdit_obj_loss_fwd(const float* model_out, const float* x0, const float* xt, const float* noise, const int64_t* t,
                                    const float* tab, const float* otab, int nsteps, int mean_type, int var_type, int loss_type,

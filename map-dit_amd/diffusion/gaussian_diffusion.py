@@ -21,6 +21,9 @@ probability; under ``SpacedDiffusion`` it sees the timesteps of the base schedul
 ``mapdit_obj_xstart`` when ``denoised_fn`` has to see the raw prediction: at most two diffusion kernels between the model's output
 and the sample, and no torch pointwise op or host synchronisation besides the user's callables.  Without hooks every method runs
 the kernel it ran before.  ``condition_mean`` / ``condition_score`` are public, with the reference's semantics.
+
+Not in the reference: ``dpm_solver_sample_loop`` (+ ``_progressive``), the multistep DPM-Solver++ of Lu et al. 2022 (orders 1 and 2) - the
+schedule and its coefficients are built here in fp64 (``_dpm_schedule``), a step is one ``mapdit_dpm_step`` launch after the model.
 """
 import enum
 import math
@@ -199,6 +202,54 @@ class GaussianDiffusion:
             tab = torch.from_numpy(np.stack(rows)).float().to(device).contiguous()
             self._tab_cache[("obj", device)] = tab
         return tab
+
+    # ---- DPM-Solver++ (Lu et al. 2022): step selection and coefficients, fp64 on the host ------------------------------
+    def _dpm_schedule(self, num_steps=20, order=2, spacing="logsnr", lower_order_final=True):
+        """-> (tau int64 [K], coef float64 [K, 3]): the timesteps tau[0] = 0 < ... < tau[K-1] = n - 1 of this diffusion that the solver
+        visits and, per solver step i (K-1 down to 0), the (c_x, c_0, c_1) of ``sample = c_x x + c_0 D + c_1 D_prev`` (layout and
+        formulas in include/mapdit.h, mapdit_dpm_step).  K <= num_steps: "logsnr" drops the duplicates its rounding produces."""
+        n = self.num_timesteps
+        if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or not 2 <= num_steps <= n:
+            raise ValueError(f"num_steps must be an integer in [2, {n}] (the diffusion's own timesteps); got {num_steps!r}")
+        if isinstance(order, bool) or order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2 (DPM-Solver++ first order / 2M); got {order!r}")
+        num_steps = int(num_steps)
+        alpha, sigma = np.sqrt(self.alphas_cumprod), np.sqrt(1.0 - self.alphas_cumprod)
+        lam = np.log(alpha / sigma)
+        if spacing == "logsnr":
+            targets = np.linspace(lam[0], lam[n - 1], num_steps)
+            tau = np.unique([int(np.argmin(np.abs(lam - v))) for v in targets])       # argmin: the lowest index on a tie
+        elif spacing == "uniform":
+            from .respace import space_timesteps
+            tau = np.array(sorted(space_timesteps(n, str(num_steps))))
+        else:
+            raise ValueError(f'spacing must be "logsnr" or "uniform"; got {spacing!r}')
+        tau = tau.astype(np.int64)
+        K = len(tau)
+        assert K >= 2 and tau[0] == 0 and tau[-1] == n - 1 and (np.diff(tau) > 0).all(), tau
+        coef = np.zeros((K, 3), dtype=np.float64)
+        coef[0] = (0.0, 1.0, 0.0)                                  # the final denoise: the x0 prediction at tau[0]
+        for i in range(1, K):
+            s, t = tau[i], tau[i - 1]
+            h = lam[t] - lam[s]
+            b = -alpha[t] * np.expm1(-h)
+            c0, c1 = b, 0.0
+            if order == 2 and i != K - 1 and not (i == 1 and lower_order_final):
+                r = (lam[s] - lam[tau[i + 1]]) / h
+                c0, c1 = b * (1.0 + 1.0 / (2.0 * r)), -b / (2.0 * r)
+            coef[i] = (sigma[t] / sigma[s], c0, c1)
+        return tau, coef
+
+    def _dpm_tables(self, device, num_steps=20, order=2, spacing="logsnr", lower_order_final=True):
+        """_dpm_schedule on the device, uploaded once per configuration -> (tau int64 [K], ctab fp32 [K][3], tau as a host list)."""
+        key = ("dpm", num_steps, order, spacing, bool(lower_order_final), device)
+        tabs = self._tab_cache.get(key)
+        if tabs is None:
+            tau, coef = self._dpm_schedule(num_steps, order, spacing, lower_order_final)
+            tabs = (torch.from_numpy(tau).to(device).contiguous(), torch.from_numpy(coef).float().to(device).contiguous(),
+                    [int(v) for v in tau])
+            self._tab_cache[key] = tabs
+        return tabs
 
     def _extract(self, name, t, shape):
         """reference _extract_into_tensor (:861-873) with the fp32 row resident on the device (uploaded once per row)."""
@@ -635,3 +686,69 @@ class GaussianDiffusion:
                                     model_kwargs=model_kwargs)
                 yield out
                 img = out["sample"]
+
+    # ---- DPM-Solver++ (not in the reference: a high-order solver of the probability-flow ODE, ~20 model evaluations) --------
+    def _dpm_step(self, model_output, x, hist, step, tabs, clip_denoised, xstart_in=None, sample=None):
+        """mapdit_dpm_step -> (sample, pred_xstart); hist is updated in place.  sample: the tensor to write (may be x itself)."""
+        tau, ctab, _ = tabs
+        mean_type, var_type, _ = self._kinds()
+        mo = None if model_output is None else self._prep(model_output)
+        sample = torch.empty_like(x) if sample is None else sample
+        xstart = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.lib().dpm_step(L.ptr(mo), x.data_ptr(), hist.data_ptr(), step.data_ptr(), ctab.data_ptr(), tau.data_ptr(), tau.shape[0],
+                             self._tables(x.device).data_ptr(), self.num_timesteps, mean_type, var_type, int(bool(clip_denoised)),
+                             L.ptr(xstart_in), sample.data_ptr(), xstart.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
+        return sample, xstart
+
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                               device=None, progress=False, num_steps=20, order=2, spacing="logsnr", lower_order_final=True):
+        """Deterministic sampling with the multistep DPM-Solver++ (Lu et al. 2022; order 2 = "2M", order 1 = the DDIM eta = 0 update):
+        at most ``num_steps`` model evaluations on timesteps of this diffusion chosen by ``spacing`` ("logsnr": nearest to equal steps
+        of the log signal-to-noise ratio, duplicates dropped; "uniform": ``space_timesteps``).  Signature and hooks as
+        ``ddim_sample_loop``; the variance channels of a learned-range model are ignored."""
+        final = None
+        for sample in self.dpm_solver_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                              denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs,
+                                                              device=device, progress=progress, num_steps=num_steps, order=order,
+                                                              spacing=spacing, lower_order_final=lower_order_final):
+            final = sample
+        with torch.cuda.device(final["sample"].device):
+            L.lib().device_error_poll(L.cur_stream())      # out-of-range label / timestep / step index anywhere in the loop
+        return final["sample"]
+
+    def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                           model_kwargs=None, device=None, progress=False, num_steps=20, order=2, spacing="logsnr",
+                                           lower_order_final=True):
+        """Yields {"sample", "pred_xstart"} per solver step.  After the model, an unhooked step is one mapdit_dpm_step launch.
+        denoised_fn sees the raw x0 prediction (mapdit_obj_xstart) and its result is clipped inside the step; cond_fn goes through
+        condition_score (mapdit_obj_step_guided without a sample: x0 moved by the gradient after the clip, not clipped again), and
+        the conditioned x0 is what the solver uses and remembers."""
+        self._supported()
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        tabs = self._dpm_tables(torch.device(device), num_steps, order, spacing, lower_order_final)
+        taus = tabs[2]
+        img = self._prep(noise if noise is not None else torch.randn(*shape, device=device))
+        hist = torch.zeros_like(img)          # c_1 = 0 on the first step, but 0 x NaN of an uninitialised buffer is NaN
+        indices = list(range(len(taus)))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        for i in indices:
+            step = torch.full((shape[0],), i, device=device, dtype=torch.int64)
+            t = torch.full((shape[0],), taus[i], device=device, dtype=torch.int64)
+            with torch.no_grad():
+                model_output = self._model_output(model, img, t, model_kwargs)
+                xin, clip = None, clip_denoised
+                if denoised_fn is not None or cond_fn is not None:
+                    xin, grad = self._hooks(model_output, img, t, denoised_fn, cond_fn, model_kwargs)
+                    if grad is not None:
+                        _, xin, _ = self._guided_step(model_output, img, t, None, clip_denoised, _STEP_DDIM, xstart_in=xin,
+                                                      cond_grad=grad, sample=False)
+                        clip = False
+                sample, xstart = self._dpm_step(model_output, img, hist, step, tabs, clip, xstart_in=xin)
+                out = {"sample": sample, "pred_xstart": xstart}
+                yield out
+                img = sample

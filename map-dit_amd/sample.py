@@ -1,6 +1,7 @@
 """MI355X counterpart of the reference's ``sample.py``: four class-conditional samples with classifier-free guidance
 from the post-hoc EMA weights of a results directory, written as an image grid.  Same flags and defaults
-(reference sample.py:83-96) plus ``--vae-path`` / ``--no-graph`` / ``--precision``.  The VAE decoder is not part of this
+(reference sample.py:83-96) plus ``--vae-path`` / ``--no-graph`` / ``--precision`` and ``--sampler dpm++`` with ``--solver-order`` /
+``--solver-spacing`` (DPM-Solver++ on the full schedule, ``--num-sampling-steps`` model evaluations; default: the ancestral sampler).  The VAE decoder is not part of this
 engine: with ``--use-vae false`` the de-normalised latents are written (PNG grid of the 4 latent channels
 as RGBA + ``<output>.npy``)."""
 from __future__ import annotations
@@ -11,7 +12,6 @@ import numpy as np
 import torch
 
 from . import sampling as S
-from .diffusion import create_diffusion
 from .train import get_model
 
 
@@ -29,6 +29,7 @@ def build_parser():
     p.add_argument("--vae-path", type=str, default=None, help="local copy of stabilityai/sd-vae-ft-mse (no network here)")
     p.add_argument("--no-graph", action="store_true", help="eager p_sample_loop instead of the captured hipGraph")
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
+    S.add_sampler_flags(p)
     return p
 
 
@@ -51,8 +52,8 @@ def main(argv=None):
     y = torch.tensor([args.class_label] * n, device=device)
     z = torch.cat([z, z], dim=0)                                          # CFG batch: conditional | null class
     y = torch.cat([y, torch.tensor([train_args["num_classes"]] * n, device=device)], dim=0)
-    diffusion = create_diffusion(str(args.num_sampling_steps))
-    samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=not args.no_graph, progress=True)
+    diffusion, solver = S.make_diffusion(args)
+    samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=not args.no_graph, progress=True, **solver)
     samples, _ = samples.chunk(2, dim=0)
     samples = S.denormalize(samples, train_args)
     if vae is not None:

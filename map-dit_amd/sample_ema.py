@@ -1,5 +1,5 @@
 """MI355X counterpart of the reference's ``sample_ema.py``: the same 8 noise draws sampled under post-hoc EMA profiles of
-relative width 0.0075 / 0.01 / 0.05 / 0.1 / 0.15, one column per width (reference sample_ema.py:24-80; flags :83-92)."""
+relative width 0.0075 / 0.01 / 0.05 / 0.1 / 0.15, one column per width (reference sample_ema.py:24-80; flags :83-92), with the ancestral sampler or ``--sampler dpm++``."""
 from __future__ import annotations
 
 import argparse
@@ -9,7 +9,6 @@ import numpy as np
 import torch
 
 from . import sampling as S
-from .diffusion import create_diffusion
 from .src.ema import calculate_posthoc_ema
 from .train import get_model
 
@@ -28,6 +27,7 @@ def build_parser():
     p.add_argument("--vae-path", type=str, default=None, help="local copy of stabilityai/sd-vae-ft-mse (no network here)")
     p.add_argument("--no-graph", action="store_true", help="eager p_sample_loop instead of the captured hipGraph")
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
+    S.add_sampler_flags(p)
     return p
 
 
@@ -39,7 +39,7 @@ def main(argv=None):
     model = get_model(train_args).to(device).eval()
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device) if args.use_vae else None
-    diffusion = create_diffusion(str(args.num_sampling_steps))
+    diffusion, solver = S.make_diffusion(args)
     n = 8
     shape = (2 * n, train_args["in_channels"], train_args["input_size"], train_args["input_size"])
     if not 0 <= args.class_label < int(train_args["num_classes"]):       # the reference fails inside F.embedding (IndexError)
@@ -55,10 +55,10 @@ def main(argv=None):
         z = torch.randn(n, *shape[1:], device=device)
         z = torch.cat([z, z], 0)
         if args.no_graph:
-            samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=False, progress=True)
+            samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=False, progress=True, **solver)
         else:
             if graphed is None:              # weights are re-imaged per replay set: the graph reads the cached bf16 images
-                graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale)
+                graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale, **solver)
             else:
                 graphed.refresh_weights()
             samples = graphed.sample(z)

@@ -1,7 +1,7 @@
 """MI355X counterpart of the reference's ``sample_fid.py``: ``--num-samples`` images in batches of ``--batch-size`` with
 random labels (classifier-free guidance when ``--cfg-scale`` > 1), stored as one uint8 NHWC array ``arr_0`` in
 ``<result-dir>/fid_samples/<output-file>`` (reference sample_fid.py:48-97; flags :100-114).  One hipGraph is captured for
-the batch shape and replayed for every batch.  Without a VAE (``--use-vae false``) the array holds the de-normalised
+the batch shape and replayed for every batch (``--sampler dpm++``: DPM-Solver++ with ``--num-sampling-steps`` model evaluations).  Without a VAE (``--use-vae false``) the array holds the de-normalised
 latents clamped to [-1, 1] and quantised the same way."""
 from __future__ import annotations
 
@@ -13,7 +13,6 @@ import numpy as np
 import torch
 
 from . import sampling as S
-from .diffusion import create_diffusion
 from .train import get_model
 
 
@@ -35,6 +34,7 @@ def build_parser():
     p.add_argument("--vae-path", type=str, default=None, help="local copy of stabilityai/sd-vae-ft-mse (no network here)")
     p.add_argument("--no-graph", action="store_true", help="eager p_sample_loop instead of the captured hipGraph")
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
+    S.add_sampler_flags(p)
     return p
 
 
@@ -54,7 +54,7 @@ def main(argv=None):
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=False)
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device) if args.use_vae else None
-    diffusion = create_diffusion(str(args.num_sampling_steps))
+    diffusion, solver = S.make_diffusion(args)
 
     n = args.batch_size
     use_cfg = args.cfg_scale > 1.0
@@ -68,10 +68,10 @@ def main(argv=None):
             z = torch.cat([z, z], dim=0)
             y = torch.cat([y, torch.tensor([args.num_classes] * n, device=device)], dim=0)
         if args.no_graph:
-            samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale if use_cfg else None, use_graph=False)
+            samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale if use_cfg else None, use_graph=False, **solver)
         else:
             if graphed is None:
-                graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale if use_cfg else None)
+                graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale if use_cfg else None, **solver)
             graphed.y.copy_(y)
             samples = graphed.sample(z)
         if use_cfg:

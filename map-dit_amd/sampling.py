@@ -1,10 +1,14 @@
-"""hipGraph-captured ancestral sampling (BASELINE config 5; reference sample_fid.py:48-76 + gaussian_diffusion.py:464-511).
+"""hipGraph-captured sampling (BASELINE config 5; reference sample_fid.py:48-76 + gaussian_diffusion.py:464-511).
 
 One denoise step of ``p_sample_loop`` — timestep map lookup, the classifier-free-guidance DiT forward, the fused
 p_mean_variance / p_sample kernel, the N(0,1) draw and the on-device ``t -= 1`` — is captured once into a hipGraph
 (torch.cuda.CUDAGraph is hipGraph on ROCm) and replayed ``num_timesteps`` times.  The reference's per-step host work
 (``th.tensor([i]*B)``, ~8 numpy table uploads, the timestep_map upload: SURVEY §3.2) disappears: schedule tables,
 the map and the step counter live on the device, and a replay is a single graph launch.
+
+``sampler="dpm++"`` captures one step of ``dpm_solver_sample_loop`` instead (the multistep DPM-Solver++, not in the reference):
+the lookup of the solver's timestep, the DiT forward, ``mapdit_dpm_step`` and ``step -= 1``, replayed once per solver step.  The
+previous x0 prediction, the step index and the solver's tables live on the device; no randomness is drawn.
 """
 from __future__ import annotations
 
@@ -17,11 +21,17 @@ class GraphedSampler:
     """Captures ``x_{t-1} = p_sample(model_fn(x_t, map[t], **kw), x_t, t)`` for a fixed batch shape.
 
     model: the DiT module (eval mode); diffusion: a SpacedDiffusion; cfg_scale: None -> model.forward, else
-    model.forward_with_cfg (y must then hold [labels, null labels], as sample_fid.py:56-66 builds it)."""
+    model.forward_with_cfg (y must then hold [labels, null labels], as sample_fid.py:56-66 builds it).
 
-    def __init__(self, model, diffusion, shape, y, cfg_scale=None, clip_denoised=False):
+    sampler: "ancestral" (p_sample, one replay per timestep of the diffusion) or "dpm++" (DPM-Solver++ with num_steps / order / spacing /
+    lower_order_final as ``diffusion.dpm_solver_sample_loop`` takes them; one replay per solver step, ``self.num_replays`` of them)."""
+
+    def __init__(self, model, diffusion, shape, y, cfg_scale=None, clip_denoised=False, sampler="ancestral", num_steps=20, order=2,
+                 spacing="logsnr", lower_order_final=True):
         assert not model.training, "sampling runs the model in eval mode"
         diffusion._supported()
+        if sampler not in ("ancestral", "dpm++"):
+            raise ValueError(f'sampler must be "ancestral" or "dpm++"; got {sampler!r}')
         if diffusion.model_var_type.name != "LEARNED_RANGE":
             raise NotImplementedError(f"GraphedSampler drives a DiT, whose output carries learned-range variance channels; a "
                                       f"{diffusion.model_var_type.name} diffusion needs a model with C output channels "
@@ -30,8 +40,14 @@ class GraphedSampler:
         dev = next(model.parameters()).device
         self.dev = dev
         self.img = torch.zeros(*shape, device=dev)
+        self.dpm = None
+        if sampler == "dpm++":
+            self.dpm = diffusion._dpm_tables(dev, num_steps, order, spacing, lower_order_final)
+            self.hist = torch.zeros_like(self.img)
+        self.num_replays = diffusion.num_timesteps if self.dpm is None else len(self.dpm[2])
         # the warm-up and the capture below each run one real step (t -> t - 1): start high enough to stay inside the schedule
-        self.t = torch.full((shape[0],), max(diffusion.num_timesteps - 1, 0), device=dev, dtype=torch.int64)
+        # (t is the index into the diffusion's schedule for "ancestral", the solver step index for "dpm++")
+        self.t = torch.full((shape[0],), max(self.num_replays - 1, 0), device=dev, dtype=torch.int64)
         self.y = y.to(dev).clone()
         self.cfg_scale, self.clip = cfg_scale, bool(clip_denoised)
         self.tab = diffusion._tables(dev)
@@ -45,17 +61,19 @@ class GraphedSampler:
             s.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(s):
                 for _ in range(2):
-                    self.t.fill_(max(diffusion.num_timesteps - 1, 0))
+                    self.t.fill_(max(self.num_replays - 1, 0))
                     self._step()
             torch.cuda.current_stream(dev).wait_stream(s)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
-            self.t.fill_(max(diffusion.num_timesteps - 1, 0))
+            self.t.fill_(max(self.num_replays - 1, 0))
             with torch.cuda.graph(self.graph):
                 self._step()
 
     def _step(self):
         d = self.diffusion
+        if self.dpm is not None:
+            return self._dpm_step()
         mapped = self.tmap[self.t.clamp_min(0)]
         if self.cfg_scale is None:
             out = self.model.forward(self.img, mapped, self.y)
@@ -75,6 +93,21 @@ class GraphedSampler:
         self.img.copy_(nxt)
         self.t.sub_(1)
 
+    def _dpm_step(self):
+        d = self.diffusion
+        tau, ctab, taus = self.dpm
+        mapped = self.tmap[tau[self.t.clamp(0, len(taus) - 1)]]
+        if self.cfg_scale is None:
+            out = self.model.forward(self.img, mapped, self.y)
+        else:
+            out = self.model.forward_with_cfg(self.img, mapped, self.y, self.cfg_scale)
+        mean_type, var_type, _ = d._kinds()
+        # in place: the kernel's sample may alias x
+        L.lib().dpm_step(out.data_ptr(), self.img.data_ptr(), self.hist.data_ptr(), self.t.data_ptr(), ctab.data_ptr(), tau.data_ptr(),
+                         len(taus), self.tab.data_ptr(), d.num_timesteps, mean_type, var_type, int(self.clip), None, self.img.data_ptr(),
+                         None, self.img.shape[0], self.img[0].numel(), L.cur_stream())
+        self.t.sub_(1)
+
     def refresh_weights(self):
         """After the model's parameters were replaced in place (``load_state_dict``): rebuild the cached weight images
         the captured graph reads (the eager forward does this lazily; a graph replay runs no Python)."""
@@ -86,7 +119,9 @@ class GraphedSampler:
     @torch.no_grad()
     def sample(self, noise=None, steps=None):
         """Run the reverse chain from ``noise`` (or fresh N(0,1)); ``steps`` bounds the prefix (default: all)."""
-        n = self.diffusion.num_timesteps
+        n = self.num_replays
+        if self.dpm is not None:
+            self.hist.zero_()
         steps = n if steps is None else steps
         if noise is None:
             self.img.normal_()
@@ -113,6 +148,22 @@ def p_sample_loop_graphed(diffusion, model, shape, noise=None, clip_denoised=Fal
     cfg = kw.pop("cfg_scale", None)
     assert not kw, f"unsupported model_kwargs: {sorted(kw)}"
     return GraphedSampler(model, diffusion, shape, y, cfg, clip_denoised).sample(noise)
+
+
+def dpm_solver_sample_loop_graphed(diffusion, model, shape, noise=None, clip_denoised=False, model_kwargs=None, device=None, *,
+                                   denoised_fn=None, cond_fn=None, num_steps=20, order=2, spacing="logsnr", lower_order_final=True):
+    """Drop-in for ``diffusion.dpm_solver_sample_loop(model.forward[_with_cfg], shape, noise, clip_denoised, model_kwargs=...,
+    num_steps=..., order=..., spacing=...)`` with the solver step replayed from a hipGraph.  ``model`` is the DiT module itself; the
+    hooks are refused as ``p_sample_loop_graphed`` refuses them and run through ``diffusion.dpm_solver_sample_loop``."""
+    if denoised_fn is not None or cond_fn is not None:
+        raise NotImplementedError("denoised_fn / cond_fn are not built for the captured sampler (a user callable cannot run inside "
+                                  "a hipGraph): use diffusion.dpm_solver_sample_loop")
+    kw = dict(model_kwargs or {})
+    y = kw.pop("y")
+    cfg = kw.pop("cfg_scale", None)
+    assert not kw, f"unsupported model_kwargs: {sorted(kw)}"
+    return GraphedSampler(model, diffusion, shape, y, cfg, clip_denoised, sampler="dpm++", num_steps=num_steps, order=order,
+                          spacing=spacing, lower_order_final=lower_order_final).sample(noise)
 
 
 # ---- shared pieces of the sampler CLIs (reference sample.py / sample_fid.py / sample_ema.py) ---------------------------
@@ -167,13 +218,43 @@ def load_vae(vae_path: str | None, device):
     return AutoencoderKL.from_pretrained(vae_path or "stabilityai/sd-vae-ft-mse").to(device)
 
 
-def run_sampler(model, diffusion, z, y, cfg_scale, use_graph: bool = True, progress: bool = False):
+SAMPLERS = ("ancestral", "dpm++")
+
+
+def add_sampler_flags(parser):
+    """The sampler choice shared by the three CLIs.  Under ``dpm++`` ``--num-sampling-steps`` is the solver's num_steps and the
+    diffusion is the full schedule, which the solver subsamples itself (``make_diffusion``)."""
+    parser.add_argument("--sampler", choices=SAMPLERS, default="ancestral",
+                        help="ancestral: the reference's p_sample_loop; dpm++: DPM-Solver++ (deterministic, ~20 steps)")
+    parser.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="dpm++ only: 1 (DDIM) or 2 (2M)")
+    parser.add_argument("--solver-spacing", choices=["logsnr", "uniform"], default="logsnr", help="dpm++ only: how its steps are chosen")
+    return parser
+
+
+def make_diffusion(args):
+    """create_diffusion for a CLI's arguments and the GraphedSampler / run_sampler keywords that select its sampler."""
+    from .diffusion import create_diffusion
+    if args.sampler == "dpm++":
+        return create_diffusion(""), dict(sampler="dpm++", num_steps=args.num_sampling_steps, order=args.solver_order,
+                                          spacing=args.solver_spacing)
+    return create_diffusion(str(args.num_sampling_steps)), {}
+
+
+def run_sampler(model, diffusion, z, y, cfg_scale, use_graph: bool = True, progress: bool = False, sampler: str = "ancestral",
+                num_steps: int = 20, order: int = 2, spacing: str = "logsnr"):
     """``diffusion.p_sample_loop(model.forward[_with_cfg], z.shape, z, clip_denoised=False, ...)`` - through the captured
-    hipGraph (default) or the eager loop."""
+    hipGraph (default) or the eager loop; with ``sampler="dpm++"``, ``diffusion.dpm_solver_sample_loop`` (num_steps, order,
+    spacing) the same two ways."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}; got {sampler!r}")
+    solver = dict(num_steps=num_steps, order=order, spacing=spacing) if sampler == "dpm++" else {}
     if use_graph:
-        return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, clip_denoised=False).sample(z)
+        return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, clip_denoised=False, sampler=sampler, **solver).sample(z)
     kw = dict(y=y) if cfg_scale is None else dict(y=y, cfg_scale=cfg_scale)
     fn = model.forward if cfg_scale is None else model.forward_with_cfg
+    if sampler == "dpm++":
+        return diffusion.dpm_solver_sample_loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=progress, device=z.device,
+                                                **solver)
     return diffusion.p_sample_loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=progress, device=z.device)
 
 

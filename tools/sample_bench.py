@@ -3,6 +3,10 @@
 
     python tools/sample_bench.py --model DiT-XL/2 --n 128 --steps 50
 Prints one JSON line: denoise steps/s, ms per step, latent images/s for a full 250-step chain.
+
+    python tools/sample_bench.py --model DiT-XL/2 --n 128 --chains 5 --solver-steps 20
+times whole captured chains instead: wall time per batch of the 250-step ancestral sampler and of DPM-Solver++ at --solver-steps
+(median of --chains runs after one warm-up run each), and their ratio.
 """
 import argparse
 import json
@@ -19,6 +23,27 @@ from mapdit_amd.sampling import GraphedSampler  # noqa: E402
 from mapdit_amd.src.models import DIT_MODELS  # noqa: E402
 
 
+def whole_chains(args, model, z, y):
+    import statistics
+    res = {}
+    for name, d, solver in (("ancestral", create_diffusion("250"), {}),
+                            ("dpm++", create_diffusion(""), dict(sampler="dpm++", num_steps=args.solver_steps))):
+        s = GraphedSampler(model, d, z.shape, y, cfg_scale=args.cfg_scale, **solver)
+        times = []
+        for k in range(args.chains + 1):          # the first run is the warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s.sample(z)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        res[name] = {"replays": s.num_replays, "s_per_batch_median": statistics.median(times[1:]), "s_per_batch": times[1:]}
+        del s
+    a, b = res["ancestral"]["s_per_batch_median"], res["dpm++"]["s_per_batch_median"]
+    print(json.dumps({"metric": f"whole captured chain, {args.model}, cfg {args.cfg_scale}, batch 2x{args.n}", "dtype": args.precision,
+                      "ancestral": res["ancestral"], "dpm++": res["dpm++"], "dpm_over_ancestral": b / a,
+                      "replay_ratio": res["dpm++"]["replays"] / res["ancestral"]["replays"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="DiT-XL/2")
@@ -27,6 +52,8 @@ def main():
     ap.add_argument("--input-size", type=int, default=32, help="side of the latents (64: 1,024 tokens per sample at patch 2)")
     ap.add_argument("--cfg-scale", type=float, default=1.5)
     ap.add_argument("--precision", choices=["bf16", "f16"], default="bf16")
+    ap.add_argument("--chains", type=int, default=0, help="> 0: time this many whole chains per sampler instead of single steps")
+    ap.add_argument("--solver-steps", type=int, default=20, help="--chains: num_steps of the dpm++ sampler")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -38,6 +65,8 @@ def main():
     z = torch.cat([z, z], 0)
     y = torch.cat([torch.randint(0, 1000, (n,), device=dev), torch.full((n,), 1000, device=dev)])
     kw = dict(y=y, cfg_scale=args.cfg_scale)
+    if args.chains > 0:
+        return whole_chains(args, model, z, y)
 
     # eager reference-API loop (p_sample per step)
     img = z
