@@ -455,9 +455,20 @@ __global__ void mpsilu_f32_to_bf16_kernel(const float* __restrict__ x, bf16_t* _
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = cvt16(silu_f(x[i]) * (1.f / MP_SILU_DIV));
 }
+// alpha * x as a 16-bit operand.  In the fp16 build hipcc contracts the product and the conversion into v_fma_mixlo_f16(alpha, x, +0):
+// one rounding (kept), but an exactly zero product comes out as +0 whatever its sign - the product's sign is put back, as v_cvt keeps
+// it in the bf16 build (and as the host's cast does).  The one rounding stays: for an alpha that is not a power of two the fp16 build
+// therefore still differs, in rare last bits, from a host cast of the fp32 product (two roundings); for alpha = 2^k the two agree.
+__device__ __forceinline__ bf16_t scaled_cvt16(float alpha, float x) {
+#if MAPDIT_DT == 1
+    return (bf16_t)((cvt16(alpha * x) & 0x7fffu) | (((__float_as_uint(alpha) ^ __float_as_uint(x)) >> 16) & 0x8000u));
+#else
+    return cvt16(alpha * x);
+#endif
+}
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, long n, float alpha) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = cvt16(alpha * x[i]);
+    if (i < n) out[i] = scaled_cvt16(alpha, x[i]);
 }
 
 __global__ void f32_to_bf16_2d_kernel(const float* __restrict__ x, int ldx, bf16_t* __restrict__ out, int ldo, int rows, int cols,
@@ -465,7 +476,7 @@ __global__ void f32_to_bf16_2d_kernel(const float* __restrict__ x, int ldx, bf16
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)rows * cols) return;
     const int r = (int)(i / cols), c = (int)(i % cols);
-    out[(size_t)r * ldo + c] = cvt16(alpha * x[(size_t)r * ldx + c]);
+    out[(size_t)r * ldo + c] = scaled_cvt16(alpha, x[(size_t)r * ldx + c]);
 }
 // out[i] = alpha * x[i]
 __global__ void scale_copy_kernel(float* __restrict__ out, const float* __restrict__ x, long n, float alpha) {
