@@ -130,6 +130,12 @@ int mapdit_gemm_tile_size_k(int M, int N, int K, int split_k_launch);
  * band width of the tile order (0 = derived from K).  The environment (MAPDIT_GEMM_TILE / _PHASES / _BAND) is read once, at the
  * first launch; this overrides it afterwards. */
 void mapdit_gemm_tuning(int tile, int phases, long band);
+/* How a launch stages its operand tiles (host logic, no GPU call).  mapdit_gemm_dma_fast: 1 if a launch of this shape on tiles of `tile`
+ * rows (256: 256 x 256, 128: 128 x 128, 64: 64 x 128) issues its LDS-DMA from a scalar base and 32-bit lane offsets -
+ * every tile inside the result, K a multiple of 64, both operands within mapdit_gemm_dma_extent_ok; 0: per-piece 64-bit lane addresses
+ * (edge tiles, K tails).  mapdit_gemm_dma_extent_ok: rows x ld x 2 bytes of an operand fit an unsigned 32-bit byte offset. */
+int mapdit_gemm_dma_fast(int layout, int M, int N, int K, int lda, int ldb, int tile);
+int mapdit_gemm_dma_extent_ok(long rows, long ld);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Weight normalisation of MPLinear / MPLinearChunk / MPEmbedding (src/utils.py:19-34, mp_linear.py:38-44,66-74,

@@ -646,8 +646,64 @@ struct EpiHeadsRaw {
     }
 };
 
+// ---- staging of interior tiles: LDS-DMA from a scalar base and 32-bit lane offsets --------------------------------------------------
+// stage_half() forms a 64-bit lane address per piece (row, swizzle, clamp, 64-bit multiply by ld): in the K loops, whose register file is
+// full, hipcc hoists none of it.  Of that address only one offset per operand and piece j depends on the lane, and nothing but a uniform
+// advance on the K-tile.  For tiles without clamp and K tail (the launcher decides: mapdit_gemm_dma_fast) the pieces are issued as
+//   global_load_lds_dwordx4 v_off, s[base:base+1]                   (m0 = the wave's LDS destination)
+// with a per-tile context: base = operand + tile origin + the wave's rows + kbeg (SGPRs, advanced by scalar adds), v_off = the lane's
+// row and swizzled 16-byte chunk (a VGPR per operand and piece j).  Same addresses, same pieces in the same order, same LDS images as stage_half.
+// Inline asm: hipcc does not select the scalar-base form from __builtin_amdgcn_global_load_lds (it keeps a 64-bit lane pointer per
+// piece and advances each with VALU adds).  An asm DMA is not in hipcc's vmcnt bookkeeping: every wait for staged data is explicit.
+//   * m0 is set in the statement that uses it and restored behind it; one wait state between an m0 write and the DMA reading it.
+//   * s_nop 4 in front of the first piece: a base that was formed by v_readfirstlane needs 5 wait states before a VMEM reads it.
+//   * no instruction offset: the hardware adds it to the LDS destination as well as to the source.  Every uniform step is in the base.
+__device__ __forceinline__ unsigned lds_addr(const char* q) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)q; }
+
+#define DMA_PIECE_FIRST(V, B) "s_mov_b32 m0, %[dst]\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %[" V "], %[" B "]\n\t"
+#define DMA_PIECE(OFF, V, B) "s_add_u32 m0, %[dst], " OFF "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[" V "], %[" B "]\n\t"
+
+// The operand tile of the 128^2 and 64-row kernels (stage_tile): four pieces per wave, 8 rows / 4 k-rows apart.  K-major: pieces 2 and 3
+// lie in k-rows with bit 3 set, whose swizzle key differs (kswz): they take a second lane offset.
+template <int KIND> struct DmaCtx128 {
+    const char* pos;    // piece j = 0 of the next K-tile to stage
+    unsigned voff, voff2, dj, dk;
+    __device__ __forceinline__ void begin(const bf16_t* G, int ld, int idx0, int kbeg, int wave, int lane) {
+        const unsigned pitch = (unsigned)ld * 2u;
+        unsigned v0, v2;
+        if (KIND == OP_ROW) {
+            pos = (const char*)G + ((size_t)(idx0 + wave * 32) * ld + kbeg) * 2;
+            v0 = v2 = (unsigned)(lane >> 3) * pitch + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);
+            dj = 8u * pitch; dk = BKT * 2;
+        } else {
+            pos = (const char*)G + ((size_t)(kbeg + wave * 16) * ld + idx0) * 2;
+            v0 = (unsigned)(lane >> 4) * pitch + (unsigned)(((lane & 15) ^ ((lane >> 4) << 1)) << 4);
+            v2 = (unsigned)(lane >> 4) * pitch + (unsigned)(((lane & 15) ^ (((lane >> 4) | 4) << 1)) << 4);
+            dj = 4u * pitch; dk = BKT * pitch;
+        }
+        asm volatile("" : "+v"(v0), "+v"(v2));
+        voff = v0; voff2 = v2;
+    }
+    // stage the K-tile at pos into `tile` (this wave's 4 KiB of it) and move on to the next
+    __device__ __forceinline__ void stage(char* tile, int wave) {
+        const char *b0 = pos, *b1 = pos + dj, *b2 = pos + 2 * (size_t)dj, *b3 = pos + 3 * (size_t)dj;
+        unsigned keep;
+        asm volatile("s_mov_b32 %[keep], m0\n\t"
+                     DMA_PIECE_FIRST("v0", "b0")
+                     DMA_PIECE("0x400", "v0", "b1")
+                     DMA_PIECE("0x800", "v2", "b2")
+                     DMA_PIECE("0xc00", "v2", "b3")
+                     "s_mov_b32 m0, %[keep]"
+                     : [keep] "=&s"(keep)
+                     : [v0] "v"(voff), [v2] "v"(voff2), [dst] "s"(lds_addr(tile + wave * 4096)), [b0] "s"(b0), [b1] "s"(b1), [b2] "s"(b2),
+                       [b3] "s"(b3)
+                     : "memory", "scc");
+        pos += dk;
+    }
+};
+
 // ---- the MFMA kernel -------------------------------------------------------------------------------------
-template <int AK, int BK, class Epi, bool KTAIL = false>
+template <int AK, int BK, class Epi, bool KTAIL = false, bool FAST = false>
 __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmP p, Epi epi) {
     __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -671,16 +727,29 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmP p, Epi epi) {
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int nk = kbase + (z < krem ? 1 : 0);
-    stage_tile<AK, KTAIL>(p.A, p.lda, m0, p.M, kbeg, p.K, smem, wave, lane);
-    stage_tile<BK, KTAIL>(p.B, p.ldb, n0, p.N, kbeg, p.K, smem + TILE_BYTES, wave, lane);
-    for (int t = 0; t < nk; ++t) {
-        __syncthreads();   // tile t has landed (vmcnt(0) + barrier); everyone is done with the other buffer
-        char* cur = smem + (t & 1) * BUF_BYTES;
-        if (t + 1 < nk) {
-            char* nxt = smem + ((t + 1) & 1) * BUF_BYTES;
-            stage_tile<AK, KTAIL>(p.A, p.lda, m0, p.M, kbeg + (t + 1) * BKT, p.K, nxt, wave, lane);
-            stage_tile<BK, KTAIL>(p.B, p.ldb, n0, p.N, kbeg + (t + 1) * BKT, p.K, nxt + TILE_BYTES, wave, lane);
+    DmaCtx128<AK> ca;
+    DmaCtx128<BK> cb;
+    if constexpr (FAST) {
+        ca.begin(p.A, p.lda, m0, kbeg, wave, lane);
+        cb.begin(p.B, p.ldb, n0, kbeg, wave, lane);
+    }
+    auto stage = [&](int t, char* buf) {                   // K-tile t of the slab; called for t = 0, 1, 2, ... in turn
+        if constexpr (FAST) {
+            ca.stage(buf, wave);
+            cb.stage(buf + TILE_BYTES, wave);
+        } else {
+            stage_tile<AK, KTAIL>(p.A, p.lda, m0, p.M, kbeg + t * BKT, p.K, buf, wave, lane);
+            stage_tile<BK, KTAIL>(p.B, p.ldb, n0, p.N, kbeg + t * BKT, p.K, buf + TILE_BYTES, wave, lane);
         }
+    };
+    stage(0, smem);
+    for (int t = 0; t < nk; ++t) {
+        // tile t has landed (vmcnt(0) + barrier); everyone is done with the other buffer.  hipcc puts the wait in front of the barrier
+        // itself for the builtin DMA; an asm DMA it does not count
+        if constexpr (FAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        char* cur = smem + (t & 1) * BUF_BYTES;
+        if (t + 1 < nk) stage(t + 1, smem + ((t + 1) & 1) * BUF_BYTES);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8_t fa[4], fb[4];
@@ -731,7 +800,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmP p, Epi epi) {
 // twice the workgroups; the four waves sit side by side (64 rows x 32 columns each), the A tile is 64 rows (staged by waves 0 and 1), the B
 // tile the same 128 columns.  Every output element is accumulated by the same MFMA steps in the same K order as above: the same bits.
 // A row-major only (NT / NN: what the strips are), K a multiple of 64.
-template <int BK, class Epi>
+template <int BK, class Epi, bool FAST = false>
 __global__ __launch_bounds__(256, 2) void gemm_mfma64_kernel(GemmP p, Epi epi) {
     __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -746,16 +815,27 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma64_kernel(GemmP p, Epi epi) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    if (wave < 2) stage_tile<OP_ROW, false>(p.A, p.lda, m0, p.M, 0, p.K, smem, wave, lane);
-    stage_tile<BK, false>(p.B, p.ldb, n0, p.N, 0, p.K, smem + TILE_BYTES, wave, lane);
+    DmaCtx128<OP_ROW> ca;
+    DmaCtx128<BK> cb;
+    if constexpr (FAST) {
+        ca.begin(p.A, p.lda, m0, 0, wave, lane);
+        cb.begin(p.B, p.ldb, n0, 0, wave, lane);
+    }
+    auto stage = [&](int t, char* buf) {                   // K-tile t; called for t = 0, 1, 2, ... in turn
+        if constexpr (FAST) {
+            if (wave < 2) ca.stage(buf, wave);
+            cb.stage(buf + TILE_BYTES, wave);
+        } else {
+            if (wave < 2) stage_tile<OP_ROW, false>(p.A, p.lda, m0, p.M, t * BKT, p.K, buf, wave, lane);
+            stage_tile<BK, false>(p.B, p.ldb, n0, p.N, t * BKT, p.K, buf + TILE_BYTES, wave, lane);
+        }
+    };
+    stage(0, smem);
     for (int t = 0; t < nk; ++t) {
+        if constexpr (FAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         char* cur = smem + (t & 1) * BUF_BYTES;
-        if (t + 1 < nk) {
-            char* nxt = smem + ((t + 1) & 1) * BUF_BYTES;
-            if (wave < 2) stage_tile<OP_ROW, false>(p.A, p.lda, m0, p.M, (t + 1) * BKT, p.K, nxt, wave, lane);
-            stage_tile<BK, false>(p.B, p.ldb, n0, p.N, (t + 1) * BKT, p.K, nxt + TILE_BYTES, wave, lane);
-        }
+        if (t + 1 < nk) stage(t + 1, smem + ((t + 1) & 1) * BUF_BYTES);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8_t fa[4], fb[2];
@@ -916,6 +996,116 @@ __device__ __forceinline__ void stage_half(const bf16_t* __restrict__ G, int ld,
     }
 }
 
+// ---- the same for the half-tile slots of the 256^2 kernels ("staging of interior tiles" above) ----------------------------------------
+// KIND as above; SIDE 0 / 1 = the M / N side of the 256^2 tile (half_map).
+template <int KIND, int SIDE> struct DmaCtx {
+    static constexpr int HALF = SIDE == 0 ? 64 : 32;              // rows (row-major) / columns (K-major) between half 0 and half 1
+    const char* base;   // piece (half 0, j = 0) of the K-tile at kbeg
+    unsigned voff;      // this lane's byte offset in piece j = 0 ...
+    unsigned voff1;     // ... and in piece j = 1, 8 rows / 4 k-rows further: a second lane offset instead of a second scalar base per piece
+                        // (the fast form frees ~20 VGPRs of address temporaries; scalar registers are what RESID / RMB run out of)
+    unsigned dh;        // half 1: HALF rows (row-major) / columns (K-major) further
+    unsigned dk;        // next K-tile
+    __device__ __forceinline__ void begin(const bf16_t* G, int ld, int idx0, int kbeg, int wave, int lane) {
+        const unsigned pitch = (unsigned)ld * 2u;
+        unsigned vo, dj;
+        if (KIND == OP_ROW) {
+            const int wrow = SIDE == 0 ? (wave >> 2) * 128 + (wave & 3) * 16 : (wave >> 1) * 64 + (wave & 1) * 16;
+            base = (const char*)G + ((size_t)(idx0 + wrow) * ld + kbeg) * 2;
+            vo = (unsigned)(lane >> 3) * pitch + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);
+            dj = 8u * pitch; dh = HALF * pitch; dk = BKT * 2;
+        } else {
+            // k-row = 8 wave + 4 j + (lane >> 4): kswz() of it is (lane >> 4) | (wave & 1) << 2, the same for both pieces
+            const int c = (lane & 15) ^ (((lane >> 4) | ((wave & 1) << 2)) << 1);
+            base = (const char*)G + ((size_t)(kbeg + wave * 8) * ld + idx0) * 2;
+            vo = (unsigned)(lane >> 4) * pitch + (unsigned)half_map<SIDE>(c * 8, 0) * 2u;
+            dj = 4u * pitch; dh = HALF * 2; dk = BKT * pitch;
+        }
+        unsigned vo1 = vo + dj;
+        asm volatile("" : "+v"(vo), "+v"(vo1));                   // kept in their registers: not re-derived from the lane id per piece
+        voff = vo; voff1 = vo1;
+    }
+    // scalar base of half h of the K-tile `rel` tiles after the one at `pos`
+    __device__ __forceinline__ const char* at(const char* pos, int rel, int h) const {
+        return pos + (size_t)rel * dk + (size_t)h * dh;
+    }
+};
+
+// One half-tile slot, this wave's two 1-KiB pieces; dst = LDS address of the first (slot + wave * 2048)
+__device__ __forceinline__ void dma_half(unsigned v0, unsigned v1, unsigned dst, const char* b) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %[keep], m0\n\t"
+                 DMA_PIECE_FIRST("v0", "b")
+                 DMA_PIECE("0x400", "v1", "b")
+                 "s_mov_b32 m0, %[keep]"
+                 : [keep] "=&s"(keep)
+                 : [v0] "v"(v0), [v1] "v"(v1), [dst] "s"(dst), [b] "s"(b)
+                 : "memory", "scc");
+}
+// Slots A0, B0, B1 of one K-tile buffer (the DMA group of phase B), in that order; dst = LDS address of the wave's first A0 piece
+__device__ __forceinline__ void dma_a0b0b1(unsigned va0, unsigned va1, unsigned vb0, unsigned vb1, unsigned dst, const char* a,
+                                           const char* b0, const char* b1) {
+    static_assert(OFF_A0 == 0 && OFF_B0 == 0x8000 && OFF_B1 == 0xc000, "slot offsets are spelled out in the asm below");
+    unsigned keep;
+    asm volatile("s_mov_b32 %[keep], m0\n\t"
+                 DMA_PIECE_FIRST("va0", "a")
+                 DMA_PIECE("0x400", "va1", "a")
+                 DMA_PIECE("0x8000", "vb0", "b0")
+                 DMA_PIECE("0x8400", "vb1", "b0")
+                 DMA_PIECE("0xc000", "vb0", "b1")
+                 DMA_PIECE("0xc400", "vb1", "b1")
+                 "s_mov_b32 m0, %[keep]"
+                 : [keep] "=&s"(keep)
+                 : [va0] "v"(va0), [va1] "v"(va1), [vb0] "v"(vb0), [vb1] "v"(vb1), [dst] "s"(dst), [a] "s"(a), [b0] "s"(b0), [b1] "s"(b1)
+                 : "memory", "scc");
+}
+
+// What the K loops of the 256^2 kernels stage through.  FAST = false: stage_half() with the arguments it always had.  The loop names the
+// K-tile by the one it computes on (t) and a distance (rel = 0, 1, 2) and calls next() once per K-tile (FAST: the scalar advance).
+template <int AK, int BK, bool KTAIL, bool FAST> struct Stage256 {
+    const GemmP& p;
+    const int m0, n0, kbeg, wave, lane;
+    DmaCtx<AK, 0> ca;
+    DmaCtx<BK, 1> cb;
+    const char *pa, *pb;                                          // FAST: the contexts' position = the K-tile the loop computes on
+    __device__ __forceinline__ Stage256(const GemmP& p_, int m0_, int n0_, int kbeg_, int wave_, int lane_)
+        : p(p_), m0(m0_), n0(n0_), kbeg(kbeg_), wave(wave_), lane(lane_) {
+        if constexpr (FAST) {
+            ca.begin(p.A, p.lda, m0, kbeg, wave, lane);
+            cb.begin(p.B, p.ldb, n0, kbeg, wave, lane);
+            pa = ca.base; pb = cb.base;
+        }
+    }
+    __device__ __forceinline__ void next() {
+        if constexpr (FAST) { pa += ca.dk; pb += cb.dk; }
+    }
+    template <int H> __device__ __forceinline__ void half_a(int t, int rel, char* slot) const {
+        if constexpr (FAST) dma_half(ca.voff, ca.voff1, lds_addr(slot + wave * 2048), ca.at(pa, rel, H));
+        else stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, kbeg + (t + rel) * BKT, p.K, H, slot, wave, lane);
+    }
+    template <int H> __device__ __forceinline__ void half_b(int t, int rel, char* slot) const {
+        if constexpr (FAST) dma_half(cb.voff, cb.voff1, lds_addr(slot + wave * 2048), cb.at(pb, rel, H));
+        else stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, kbeg + (t + rel) * BKT, p.K, H, slot, wave, lane);
+    }
+    // A0, B0, B1 of K-tile t + rel into the buffer `buf`
+    __device__ __forceinline__ void a0b0b1(int t, int rel, char* buf) const {
+        if constexpr (FAST) {
+            dma_a0b0b1(ca.voff, ca.voff1, cb.voff, cb.voff1, lds_addr(buf + wave * 2048), ca.at(pa, rel, 0),
+                                            cb.at(pb, rel, 0), cb.at(pb, rel, 1));
+        } else {
+            half_a<0>(t, rel, buf + OFF_A0);
+            half_b<0>(t, rel, buf + OFF_B0);
+            half_b<1>(t, rel, buf + OFF_B1);
+        }
+    }
+    // prologue of a tile's K loop, in steady-state issue order: A0 B0 B1 A1 of K-tile 0, then A0 B0 B1 of K-tile 1
+    __device__ __forceinline__ void prologue(char* smem, int nk) const {
+        a0b0b1(0, 0, smem);
+        half_a<1>(0, 0, smem + OFF_A1);
+        if (nk > 1) a0b0b1(0, 1, smem + KBUF_BYTES);
+    }
+};
+
 #define G256_END_LOAD()                                   \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
     __builtin_amdgcn_sched_barrier(0);                    \
@@ -928,7 +1118,7 @@ __device__ __forceinline__ void stage_half(const bf16_t* __restrict__ G, int ld,
 
 // One output tile (virtual workgroup `bid` of `nwg` in the band-major tile order).  The kernel below calls it once per tile of its
 // workgroup.
-template <int AK, int BK, class Epi, bool KTAIL, bool FE = false>
+template <int AK, int BK, class Epi, bool KTAIL, bool FE = false, bool FAST = false>
 __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, char* smem, const int bid, const int nwg) {
 #ifdef MAPDIT_GEMM_STAMPS
     long long* stamp_lds = (long long*)(smem + SMEM2_BYTES);
@@ -992,15 +1182,9 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
     // prologue, in steady-state issue order: A0 B0 B1 A1 of tile 0, then A0 B0 B1 of tile 1 (its A1 is phase 1's DMA)
-    stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, kbeg, p.K, 0, smem + OFF_A0, wave, lane);
-    stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, kbeg, p.K, 0, smem + OFF_B0, wave, lane);
-    stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, kbeg, p.K, 1, smem + OFF_B1, wave, lane);
-    stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, kbeg, p.K, 1, smem + OFF_A1, wave, lane);
+    Stage256<AK, BK, KTAIL, FAST> sg(p, m0, n0, kbeg, wave, lane);
+    sg.prologue(smem, nk);
     if (nk > 1) {
-        char* b1 = smem + KBUF_BYTES;
-        stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, kbeg + BKT, p.K, 0, b1 + OFF_A0, wave, lane);
-        stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, kbeg + BKT, p.K, 0, b1 + OFF_B0, wave, lane);
-        stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, kbeg + BKT, p.K, 1, b1 + OFF_B1, wave, lane);
         if (p.phases == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // A0, B0, B1 of tile 0 have landed
         else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");                  // A0, B0 of tile 0; five half-tiles in flight
     } else {
@@ -1028,14 +1212,13 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
         for (int t = 0; t < nk; ++t) {
             char* cur = smem + (t & 1) * KBUF_BYTES;
             char* nxt = smem + ((t + 1) & 1) * KBUF_BYTES;
-            const int k1 = kbeg + (t + 1) * BKT, k2 = kbeg + (t + 2) * BKT;
             const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
             G256_STAMP(0);
             load_a(cur + OFF_A0);
             G256_LOAD_B(fb0, cur + OFF_B0);
             G256_LOAD_B(fb1, cur + OFF_B1);
             if (has1) {
-                stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k1, p.K, 1, nxt + OFF_A1, wave, lane);
+                sg.template half_a<1>(t, 1, nxt + OFF_A1);
                 G256_STAMP(1);
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else {
@@ -1051,9 +1234,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
             G256_STAMP(5);
             load_a(cur + OFF_A1);
             if (has2) {
-                stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k2, p.K, 0, cur + OFF_A0, wave, lane);
-                stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 0, cur + OFF_B0, wave, lane);
-                stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 1, cur + OFF_B1, wave, lane);
+                sg.a0b0b1(t, 2, cur);
                 G256_STAMP(6);
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else if (has1) {
@@ -1069,40 +1250,41 @@ __device__ __forceinline__ void gemm256_tile(const GemmP& p, const Epi& epi, cha
             G256_STAMP(9);
             G256_END_MFMA();
             G256_STAMP(10);
+            sg.next();
         }
     } else
     for (int t = 0; t < nk; ++t) {
         char* cur = smem + (t & 1) * KBUF_BYTES;
         char* nxt = smem + ((t + 1) & 1) * KBUF_BYTES;
-        const int k1 = kbeg + (t + 1) * BKT, k2 = kbeg + (t + 2) * BKT;
         const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
         // phase 1: quadrant (0,0); slot A1 of the other buffer was last read in phase 3 of tile t-1
         load_a(cur + OFF_A0);
         G256_LOAD_B(fb0, cur + OFF_B0);
-        if (has1) stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k1, p.K, 1, nxt + OFF_A1, wave, lane);
+        if (has1) sg.template half_a<1>(t, 1, nxt + OFF_A1);
         G256_WAIT_DMA(has2);
         G256_END_LOAD();
         G256_MFMA(0, 0, fb0);
         G256_END_MFMA();
         // phase 2: quadrant (0,1); slot A0 was last read in phase 1
         G256_LOAD_B(fb1, cur + OFF_B1);
-        if (has2) stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k2, p.K, 0, cur + OFF_A0, wave, lane);
+        if (has2) sg.template half_a<0>(t, 2, cur + OFF_A0);
         G256_WAIT_DMA(has2);
         G256_END_LOAD();
         G256_MFMA(0, 1, fb1);
         G256_END_MFMA();
         // phase 3: quadrant (1,1); slot B0 was last read in phase 1 (its fragments live on in fb0)
         load_a(cur + OFF_A1);
-        if (has2) stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 0, cur + OFF_B0, wave, lane);
+        if (has2) sg.template half_b<0>(t, 2, cur + OFF_B0);
         G256_END_LOAD();
         G256_MFMA(1, 1, fb1);
         G256_END_MFMA();
         // phase 4: quadrant (1,0) from registers only; slot B1 was last read in phase 2
-        if (has2) stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 1, cur + OFF_B1, wave, lane);
+        if (has2) sg.template half_b<1>(t, 2, cur + OFF_B1);
         G256_WAIT_DMA(has2);
         G256_END_LOAD();
         G256_MFMA(1, 0, fb0);
         G256_END_MFMA();
+        sg.next();
     }
     if (wm == 0) {                                         // rebalance the barrier count of the two groups
         __builtin_amdgcn_s_barrier();
@@ -1368,7 +1550,7 @@ __device__ __forceinline__ void stagger_start(const GemmP& p) {
 // XCD either way, so the band-major order keeps its meaning).  What it saves is the hand-over between two workgroups on a CU: the
 // dispatch of the next one waits for the previous one's stores to drain and its LDS to be released (3-7 k cycles per tile of
 // ~50 k); inside one workgroup the next tile's prologue starts behind the last store's issue.
-template <int AK, int BK, class Epi, bool KTAIL = false, bool FE = false>
+template <int AK, int BK, class Epi, bool KTAIL = false, bool FE = false, bool FAST = false>
 __global__ __launch_bounds__(512, 2) void gemm_mfma256_kernel(GemmP p, Epi epi) {
 #ifdef MAPDIT_GEMM_STAMPS
     __shared__ __attribute__((aligned(16))) char smem[SMEM2_BYTES + (2 * STAMP_TILES * STAMP_POINTS + 8) * 8];
@@ -1378,7 +1560,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256_kernel(GemmP p, Epi epi) 
     const int total = p.tiles * p.split_k;
     stagger_start(p);
     for (int v = blockIdx.x; v < total; v += gridDim.x) {
-        gemm256_tile<AK, BK, Epi, KTAIL, FE>(p, epi, smem, v, total);
+        gemm256_tile<AK, BK, Epi, KTAIL, FE, FAST>(p, epi, smem, v, total);
         __syncthreads();                                   // the tile's last LDS reads are done before the next prologue lands
     }
 }
@@ -1396,6 +1578,7 @@ struct GroupArgs {
     int first[GROUP_MAX + 1];      // first[i] = virtual workgroups (tiles x split_k) of the problems before i; first[n] = all
     int n;
 };
+template <bool FAST>
 __global__ __launch_bounds__(512, 2) void gemm_mfma256_group_kernel(GroupArgs g) {
 #ifdef MAPDIT_GEMM_STAMPS
     __shared__ __attribute__((aligned(16))) char smem[SMEM2_BYTES + (2 * STAMP_TILES * STAMP_POINTS + 8) * 8];
@@ -1406,7 +1589,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256_group_kernel(GroupArgs g)
     for (int v = blockIdx.x; v < total; v += gridDim.x) {
         int i = 0;
         while (i + 1 < g.n && v >= g.first[i + 1]) ++i;
-        gemm256_tile<OP_KMAJ, OP_KMAJ, EpiStoreF32, false, false>(g.p[i], g.e[i], smem, v - g.first[i], g.first[i + 1] - g.first[i]);
+        gemm256_tile<OP_KMAJ, OP_KMAJ, EpiStoreF32, false, false, FAST>(g.p[i], g.e[i], smem, v - g.first[i], g.first[i + 1] - g.first[i]);
         __syncthreads();
     }
 }
@@ -1449,18 +1632,10 @@ constexpr int WPRIV_BYTES = 4096;                          // per-wave epilogue 
 constexpr int SMEM_W_BYTES = 2 * KBUF_BYTES + 8 * WPRIV_BYTES;   // 163,840 B: all of the CU's LDS
 
 // prologue of a tile's K loop, in steady-state issue order: A0 B0 B1 A1 of K-tile 0, then A0 B0 B1 of K-tile 1
-template <int AK, int BK, bool KTAIL>
+template <int AK, int BK, bool KTAIL, bool FAST>
 __device__ __forceinline__ void g256_prologue(const GemmP& p, const TileCoord& c, char* smem, int wave, int lane) {
-    stage_half<AK, 0, KTAIL>(p.A, p.lda, c.m0, p.M, c.kbeg, p.K, 0, smem + OFF_A0, wave, lane);
-    stage_half<BK, 1, KTAIL>(p.B, p.ldb, c.n0, p.N, c.kbeg, p.K, 0, smem + OFF_B0, wave, lane);
-    stage_half<BK, 1, KTAIL>(p.B, p.ldb, c.n0, p.N, c.kbeg, p.K, 1, smem + OFF_B1, wave, lane);
-    stage_half<AK, 0, KTAIL>(p.A, p.lda, c.m0, p.M, c.kbeg, p.K, 1, smem + OFF_A1, wave, lane);
-    if (c.nk > 1) {
-        char* b1 = smem + KBUF_BYTES;
-        stage_half<AK, 0, KTAIL>(p.A, p.lda, c.m0, p.M, c.kbeg + BKT, p.K, 0, b1 + OFF_A0, wave, lane);
-        stage_half<BK, 1, KTAIL>(p.B, p.ldb, c.n0, p.N, c.kbeg + BKT, p.K, 0, b1 + OFF_B0, wave, lane);
-        stage_half<BK, 1, KTAIL>(p.B, p.ldb, c.n0, p.N, c.kbeg + BKT, p.K, 1, b1 + OFF_B1, wave, lane);
-    }
+    Stage256<AK, BK, KTAIL, FAST> sg(p, c.m0, c.n0, c.kbeg, wave, lane);
+    sg.prologue(smem, c.nk);
 }
 
 // Per epilogue: accumulator tiles between the load of its stream operand and the use (kEpiPrefetch), and whether the LDS round trip of
@@ -1555,7 +1730,7 @@ __device__ __forceinline__ void g256w_epilogue(const GemmP& p, const Epi& epi, c
     }
 }
 
-template <int AK, int BK, class Epi, bool KTAIL = false>
+template <int AK, int BK, class Epi, bool KTAIL = false, bool FAST = false>
 __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi) {
     __shared__ __attribute__((aligned(16))) char smem[SMEM_W_BYTES];
     const int total = p.tiles * p.split_k;
@@ -1566,7 +1741,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
     TileCoord c = tile_coord(p, v, total);
     {
         const int tid0 = threadIdx.x;
-        g256_prologue<AK, BK, KTAIL>(p, c, smem, __builtin_amdgcn_readfirstlane(tid0 >> 6), tid0 & 63);
+        g256_prologue<AK, BK, KTAIL, FAST>(p, c, smem, __builtin_amdgcn_readfirstlane(tid0 >> 6), tid0 & 63);
     }
     bool first = true;
 #ifdef MAPDIT_GEMM_STAMPS
@@ -1584,7 +1759,8 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
         const int tid = tid_, lane = tid & 63;
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int wm = wave >> 2, wn = wave & 3;           // wm doubles as the stagger group (waves 4-7 run behind)
-        const int m0 = c.m0, n0 = c.n0, kbeg = c.kbeg, nk = c.nk;
+        const int nk = c.nk;
+        Stage256<AK, BK, KTAIL, FAST> sg(p, c.m0, c.n0, c.kbeg, wave, lane);
         f32x4_t acc[8][4];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -1614,13 +1790,12 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
         for (int t = 0; t < nk; ++t) {
             char* cur = smem + (t & 1) * KBUF_BYTES;
             char* nxt = smem + ((t + 1) & 1) * KBUF_BYTES;
-            const int k1 = kbeg + (t + 1) * BKT, k2 = kbeg + (t + 2) * BKT;
             const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
             load_a(cur + OFF_A0);
             G256_LOAD_B(fb0, cur + OFF_B0);
             G256_LOAD_B(fb1, cur + OFF_B1);
             if (has1) {
-                stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k1, p.K, 1, nxt + OFF_A1, wave, lane);
+                sg.template half_a<1>(t, 1, nxt + OFF_A1);
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1631,9 +1806,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
             G256_END_MFMA();
             load_a(cur + OFF_A1);
             if (has2) {
-                stage_half<AK, 0, KTAIL>(p.A, p.lda, m0, p.M, k2, p.K, 0, cur + OFF_A0, wave, lane);
-                stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 0, cur + OFF_B0, wave, lane);
-                stage_half<BK, 1, KTAIL>(p.B, p.ldb, n0, p.N, k2, p.K, 1, cur + OFF_B1, wave, lane);
+                sg.a0b0b1(t, 2, cur);
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else if (has1) {
                 asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -1644,6 +1817,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
             G256_MFMA(1, 1, fb1);
             G256_MFMA(1, 0, fb0);
             G256_END_MFMA();
+            sg.next();
         }
         if (wm == 0) {                                     // rebalance the barrier count of the two groups
             __builtin_amdgcn_s_barrier();
@@ -1656,7 +1830,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
         TileCoord cn = c;
         if (vn < total) {
             cn = tile_coord(p, vn, total);
-            g256_prologue<AK, BK, KTAIL>(p, cn, smem, wave, lane);
+            g256_prologue<AK, BK, KTAIL, FAST>(p, cn, smem, wave, lane);
         }
         GW_STAMP(ts3_);
         if (c.m0 + BM2 <= p.M && c.n0 + BN2 <= p.N)
@@ -1736,6 +1910,7 @@ struct GemmEnv {
     int nsplit = 1;          // MAPDIT_GEMM_NSPLIT = 0: no column split of results whose width is an odd multiple of 128
     int fast_epi = 1;        // MAPDIT_GEMM_FE = 0: never the straight-line epilogue instantiation (RESID; A/B)
     int band768 = 3;         // MAPDIT_GEMM_BAND768 = column tiles per band of the K <= 768 forward (NT) GEMMs (fc1, QKV)
+    int dma_fast = 1;        // MAPDIT_GEMM_DMA = 0: never the scalar-base staging of interior tiles (A/B)
     int stagger = -1;        // MAPDIT_GEMM_STAGGER = late start of every second workgroup, units of 8,128 cycles (persistent launches); -1: by epilogue
     GemmEnv() {
         if (const char* e = getenv("MAPDIT_GEMM_PERSIST")) persist = atoi(e);
@@ -1744,6 +1919,7 @@ struct GemmEnv {
         if (const char* e = getenv("MAPDIT_GEMM_STAGGER")) stagger = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_BAND768")) band768 = atoi(e) > 0 ? atoi(e) : 3;
         if (const char* e = getenv("MAPDIT_GEMM_FE")) fast_epi = atoi(e);
+        if (const char* e = getenv("MAPDIT_GEMM_DMA")) dma_fast = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_TILE_RULE")) old_tile_rule = e[0] == 'o';
         if (const char* e = getenv("MAPDIT_GEMM_TILE")) tile = atoi(e);
         if (const char* e = getenv("MAPDIT_GEMM_PHASES")) phases = gemm_phases_arg(atoi(e));
@@ -1752,6 +1928,7 @@ struct GemmEnv {
 };
 GemmEnv& mapdit_gemm_env_ref();
 static GemmEnv& gemm_env() { return mapdit_gemm_env_ref(); }
+extern "C" int mapdit_gemm_dma_fast(int layout, int M, int N, int K, int lda, int ldb, int tile);
 #if MAPDIT_DT == 0
 GemmEnv& mapdit_gemm_env_ref() {
     static GemmEnv env;
@@ -1795,6 +1972,22 @@ extern "C" int mapdit_gemm_tile_size_k(int M, int N, int K, int split_k_launch) 
     if (t256 < 128) return 128;
     if (!gemm_env().old_tile_rule && t256 > 256 && t256 <= 320) return 128;
     return 256;
+}
+
+// The scalar-base staging (DmaCtx) keeps every offset of an operand but its 64-bit base in 32 bits - the lane offset, the steps between
+// pieces and halves, the advance per K-tile (64 rows of a K-major operand): operands whose extent, rows x ld x 2 bytes, does not fit an
+// unsigned 32-bit byte offset stay on the 64-bit lane addresses of stage_half / stage_tile.
+extern "C" int mapdit_gemm_dma_extent_ok(long rows, long ld) {
+    return rows > 0 && ld > 0 && ld < (1l << 31) && rows < (1l << 32) && (unsigned long)rows * (unsigned long)ld * 2ul < (1ul << 32);
+}
+// 1 if a launch on tiles of `tile` rows (256: 256 x 256, 128: 128 x 128, 64: 64 x 128) stages that way: every tile inside the result (no
+// row or column clamp), no K tail, both operands within the 32-bit extent.  Anything else keeps stage_half / stage_tile.
+extern "C" int mapdit_gemm_dma_fast(int layout, int M, int N, int K, int lda, int ldb, int tile) {
+    if (layout < MAPDIT_NT || layout > MAPDIT_TN || (tile != 256 && tile != 128 && tile != 64)) return 0;
+    const int tn = tile == 256 ? 256 : 128;
+    if (M <= 0 || N <= 0 || K <= 0 || M % tile != 0 || N % tn != 0 || K % 64 != 0) return 0;
+    const bool a_kmaj = layout == MAPDIT_TN, b_kmaj = layout != MAPDIT_NT;
+    return mapdit_gemm_dma_extent_ok(a_kmaj ? K : M, lda) && mapdit_gemm_dma_extent_ok(b_kmaj ? K : N, ldb);
 }
 extern "C" int mapdit_gemm_tile_size_ex(int M, int N, int split_k_launch) { return mapdit_gemm_tile_size_k(M, N, 0, split_k_launch); }
 extern "C" int mapdit_gemm_tile_size(int M, int N) { return mapdit_gemm_tile_size_ex(M, N, 0); }
@@ -1911,26 +2104,29 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
         bool fe = false;
         if constexpr (kFastEpi<Epi>)
             fe = gemm_env().fast_epi && M % BM2 == 0 && N % BN2 == 0 && epi.fast_ok();
-        auto go = [&](auto tail) {
-            constexpr bool TAIL = decltype(tail)::value;
+        // FAST: the K loop stages from a scalar base and one lane offset per operand (DmaCtx) - interior tiles only, never with a K tail
+        const bool fast = gemm_env().dma_fast && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 256);
+        auto go = [&](auto tail, auto fst) {
+            constexpr bool TAIL = decltype(tail)::value, FAST = decltype(fst)::value;
             with_operand_kinds(layout, [&](auto ak, auto bk) {
                 if constexpr (!kReduce<Epi>) {
-                    if (use_w) { hipLaunchKernelGGL((gemm_mfma256w_kernel<ak.value, bk.value, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi); return; }
+                    if (use_w) { hipLaunchKernelGGL((gemm_mfma256w_kernel<ak.value, bk.value, Epi, TAIL, FAST>), dim3(grid), dim3(512), 0, st, p, epi); return; }
                 }
                 if constexpr (kFastEpi<Epi> && !TAIL) {
-                    if (fe) { hipLaunchKernelGGL((gemm_mfma256_kernel<ak.value, bk.value, Epi, false, true>), dim3(grid), dim3(512), 0, st, p, epi); return; }
+                    if (fe) { hipLaunchKernelGGL((gemm_mfma256_kernel<ak.value, bk.value, Epi, false, true, FAST>), dim3(grid), dim3(512), 0, st, p, epi); return; }
                 }
-                hipLaunchKernelGGL((gemm_mfma256_kernel<ak.value, bk.value, Epi, TAIL>), dim3(grid), dim3(512), 0, st, p, epi);
+                hipLaunchKernelGGL((gemm_mfma256_kernel<ak.value, bk.value, Epi, TAIL, false, FAST>), dim3(grid), dim3(512), 0, st, p, epi);
             });
         };
         if constexpr (kHasTail<Epi>) {
             if (ktail) {
-                go(std::true_type());
+                go(std::true_type(), std::false_type());
                 MD_LAUNCH_CHECK();
                 return MAPDIT_OK;
             }
         }
-        go(std::false_type());
+        if (fast) go(std::false_type(), std::true_type());
+        else go(std::false_type(), std::false_type());
     } else if (mfma) {
         // Round 5: few 128^2 tiles (DiT-XL's 128-column strips: 128 or fewer workgroups on 256 CUs) -> 64-row tiles, twice the workgroups, the
         // same bits (gemm_mfma64_kernel).  For the epilogues the strips carry.  MAPDIT_GEMM_TILE64=0 switches it off (A/B).
@@ -1940,8 +2136,10 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
             if (t64_env && !a_kmaj && !ktail && split_k == 1 && t128 <= 160 && M >= 256) {
                 GemmP p{A, B, lda, ldb, M, N, K, cdiv(N, BN), 0, 1, 0, 4, n_off, 0};
                 p.tiles = cdiv(M, 64) * p.tiles_n;
+                const bool fast = gemm_env().dma_fast && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 64);
                 with_operand_kinds(layout, [&](auto, auto bk) {       // (A is row-major here)
-                    hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
+                    if (fast) hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi, true>), dim3(p.tiles), dim3(256), 0, st, p, epi);
+                    else hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
                 });
                 MD_LAUNCH_CHECK();
                 return MAPDIT_OK;
@@ -1959,8 +2157,10 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
                 return MAPDIT_OK;
             }
         }
+        const bool fast = gemm_env().dma_fast && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 128);
         with_operand_kinds(layout, [&](auto ak, auto bk) {
-            hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
+            if (fast) hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi, false, true>), dim3(grid), dim3(256), 0, st, p, epi);
+            else hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
         });
     } else {
         if (n_off != 0 || force128) {          // the scalar fallback indexes columns from 0: never the second half of a column split
@@ -1999,6 +2199,7 @@ extern "C" int MD_SYM_GEMM_GROUP(int n, const mapdit_gemm_group_item_t* items, i
     MD_CHECK(K > 0 && K % BKT == 0 && split_k >= 1 && split_k <= K / BKT, "gemm_group: K=%d must be a multiple of 64 and split_k=%d <= K / 64", K, split_k);
     GroupArgs g{};
     g.n = n;
+    bool fast = gemm_env().dma_fast != 0;
     for (int i = 0; i < n; ++i) {
         const mapdit_gemm_group_item_t& it = items[i];
         MD_CHECK(it.A && it.B && it.out && it.M > 0 && it.N > 0, "gemm_group: item %d: null / empty", i);
@@ -2014,8 +2215,11 @@ extern "C" int MD_SYM_GEMM_GROUP(int n, const mapdit_gemm_group_item_t* items, i
         p.band = (int)band;
         g.e[i] = EpiStoreF32{it.out, it.ldo, it.alpha, 0, it.slab_stride};
         g.first[i + 1] = g.first[i] + p.tiles * split_k;
+        fast = fast && mapdit_gemm_dma_fast(MAPDIT_TN, it.M, it.N, K, it.lda, it.ldb, 256);
     }
-    hipLaunchKernelGGL(gemm_mfma256_group_kernel, dim3(g.first[n]), dim3(512), 0, (hipStream_t)stream, g);
+    // (one kernel for the whole group: the scalar-base staging only if every item qualifies)
+    if (fast) hipLaunchKernelGGL(gemm_mfma256_group_kernel<true>, dim3(g.first[n]), dim3(512), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL(gemm_mfma256_group_kernel<false>, dim3(g.first[n]), dim3(512), 0, (hipStream_t)stream, g);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }
