@@ -332,6 +332,9 @@ int mapdit_sum_bf16_chunks(float* out, const uint16_t* chunks, int nchunks, long
 /* out[i] = alpha * x[i] (abi 5): the label table's gradient when the table is a plain nn.Embedding (MAPDIT_OFF_MP_EMBEDDING) - the
  * scattered rows, divided by the fp16 loss scale. */
 int mapdit_scale_copy(float* out, const float* x, long n, float alpha, void* stream);
+/* out[i] += alpha * x[i], the product rounded to fp32 before the addition (additive within abi 5): mapdit_scale_copy's accumulate form -
+ * that label-table gradient under mapdit_engine_set_grad_accumulate. */
+int mapdit_scale_accumulate(float* out, const float* x, long n, float alpha, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Cosine attention (src/layers/attention.py:37-51).  Head-major operands are [B*H][T][head_dim] bf16, row-major.
@@ -609,7 +612,8 @@ int mapdit_engine_prepare_weights(mapdit_engine_t* e, int forced, void* stream);
 /* out [N, 2C, S, S] = DiT(x, t, y_eff); y_eff already has label drop applied.  save != 0 keeps activations. */
 int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const int64_t* t, const int64_t* y_eff, int N, int save,
                           float* out, void* stream);
-/* Backward of the last saved forward: writes d loss / d parameter into every bound grad pointer (overwrite).  A bf16 / f16 engine
+/* Backward of the last saved forward: writes d loss / d parameter into every bound grad pointer (overwrite; after
+ * mapdit_engine_set_grad_accumulate: adds).  A bf16 / f16 engine
  * reads the saved forward without changing it: the backward may be run again over the same forward (another dout). */
 int mapdit_engine_backward(mapdit_engine_t* e, const float* dout, void* stream);
 /* The same in pieces, for overlapping the data-parallel gradient reduction with backward: stage 0 = final layer,
@@ -637,6 +641,21 @@ int mapdit_engine_loss_scale(mapdit_engine_t* e, float* out);
  * gradient buffer (none needs to be bound); what the fused kernels cannot skip (gain partials, MPScale reference sums) lands in scratch.
  * Refused while a staged backward is in progress; a forward drops a request no backward consumed (call it between forward and backward). */
 int mapdit_engine_set_input_grad(mapdit_engine_t* e, float* dx, int input_only);
+/* Gradient accumulation (additive within abi 5).  One-shot, like the input-gradient request: with on != 0 the next backward - one
+ * mapdit_engine_backward call, or the whole run of mapdit_engine_backward_stages from stage 0 to depth+1 - ADDS to every bound gradient
+ * buffer instead of overwriting it: g <- g + new, where `new` is the fp32 value a fresh backward stores and the addition is one fp32
+ * addition per element (the accumulate forms of the writers: bit 0 of the weight-norm Jacobians' flags, mapdit_reduce_partials,
+ * mapdit_scale_accumulate, the MPScale reference sums without their memset; no atomics, no scratch copy, a fixed order: steps stay
+ * bit-reproducible, and accumulating onto zeros gives a fresh backward's bits).  k micro-batches per optimiser step: a fresh backward,
+ * then k - 1 accumulating ones.  The request is cleared when that backward's last stage returns and dropped by the next forward (call it
+ * between forward and backward); an input-only backward (mapdit_engine_set_input_grad) writes no parameter gradient and ignores it.
+ * Entries of the gradient table that are not a parameter's gradient (the scratch bound for buffers) may hold anything afterwards.
+ * Refused - mapdit_last_error() names "accumulate" - while a staged backward is in progress, on a MAPDIT_PREC_BF16X3 engine (accumulate
+ * there by keeping a copy) and while the weight passes are sharded (mapdit_engine_set_shard with world > 1: the buffers hold raw sums
+ * between the exchange and the Jacobian).  fp16: the automatic loss scale is chosen for a loss that is the MEAN over the N samples of the
+ * forward; keep each micro-batch's loss such a mean and fold 1 / k into the optimiser's gradient scale instead of dividing the loss, or
+ * set the loss scale k times higher. */
+int mapdit_engine_set_grad_accumulate(mapdit_engine_t* e, int on);
 
 /* Measurement hook: bracket every launch of one kernel family with HIP events on the launch stream.
  * MAPDIT_PROF_FC1_FWD = the block-MLP fc1 GEMM (gemm NT + SILU2 epilogue, [N*T, 4D] = [N*T, D] x [4D, D]^T). */

@@ -96,6 +96,10 @@ struct mapdit_engine {
     float* ig_dx = nullptr;
     bool ig_only = false;
     bool have_saved = false;
+    // mapdit_engine_set_grad_accumulate, one-shot: every parameter gradient the next backward writes is g <- g + new, `new` being the fp32
+    // value a fresh backward stores (the accumulate forms of the writers: same arithmetic, one more fp32 addition; fixed order, no atomics).
+    // Cleared when that backward's last stage returns and by the next forward; an input-only backward writes no gradient and ignores it.
+    bool gacc = false;
     // mapdit_config_t.recompute of a 16-bit training engine (0 otherwise).  blk[] keeps one entry per block at every level: a buffer that
     // exists once (MLP: hact, hdact; BLOCK: everything but xm and y2) is carved with block 0 and every other entry points at it, and block
     // i's backward stage starts by putting block i back into it (recompute_block).
@@ -200,6 +204,10 @@ namespace {
 int pidx_block(int i, int which) { return MAPDIT_NUM_GLOBAL + i * MAPDIT_NUM_BLOCK + which; }
 
 const float CA = 0.7f / sqrtf(0.58f), CB = 0.3f / sqrtf(0.58f);   // mp_sum(x, y, 0.3): src/utils.py:15-16
+
+// 1 while the running backward adds into the bound gradient buffers (mapdit_engine::gacc): bit 0 of the weight-norm Jacobians' flags, the
+// `accumulate` of mapdit_reduce_partials
+int grad_acc(const mapdit_engine* e) { return e->gacc && !e->ig_only ? 1 : 0; }
 
 // MAPDIT_SIDE_JAC=1 moves the weight-norm Jacobians to a side stream (round 5, measured and NOT the default: see the comment at
 // mapdit_engine::side); read once.
@@ -601,6 +609,9 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
     const bool no_fuse = fuse_env == 0 || (fuse_env < 0 && !e->dx16);
     const bool any_m = fuse_env == 2 || (fuse_env < 0 && e->dx16);
     const int D = e->D;
+    // accumulation: the pass never sums the gain partials into the gradient itself (its dgain_out form stores) - they go through
+    // mapdit_reduce_partials, which adds them up in the same order and has the accumulate form
+    const int acc = grad_acc(e);
     int npart = 0;
     a.part_scratch = e->rmb_part;                       // lets small batches take the row-split form (more blocks)
     a.part_scratch_bytes = (size_t)8 * e->cfg.max_batch * 3 * D * sizeof(float);
@@ -615,9 +626,9 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
         TRY(gemm16(e, MAPDIT_NN, M, D, K, dy, ld_dy, wimg, D, epi_bf16(e->dxm, D), st));
         mapdit_resid_mod_bwd_t m = a;
         m.dxo = nullptr; m.dxo_bf = nullptr; m.y_up = nullptr; m.g_up = nullptr; m.dy_up = nullptr; m.dg_up = nullptr;
-        m.x = e->XH[site]; m.dxm = e->dxm; m.dx = e->ln_g; m.dx_bf = nullptr; m.dgain_out = dgain;
+        m.x = e->XH[site]; m.dxm = e->dxm; m.dx = e->ln_g; m.dx_bf = nullptr; m.dgain_out = acc ? nullptr : dgain;
         TRY(DT_FN(e, mapdit_resid_mod_bwd)(&m, st));
-        if (npart) TRY(mapdit_reduce_partials(e->gain_part, npart, dgain, 0, st));
+        if (npart) TRY(mapdit_reduce_partials(e->gain_part, npart, dgain, acc, st));
         TRY(DT_FN(e, mapdit_ln_bwd_merge)(e->ln_g, e->XH[site], e->rstd[site], a.dxo, a.dxo_bf, a.ca, e->ln_s, (long)M, D, st));
         mapdit_resid_mod_bwd_t r = a;
         int npart_r = 0;
@@ -632,7 +643,7 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
         TRY(DT_FN(e, mapdit_resid_mod_bwd)(&a, st));
         TRY(mapdit_rot_coef_bwd(e->rot_dA, e->rot_dB, D, rot->theta, rot->scale, e->ldm, rot->gain, rot->dtheta, rot->dscale, e->ldm,
                                 e->gain_part, e->ginv, a.n_samples, D, st));
-        return mapdit_reduce_partials(e->gain_part, a.n_samples * cdiv(D / 2, 256), dgain, 0, st);
+        return mapdit_reduce_partials(e->gain_part, a.n_samples * cdiv(D / 2, 256), dgain, acc, st);
     }
     // Round 5: a width that is an odd multiple of 128 on few enough rows that the 256^2 tiles of its first D - 128 columns fill the
     // chip about once (DiT-XL/2 at 64 samples: 1152 = 4 x 256 + 128, 64 x 4 = 256 tiles) was refused by the rule above (320 tiles with
@@ -665,7 +676,7 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
         int npart2 = 0;
         b.gain_partials_out = &npart2;
         TRY(DT_FN(e, mapdit_resid_mod_bwd)(&b, st));
-        return mapdit_reduce_partials(e->gain_part, npart1 + npart2, dgain, 0, st);
+        return mapdit_reduce_partials(e->gain_part, npart1 + npart2, dgain, acc, st);
     }
     if (!no_fuse && e->T % 64 == 0 && 256 % e->T == 0 && K % 64 == 0 && (M <= 32768 || any_m) && mapdit_gemm_tile_size_k(M, D, K, 0) == 256) {
         mapdit_epilogue_t ep; memset(&ep, 0, sizeof(ep));
@@ -676,11 +687,11 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
     } else {
         TRY(gemm16(e, MAPDIT_NN, M, D, K, dy, ld_dy, wimg, D, epi_bf16(e->dxm, D), st));
         a.dxm = e->dxm;
-        a.dgain_out = dgain;                            // the gain partials are summed by the pass itself (npart = 0 then)
+        a.dgain_out = acc ? nullptr : dgain;            // the gain partials are summed by the pass itself (npart = 0 then)
         TRY(DT_FN(e, mapdit_resid_mod_bwd)(&a, st));
         if (npart == 0) return MAPDIT_OK;
     }
-    return mapdit_reduce_partials(e->gain_part, npart, dgain, 0, st);
+    return mapdit_reduce_partials(e->gain_part, npart, dgain, acc, st);
 }
 
 // dW for one linear: G = dy^T x (TN GEMM into scratch), then the weight-norm Jacobian into the bound grad.
@@ -777,7 +788,7 @@ int dw_group_flush(mapdit_engine* e, int K, void* st) {
                 ++nred;
             }
         } else
-            jac[njac++] = mapdit_wn_bwd_item_t{e->params[q.pidx], outs[k], w.cols, S, (long)w.rows * w.cols, e->grads[q.pidx], w.rows, w.cols, 1.f, e->wn_plain};
+            jac[njac++] = mapdit_wn_bwd_item_t{e->params[q.pidx], outs[k], w.cols, S, (long)w.rows * w.cols, e->grads[q.pidx], w.rows, w.cols, 1.f, e->wn_plain | grad_acc(e)};
     }
     if (nred > 0) TRY(mapdit_reduce_slabs_group(nred, red_out, red_in, red_stride, red_n, S, st));
     // the group's Jacobians as one launch too (vector path: the weights' columns are multiples of 8 here)
@@ -830,7 +841,7 @@ int linear_dw(mapdit_engine* e, int pidx, const bf16_t* dy, int ld_dy, const bf1
         TRY(g_claim(e, 0, st));
         TRY(gemm16(e, MAPDIT_TN, w.rows, w.cols, K, dy, ld_dy, x, ld_x, ep, st));
         if (e->grads[pidx])
-            TRY(mapdit_weightnorm_bwd(e->params[pidx], e->G, w.cols, split, slab, e->grads[pidx], w.rows, w.cols, 1.f, e->wn_plain, st));
+            TRY(mapdit_weightnorm_bwd(e->params[pidx], e->G, w.cols, split, slab, e->grads[pidx], w.rows, w.cols, 1.f, e->wn_plain | grad_acc(e), st));
         return MAPDIT_OK;
     }
     // the GEMM on the caller's stream into the buffer whose previous Jacobian has finished, the Jacobian behind it on the side stream
@@ -841,7 +852,8 @@ int linear_dw(mapdit_engine* e, int pidx, const bf16_t* dy, int ld_dy, const bf1
     TRY(gemm16(e, MAPDIT_TN, w.rows, w.cols, K, dy, ld_dy, x, ld_x, ep, st));
     HIP_TRY(hipEventRecord(e->ev_gemm[b], (hipStream_t)st), "linear_dw: event record");
     HIP_TRY(hipStreamWaitEvent(e->side, e->ev_gemm[b], 0), "linear_dw: side stream wait");
-    TRY(mapdit_weightnorm_bwd_slim(e->params[pidx], e->Gbuf[b], w.cols, split, slab, e->grads[pidx], w.rows, w.cols, 1.f, e->wn_plain, e->side));
+    TRY(mapdit_weightnorm_bwd_slim(e->params[pidx], e->Gbuf[b], w.cols, split, slab, e->grads[pidx], w.rows, w.cols, 1.f, e->wn_plain | grad_acc(e),
+                                   e->side));
     HIP_TRY(hipEventRecord(e->ev_jac[b], e->side), "linear_dw: event record (side)");
     e->jac_pending[b] = true;
     return MAPDIT_OK;
@@ -1103,6 +1115,21 @@ extern "C" int mapdit_engine_set_input_grad(mapdit_engine_t* e, float* dx, int i
     MD_CHECK(dx || !input_only, "engine_set_input_grad: input_only without a dx buffer");
     e->ig_dx = dx;
     e->ig_only = dx && input_only;
+    return MAPDIT_OK;
+}
+
+// One-shot (consumed by the backward that reaches stage L+1, dropped by the next forward): that backward ADDS every parameter gradient to
+// what the bound gradient buffers hold (mapdit.h).  Like the input-gradient request it cannot change between the stages of a staged backward.
+// Not built where the gradient buffers do not hold finished gradients when a backward returns (sharded weight passes: raw sums that wait
+// for the reduce-scatter) and for the bf16x3 parity engine, whose backward has writers of its own.
+extern "C" int mapdit_engine_set_grad_accumulate(mapdit_engine_t* e, int on) {
+    MD_CHECK(e, "engine_set_grad_accumulate: null argument");
+    MD_CHECK(e->train, "engine_set_grad_accumulate: gradient accumulate needs a training engine");
+    MD_CHECK(e->next_stage == 0, "engine_set_grad_accumulate: gradient accumulate cannot change while a staged backward is in progress");
+    MD_CHECK(!on || e->cfg.precision != MAPDIT_PREC_BF16X3, "engine_set_grad_accumulate: gradient accumulate is not built for the bf16x3 engine");
+    MD_CHECK(!on || e->shard_world <= 1, "engine_set_grad_accumulate: gradient accumulate is not built for sharded weight passes (%d ranks)",
+             e->shard_world);
+    e->gacc = on != 0;
     return MAPDIT_OK;
 }
 
@@ -1570,6 +1597,7 @@ extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const i
     e->have_saved = save != 0;
     e->ig_dx = nullptr;                   // an unconsumed input-gradient request belonged to the previous forward's backward
     e->ig_only = false;
+    e->gacc = false;                      // (so did an unconsumed accumulate request)
     return MAPDIT_OK;
 }
 
@@ -1657,6 +1685,8 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
         if (!io) return e->grads[idx];
         return e->dcd + (idx == MAPDIT_P_MS_REF ? 0 : idx == MAPDIT_P_SS_REF ? NSCALE : 2 * NSCALE);
     };
+    const int acc = grad_acc(e);          // accumulation (mapdit_engine_set_grad_accumulate): every writer of a bound gradient adds
+    MD_CHECK(!acc || e->shard_world <= 1, "engine_backward: gradient accumulate is not built for sharded weight passes");
     if (stage_from == 0) {
     e->dw_pending.clear();
     // fp16: the whole backward runs on gradients multiplied by a power of two (mapdit_config_t.loss_scale) so that the 16-bit
@@ -1671,8 +1701,9 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     hipError_t he = io ? hipSuccess : hipMemsetAsync(e->dcs, 0, (size_t)N * D * 4, hs);
     if (he == hipSuccess) he = hipMemsetAsync(e->dcd, 0, (size_t)N * D * 4, hs);
     if (he == hipSuccess && !io) he = hipMemsetAsync(e->dtable, 0, (size_t)c.table_rows * D * 4, hs);
-    if (he == hipSuccess && !io && G(MAPDIT_P_MS_REF)) he = hipMemsetAsync(G(MAPDIT_P_MS_REF), 0, NSCALE * 4, hs);
-    if (he == hipSuccess && !io && G(MAPDIT_P_SS_REF)) he = hipMemsetAsync(G(MAPDIT_P_SS_REF), 0, NSCALE * 4, hs);
+    // (mapdit_final_out_bwd ADDS its sample-ordered sum to the two MPScale reference gradients: cleared for a fresh backward, kept under accumulation)
+    if (he == hipSuccess && !io && !acc && G(MAPDIT_P_MS_REF)) he = hipMemsetAsync(G(MAPDIT_P_MS_REF), 0, NSCALE * 4, hs);
+    if (he == hipSuccess && !io && !acc && G(MAPDIT_P_SS_REF)) he = hipMemsetAsync(G(MAPDIT_P_SS_REF), 0, NSCALE * 4, hs);
     MD_CHECK(he == hipSuccess, "engine_backward: memset failed: %s", hipGetErrorString(he));
     MD_CHECK(G(MAPDIT_P_MS_REF) && G(MAPDIT_P_SS_REF), "engine_backward: gradient buffers not bound");
 
@@ -1798,6 +1829,7 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
     }
     if (io) {
         e->ig_only = false;
+        e->gacc = false;                  // (one-shot: it named this backward, which wrote no parameter gradient)
         e->next_stage = 0;                // (the saved forward stays: a backward reads it and changes none of it - it may run again)
         return side_join(e, st);
     }
@@ -1809,19 +1841,20 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
         ep.split_k = pick_split_k(D, e->ldp, M, e->G_cap / slab);
         ep.slab_stride = slab;
         TRY(gemm16(e, MAPDIT_TN, D, e->ldp, M, e->dx0_bf, D, e->patches, e->ldp, ep, st));
-        TRY(mapdit_weightnorm_bwd(e->params[MAPDIT_P_X_EMB], e->G, e->ldp, ep.split_k, slab, G(MAPDIT_P_X_EMB), D, e->P1, 1.f, e->wn_plain, st));
+        TRY(mapdit_weightnorm_bwd(e->params[MAPDIT_P_X_EMB], e->G, e->ldp, ep.split_k, slab, G(MAPDIT_P_X_EMB), D, e->P1, 1.f, e->wn_plain | acc, st));
     }
     // ---- conditioning path ------------------------------------------------------------------------------------------
     TRY(DT_FN(e, mapdit_cond_combine_bwd)(e->c, e->dcs, e->dcd, e->y_copy, e->dtemb_bf, e->dtable, N, D, c.table_rows, st));
     if (e->plain_embedding)           // nn.Embedding: the gradient is the scattered rows (no normalisation Jacobian)
-        TRY(mapdit_scale_copy(G(MAPDIT_P_Y_EMB), e->dtable, (long)c.table_rows * D, e->ginv, st));
+        TRY((acc ? mapdit_scale_accumulate : mapdit_scale_copy)(G(MAPDIT_P_Y_EMB), e->dtable, (long)c.table_rows * D, e->ginv, st));
     else
-        TRY(mapdit_weightnorm_bwd(e->params[MAPDIT_P_Y_EMB], e->dtable, D, 1, 0, G(MAPDIT_P_Y_EMB), c.table_rows, D, sqrtf((float)D) * e->ginv, 0,
+        TRY(mapdit_weightnorm_bwd(e->params[MAPDIT_P_Y_EMB], e->dtable, D, 1, 0, G(MAPDIT_P_Y_EMB), c.table_rows, D, sqrtf((float)D) * e->ginv, acc,
                                   st));
     TRY(gemm16(e, MAPDIT_NN, N, D, D, e->dtemb_bf, D, W(MAPDIT_P_T2), D, epi_dsilu(e->dh1_bf, e->h1_pre, D), st));
     // (plain SiLU: temb = 0.596 W2 mp_silu(h1) - the factor reaches both weight gradients of the timestep MLP; dh1 itself has no other use)
     TRY(linear_dw(e, MAPDIT_P_T2, e->dtemb_bf, D, e->h1_act, D, N, sa, st));
     TRY(linear_dw(e, MAPDIT_P_T0, e->dh1_bf, D, e->four, FOURIER, N, sa, st));
+    e->gacc = false;                      // one-shot: consumed by this backward
     e->next_stage = 0;                    // (the saved forward stays, as above)
     return side_join(e, st);
 }

@@ -483,6 +483,11 @@ __global__ void scale_copy_kernel(float* __restrict__ out, const float* __restri
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = alpha * x[i];
 }
+// out[i] += alpha * x[i]: the product is rounded to fp32 first (what scale_copy_kernel stores), then added - not one fused multiply-add
+__global__ void scale_accumulate_kernel(float* __restrict__ out, const float* __restrict__ x, long n, float alpha) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = out[i] + __fmul_rn(alpha, x[i]);
+}
 // out[i] = sum_s slabs[s*stride + i], four elements per thread   (fixed order; n a multiple of 4, 16-byte aligned)
 __global__ void reduce_slabs_kernel(float* __restrict__ out, const float* __restrict__ slabs, int nslabs, long stride, long n4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -551,6 +556,12 @@ extern "C" int MD_SYM_F32_TO_16_2D(const float* x, int ldx, uint16_t* out, int l
 extern "C" int mapdit_scale_copy(float* out, const float* x, long n, float alpha, void* stream) {
     MD_CHECK(out && x && n > 0, "scale_copy: bad argument");
     hipLaunchKernelGGL(scale_copy_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, out, x, n, alpha);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+extern "C" int mapdit_scale_accumulate(float* out, const float* x, long n, float alpha, void* stream) {
+    MD_CHECK(out && x && n > 0, "scale_accumulate: bad argument");
+    hipLaunchKernelGGL(scale_accumulate_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, out, x, n, alpha);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }

@@ -17,6 +17,7 @@ gradient scale 1/world.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -81,7 +82,32 @@ def _all_reduce_sum(t, group):
     return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=True)
 
 
-class GradReducer:
+class _NoSync:
+    """``no_sync()`` of the replicated reducers, in the sense of DistributedDataParallel's: gradient accumulation over k micro-batches runs
+    the first k - 1 backwards inside it.  There nothing is exchanged - ``_on_stage`` / ``reduce`` return at once and the model's stage hook
+    is taken off, so the backward is the engine's unstaged one - and the gradients add up in this rank's flat buffer (the engine
+    accumulates in place while ``p.grad`` stays set).  The first backward outside is the usual staged, overlapped one: every stage's slice
+    holds this rank's sum over all micro-steps when its collective is issued, every rank receives the same bits, replicas stay identical.
+    ``grad_scale`` stays 1 / world: the caller folds 1 / k into the optimiser's gradient scale (train.py --grad-accum-steps)."""
+
+    _sync = True
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        model = getattr(self, "model", None)
+        was, hook = self._sync, getattr(model, "_stage_hook", None)
+        self._sync = False
+        if model is not None:
+            model._stage_hook = None
+        try:
+            yield self
+        finally:
+            self._sync = was
+            if model is not None:
+                model._stage_hook = hook
+
+
+class GradReducer(_NoSync):
     """Sum-all-reduce of a flat gradient buffer after backward, in a few large buckets.  Works with any
     torch.distributed backend: RCCL on GPUs, gloo on CPU for tests."""
 
@@ -95,7 +121,7 @@ class GradReducer:
         return 1.0 / self.world
 
     def reduce(self, flat: torch.Tensor):
-        if self.world == 1:
+        if self.world == 1 or not self._sync:
             return
         works = [dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
                  for lo, hi in bucket_slices(flat.numel(), self.n_buckets)]
@@ -127,7 +153,7 @@ def stage_slices(model):
     return out
 
 
-class OverlappedGradReducer:
+class OverlappedGradReducer(_NoSync):
     """All-reduce each backward stage's gradient slice as soon as that stage is enqueued (see module docstring).
     Usage: r = OverlappedGradReducer(model); ...; loss.backward(); r.finish(); opt.step()."""
 
@@ -147,7 +173,7 @@ class OverlappedGradReducer:
         return 1.0 / self.world
 
     def _on_stage(self, stage: int):
-        if self.world == 1 and not self.force_collective:
+        if (self.world == 1 and not self.force_collective) or not self._sync:
             return
         lo, hi = self.slices[stage]
         self.works.append(_all_reduce_sum(self.model._gflat[lo:hi], self.group))
@@ -245,7 +271,7 @@ GradReducer.name = "allreduce-fp32-after-backward"
 GradReducer.attach = _ReducerBase.attach
 
 
-class Zero1Reducer(_ReducerBase):
+class Zero1Reducer(_NoSync, _ReducerBase):
     """Reduce-scatter + sharded optimiser + all-gather (ZeRO stage 1; SURVEY.md §8e "optional").
 
     Every backward stage's gradient slice [lo, hi) is cut into `world` equal parts; rank r receives the SUM of part r
@@ -309,7 +335,7 @@ class Zero1Reducer(_ReducerBase):
             dist.all_reduce(status, op=dist.ReduceOp.MAX, group=self.group)
 
     def _on_stage(self, stage: int):
-        if self.world == 1 and not self.force_collective:
+        if (self.world == 1 and not self.force_collective) or not self._sync:
             return
         lo, hi = self.slices[stage]
         g = self.model._gflat
@@ -447,6 +473,13 @@ class ShardedPassReducer(_ReducerBase):
     @property
     def grad_scale(self) -> float:
         return 1.0 / self.world
+
+    def no_sync(self):
+        """Not built: between the exchange and the Jacobian this reducer's gradient buffers hold raw sums, and accumulating there is
+        another scheme (the facade refuses an accumulating backward with the same message)."""
+        from .src.dit import SHARDED_ACCUMULATE_ERROR
+        from ._lib import MapditError
+        raise MapditError(SHARDED_ACCUMULATE_ERROR)
 
     def own(self, w):
         """[lo, hi) of the flat buffers: the rows of sharded weight `w` this rank owns."""

@@ -230,6 +230,11 @@ class _Runtime:
             pass
 
 
+SHARDED_ACCUMULATE_ERROR = ("gradient accumulation is not supported together with sharded weight passes (--grad-comm zero1w / zero1w-bf16, "
+                            "parallel.ShardedPassReducer): the gradient buffers hold raw sums between the exchange and the weight-norm "
+                            "Jacobian; use --grad-comm allreduce or zero1, or reset p.grad to None before every backward")
+
+
 class _DiTFunction(torch.autograd.Function):
     """Autograd node for the whole network.  Parameter gradients are written by the engine straight into the
     module's flat gradient buffer (``p.grad`` are views of it), so they are not returned to autograd.  With
@@ -264,16 +269,25 @@ class _DiTFunction(torch.autograd.Function):
             rt.lib.engine_backward(rt.handle, dout.data_ptr(), L.cur_stream())
             return None, None, dx, None, None, None
         accumulate = model._attach_grads()
-        keep = model._gflat.clone() if accumulate else None
+        if accumulate and getattr(model, "_shard", None) is not None:
+            raise L.MapditError(SHARDED_ACCUMULATE_ERROR)
+        # Gradient accumulation (p.grad still set from an earlier backward).  The bf16 / f16 engines add in place: every gradient writer of
+        # this backward runs in its accumulate form (mapdit_engine_set_grad_accumulate), no copy of the flat buffer, no extra pass over it.
+        # "bf16x3", the parity instrument, keeps a copy and adds it back.
+        in_engine = accumulate and rt.precision != "bf16x3"
+        keep = model._gflat.clone() if accumulate and not in_engine else None
         rt.bind(model)
         if dx is not None:
             rt.lib.engine_set_input_grad(rt.handle, dx.data_ptr(), 0)       # one-shot: consumed by the last stage below
+        if in_engine:
+            rt.lib.engine_set_grad_accumulate(rt.handle, 1)                 # one-shot too: consumed by the last stage, dropped by a forward
         hook = getattr(model, "_stage_hook", None)
         if hook is None:
             rt.lib.engine_backward(rt.handle, dout.data_ptr(), L.cur_stream())
         else:
-            # staged backward: after each stage the data-parallel reducer all-reduces the slice that stage finalised
-            assert keep is None, "gradient accumulation is not supported together with the overlapped DP reducer"
+            # staged backward: after each stage the data-parallel reducer all-reduces the slice that stage finalised (under accumulation:
+            # this rank's sum over the micro-steps - the earlier ones ran inside reducer.no_sync(), without an exchange)
+            assert keep is None, "gradient accumulation in bf16x3 precision is not supported together with the overlapped DP reducer"
             for stage in range(model.depth + 2):
                 rt.lib.engine_backward_stages(rt.handle, dout.data_ptr(), stage, stage, L.cur_stream())
                 hook(stage)

@@ -8,10 +8,12 @@
 Same arguments, defaults, schedule derivations, experiment directory layout (NNN-DiT-X-p/, config.yaml, log.txt,
 checkpoints/NNNNNNN.pt with {"model", "opt"}, ema/{std:.3f}_{t:07d}.pt fp16 snapshots) and log line as the reference.
 Added: --synthetic (N(0,1) latents, no dataset), the README's --use-* flags (accepted; the snapshot hard-wires all of
-them on, SURVEY F5 — turning one off is refused), and data parallelism when launched under torchrun (global batch =
---batch-size, sharded evenly; gradients summed over RCCL and averaged).
+them on, SURVEY F5 — turning one off is refused), data parallelism when launched under torchrun (global batch =
+--batch-size, sharded evenly; gradients summed over RCCL and averaged), and --grad-accum-steps K: one optimiser step over K
+micro-batches per rank (the activations of --batch-size / (world * K) samples are alive at a time).
 """
 import argparse
+import contextlib
 import math
 import os
 from glob import glob
@@ -111,6 +113,12 @@ def build_parser():
                    help="keep fewer activations for the backward and regenerate them block by block (bit-identical gradients): mlp = a "
                         "block's fc1 GEMM is issued again (24 instead of 40 x hidden bytes per token and block), block = the block's whole "
                         "forward (12); f16 / bf16 precisions")
+    p.add_argument("--grad-accum-steps", type=int, default=1,
+                   help="K > 1: an optimiser step is taken over K micro-batches - each rank's share of --batch-size is cut into K equal "
+                        "parts, forward and backward run once per part and the engine adds the gradients up in place (the first K - 1 "
+                        "parts without a gradient exchange).  Steps, schedules, checkpoints and steps/sec count optimiser steps; "
+                        "activation memory is that of one part.  Not with --grad-comm zero1w / zero1w-bf16 or --precision bf16x3 under "
+                        "data parallelism")
     for f in MP_FLAGS:
         p.add_argument(f"--use-{f}", dest="use_" + f.replace("-", "_"), action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--use-rotation-modulation", action=argparse.BooleanOptionalAction, default=False,
@@ -119,8 +127,25 @@ def build_parser():
     return p
 
 
+def micro_batch(batch_size: int, world: int, accum_steps: int) -> int:
+    """Samples of one forward: the per-rank share of the global batch (parallel.shard_batch) cut into `accum_steps` equal micro-batches.
+    Raises ValueError when either split is ragged."""
+    if accum_steps < 1:
+        raise ValueError(f"--grad-accum-steps must be >= 1, got {accum_steps}")
+    lo, hi = parallel.shard_batch(int(batch_size), 0, world)
+    if (hi - lo) % accum_steps:
+        raise ValueError(f"--grad-accum-steps {accum_steps} does not divide the per-rank batch {hi - lo} "
+                         f"(--batch-size {batch_size} over {world} rank(s)): micro-batches must be equal")
+    return (hi - lo) // accum_steps
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    K = int(args.grad_accum_steps)
+    micro = micro_batch(args.batch_size, int(os.environ.get("WORLD_SIZE", "1")), K)      # (fails here, before any device work)
+    if K > 1 and args.grad_comm in ("zero1w", "zero1w-bf16"):
+        raise NotImplementedError("--grad-accum-steps is not built for --grad-comm zero1w / zero1w-bf16 (sharded weight passes keep raw "
+                                  "gradient sums between the exchange and the Jacobian); use allreduce or zero1")
     # --no-use-forced-weight-normalization is the one off-path the snapshot's code defines (skip the in-place rewrite); the other seven are
     # built as restatements of their README lines (BUILT_OFF_FORMS, parity unpinned: the snapshot hard-wires every feature on, SURVEY F5)
     off = [f for f in MP_FLAGS if not getattr(args, "use_" + f.replace("-", "_"))
@@ -186,7 +211,10 @@ def main(argv=None):
     torch.manual_seed(args.seed + 1000003 * (rank + 1))
     reducer = parallel.make_reducer(model, args.grad_comm)
     opt = FusedAdamEMA(model, lr=args.lr, betas=(0.9, 0.99), ema_stds=(0.05, 0.1),
-                       lr_lambda=create_lr_lambda(args.num_lin_warmup, args.start_decay), grad_scale=reducer.grad_scale)
+                       lr_lambda=create_lr_lambda(args.num_lin_warmup, args.start_decay),
+                       # K micro-batches: every micro-loss is the plain mean of its micro-batch (the magnitude the automatic fp16 loss
+                       # scale is chosen for) and the gradients are SUMMED over the K backwards - the mean over them is taken here
+                       grad_scale=reducer.grad_scale if K == 1 else reducer.grad_scale / K)
     reducer.attach(opt)
 
     def batches():
@@ -206,10 +234,24 @@ def main(argv=None):
     train_steps, log_steps, running, start = 0, 0, torch.zeros((), device=dev), time()
     log(f"training for {args.num_steps} steps...")
     for x, y in batches():
-        t = torch.randint(0, diffusion.num_timesteps, (x.shape[0],), device=dev)
-        loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
-        opt.zero_grad()
-        loss.backward()
+        if K == 1:
+            t = torch.randint(0, diffusion.num_timesteps, (x.shape[0],), device=dev)
+            loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
+            opt.zero_grad()
+            loss.backward()
+        else:
+            # one optimiser step over K micro-batches: a fresh backward, then accumulating ones (p.grad stays set: the engine adds in place);
+            # only the last one exchanges gradients - its stages hand over this rank's sums over all K
+            opt.zero_grad()
+            loss = torch.zeros((), device=dev)
+            for k in range(K):
+                xk, yk = x[k * micro:(k + 1) * micro], y[k * micro:(k + 1) * micro]
+                t = torch.randint(0, diffusion.num_timesteps, (micro,), device=dev)              # each micro-batch draws its own
+                part = diffusion.training_losses(model, xk, t, dict(y=yk))["loss"].mean()        # NOT divided by K: see grad_scale above
+                with (reducer.no_sync() if k < K - 1 else contextlib.nullcontext()):
+                    part.backward()
+                loss = loss + part.detach()
+            loss = loss / K
         reducer.finish()
         opt.step()
         running += loss.detach()
