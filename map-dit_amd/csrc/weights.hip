@@ -391,34 +391,6 @@ __global__ __launch_bounds__(256) void grad_nonfinite_ranges_kernel(const float*
     }
 }
 
-#if 0
-    {
-        float4 P = *(float4*)(p + i), G = *(const float4*)(g + i), M = *(float4*)(m + i), V = *(float4*)(v + i);
-        float pp[4] = {P.x, P.y, P.z, P.w}, gg[4] = {G.x, G.y, G.z, G.w}, mm[4] = {M.x, M.y, M.z, M.w},
-              vv[4] = {V.x, V.y, V.z, V.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gk = gg[k] * gs;
-            mm[k] = b1 * mm[k] + (1.f - b1) * gk;
-            vv[k] = b2 * vv[k] + (1.f - b2) * gk * gk;
-            pp[k] -= step_size * mm[k] / (sqrtf(vv[k]) * inv_sqrt_bc2 + eps);
-        }
-        *(float4*)(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        *(float4*)(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        if (e1) {
-            float4 E = *(float4*)(e1 + i);
-            E.x += eb1 * (pp[0] - E.x); E.y += eb1 * (pp[1] - E.y); E.z += eb1 * (pp[2] - E.z); E.w += eb1 * (pp[3] - E.w);
-            *(float4*)(e1 + i) = E;
-        }
-        if (e2) {
-            float4 E = *(float4*)(e2 + i);
-            E.x += eb2 * (pp[0] - E.x); E.y += eb2 * (pp[1] - E.y); E.z += eb2 * (pp[2] - E.z); E.w += eb2 * (pp[3] - E.w);
-            *(float4*)(e2 + i) = E;
-        }
-    }
-#endif
-
 // Non-finite gradient guard (fp16 engine): any inf / NaN among the n gradients records `step` in status[0]; the first thread to do
 // so for this step also counts it in status[1].  Atomics run in the overflow case only (a finite step issues none).
 __global__ __launch_bounds__(256) void grad_nonfinite_kernel(const float* __restrict__ g, long n, int* __restrict__ status, int step) {
