@@ -225,6 +225,39 @@ int mapdit_adam_ema_step_ranges(float* params, const float* grads, float* exp_av
                                 float beta1, float beta2, float eps, const int* status, int step, void* stream);
 int mapdit_grad_nonfinite_check_ranges(const float* grads, const mapdit_range_t* ranges_dev, int nranges, long total_blocks, int* status,
                                        int step, void* stream);
+/* Global gradient-norm clipping on the device, fused into the step (additive within abi 5): torch.nn.utils.clip_grad_norm_(params, max_norm,
+ * norm_type=2) followed by the optimiser step, on the gradient the optimiser actually uses -
+ *     norm = |grad_scale| * sqrt(sum g^2)      coef = min(max_norm / (norm + 1e-6), 1)      the step uses g * grad_scale * coef
+ * - except that the gradient buffer is NOT rewritten.  Nothing is read back: the coefficient stays in device memory.
+ *   mapdit_grad_sqnorm / _ranges: a 256-thread workgroup owns 4,096 consecutive elements (of one range: the ownership, table and
+ *     total_blocks of mapdit_adam_ema_step_ranges) and writes partials[block] = its sum of g^2, an fp64.  Squares and sums are fp64 from the
+ *     first operation on, the order is fixed (thread, wave, the four waves through LDS), there are no atomics: two runs give the same bits,
+ *     and a finite gradient of 3e19 gives a finite norm.  n a multiple of 4, grads 16-byte aligned; partials holds ceil(n / 4096)
+ *     (total_blocks) doubles.
+ *   mapdit_grad_sqnorm_sum: one workgroup adds nblocks partials in a fixed order into sqsum[0] - the one double a sharded optimiser
+ *     (ZeRO-1) all-reduces(SUM) before mapdit_grad_clip_coef(sqsum, 1, ...).
+ *   mapdit_grad_clip_coef: one workgroup adds nblocks fp64 values in the same fixed order, evaluates the two formulas in fp64 and writes
+ *     clip[0] = (float)norm, clip[1] = (float)coef.  max_norm = +inf is legal (coef exactly 1: the call measures the norm); max_norm <= 0 or
+ *     NaN is an error.  An fp64 sum of fp32 squares is finite exactly when every gradient is, so this pass subsumes
+ *     mapdit_grad_nonfinite_check: with status != NULL (step > 0) a non-finite sum sets status[0] = step and increments status[1] unless
+ *     status[0] was step already - the contract of mapdit_grad_nonfinite_check, by one thread with plain stores.  With status == NULL the
+ *     outputs follow the formulas (NaN norm -> NaN coef, inf norm -> coef 0: torch with error_if_nonfinite=False).
+ *   mapdit_adam_ema_step_clipped / _ranges_clipped: mapdit_adam_ema_step_guarded / _ranges (status may be NULL in both) with the gradient
+ *     scale grad_scale * clip[1], ONE fp32 multiplication: with clip[1] == 1.0f the results are those of the existing entry points bit for
+ *     bit, otherwise those of the existing entry points called with grad_scale' = fp32(grad_scale * clip[1]). */
+int mapdit_grad_sqnorm(const float* grads, long n, double* partials, void* stream);
+int mapdit_grad_sqnorm_ranges(const float* grads, const mapdit_range_t* ranges_dev, int nranges, long total_blocks, double* partials,
+                              void* stream);
+int mapdit_grad_sqnorm_sum(const double* partials, long nblocks, double* sqsum, void* stream);
+int mapdit_grad_clip_coef(const double* partials, long nblocks, float grad_scale, float max_norm, float* clip /* {norm, coef} */,
+                          int* status /* may be NULL */, int step, void* stream);
+int mapdit_adam_ema_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema_a, float* ema_b, long n,
+                                 const mapdit_adam_scalars_t* hyper, float beta1, float beta2, float eps, const int* status /* may be NULL */,
+                                 int step, const float* clip, void* stream);
+int mapdit_adam_ema_step_ranges_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema_a, float* ema_b,
+                                        const mapdit_range_t* ranges_dev, int nranges, long total_blocks, const mapdit_adam_scalars_t* hyper,
+                                        float beta1, float beta2, float eps, const int* status /* may be NULL */, int step, const float* clip,
+                                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Token-stream kernels of the DiT block (src/utils.py:11-16, src/blocks/dit_block.py:33-36).

@@ -336,13 +336,17 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
                                                      float* __restrict__ m, float* __restrict__ v,
                                                      float* __restrict__ e1, float* __restrict__ e2, long n,
                                                      const float* __restrict__ hp, mapdit_adam_scalars_t hs, float b1,
-                                                     float b2, float eps, const int* __restrict__ status = nullptr, int step = 0) {
+                                                     float b2, float eps, const int* __restrict__ status = nullptr, int step = 0,
+                                                     const float* __restrict__ clip = nullptr) {
     // non-finite gradient guard: the check kernel recorded this step as bad - leave parameters, moments and EMA copies alone
     if (status && status[0] == step) return;
     // hyper-parameters of the step: by value (kernel arguments, nothing crosses PCIe) or, for a caller that replays one captured
     // launch with changing values, from a 5-float device buffer
     const float step_size = hp ? hp[0] : hs.step_size, inv_sqrt_bc2 = hp ? hp[1] : hs.inv_sqrt_bc2, eb1 = hp ? hp[2] : hs.ema_beta_a,
-                eb2 = hp ? hp[3] : hs.ema_beta_b, gs = hp ? hp[4] : hs.grad_scale;
+                eb2 = hp ? hp[3] : hs.ema_beta_b, gs0 = hp ? hp[4] : hs.grad_scale;
+    // global-norm clipping: the coefficient grad_clip_coef_kernel left on the device joins the gradient scale by ONE fp32
+    // multiplication - with clip[1] == 1 the step is the unclipped one bit for bit
+    const float gs = clip ? gs0 * clip[1] : gs0;
     long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const long stride = (long)gridDim.x * blockDim.x * 4;
     for (; i + 3 < n; i += stride) adam_ema_apply4(p, g, m, v, e1, e2, i, step_size, inv_sqrt_bc2, eb1, eb2, gs, b1, b2, eps);
@@ -353,8 +357,10 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
 __global__ __launch_bounds__(256) void adam_ema_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                             float* __restrict__ v, float* __restrict__ e1, float* __restrict__ e2,
                                                             const mapdit_range_t* __restrict__ ranges, int nranges, mapdit_adam_scalars_t hs,
-                                                            float b1, float b2, float eps, const int* __restrict__ status, int step) {
+                                                            float b1, float b2, float eps, const int* __restrict__ status, int step,
+                                                            const float* __restrict__ clip = nullptr) {
     if (status && status[0] == step) return;
+    const float gs = clip ? hs.grad_scale * clip[1] : hs.grad_scale;      // (as adam_ema_kernel)
     int lo = 0, hi = nranges - 1;
     const long blk = blockIdx.x;
     while (lo < hi) {
@@ -365,7 +371,7 @@ __global__ __launch_bounds__(256) void adam_ema_ranges_kernel(float* __restrict_
     const long base = r.lo + (blk - r.first_block) * 4096;
     const long end = base + 4096 < r.hi ? base + 4096 : r.hi;
     for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024)
-        adam_ema_apply4(p, g, m, v, e1, e2, i, hs.step_size, hs.inv_sqrt_bc2, hs.ema_beta_a, hs.ema_beta_b, hs.grad_scale, b1, b2, eps);
+        adam_ema_apply4(p, g, m, v, e1, e2, i, hs.step_size, hs.inv_sqrt_bc2, hs.ema_beta_a, hs.ema_beta_b, gs, b1, b2, eps);
 }
 
 // the non-finite check over the same ranges
@@ -405,6 +411,101 @@ __global__ __launch_bounds__(256) void grad_nonfinite_kernel(const float* __rest
     }
     if (bad) {
         if (atomicExch(&status[0], step) != step) atomicAdd(&status[1], 1);
+    }
+}
+
+// ---- global gradient norm (clip_grad_norm_, norm_type 2) ------------------------------------------------------------------------------
+// Sum of a 256-thread workgroup's fp64 values in a fixed order: across the wave (xor butterfly: every lane adds the same pairs), then the
+// four waves through LDS in wave order.  Valid in thread 0.  No atomics: two runs give the same bits.
+__device__ __forceinline__ double block_sum_f64(double v) {
+    __shared__ double wsum[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// Sum of squares of elements [base, end) (at most 4,096, end - base a multiple of 4) of one workgroup: squares and sums in fp64 from the
+// first operation on (the product of two fp32 values is exact there, and 3e19^2 does not overflow as it would in fp32).  The four
+// float4 loads of a thread are issued before the first is used.
+__device__ __forceinline__ double block_sqsum(const float* __restrict__ g, long base, long end) {
+    float4 x[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long i = base + threadIdx.x * 4 + k * 1024;
+        x[k] = i + 3 < end ? *(const float4*)(g + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double a = x[k].x, b = x[k].y, c = x[k].z, d = x[k].w;
+        acc += a * a;
+        acc += b * b;
+        acc += c * c;
+        acc += d * d;
+    }
+    return block_sum_f64(acc);
+}
+
+// partials[block] = sum of g^2 over the block's 4,096 consecutive elements of [0, n)
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ partials) {
+    const long base = (long)blockIdx.x * 4096;
+    const double s = block_sqsum(g, base, base + 4096 < n ? base + 4096 : n);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// the same over a range table: ownership and binary search of adam_ema_ranges_kernel
+__global__ __launch_bounds__(256) void grad_sqnorm_ranges_kernel(const float* __restrict__ g, const mapdit_range_t* __restrict__ ranges, int nranges,
+                                                               double* __restrict__ partials) {
+    int lo = 0, hi = nranges - 1;
+    const long blk = blockIdx.x;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (ranges[mid].first_block <= blk) lo = mid; else hi = mid - 1;
+    }
+    const mapdit_range_t r = ranges[lo];
+    const long base = r.lo + (blk - r.first_block) * 4096;
+    const double s = block_sqsum(g, base, base + 4096 < r.hi ? base + 4096 : r.hi);
+    if (threadIdx.x == 0) partials[blk] = s;
+}
+
+// One workgroup: thread t adds partials[t], partials[t + 256], ... in that order, then block_sum_f64.  Valid in thread 0.
+__device__ __forceinline__ double partials_sum(const double* __restrict__ partials, long nblocks) {
+    double acc = 0.0;
+    long i = threadIdx.x;
+    for (; i + 7 * 256 < nblocks; i += 8 * 256) {          // eight loads in flight (one workgroup reads 1 MB for DiT-B/2), added in index order
+        double t[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = partials[i + k * 256];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc += t[k];
+    }
+    for (; i < nblocks; i += 256) acc += partials[i];
+    return block_sum_f64(acc);
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_sum_kernel(const double* __restrict__ partials, long nblocks, double* __restrict__ sqsum) {
+    const double s = partials_sum(partials, nblocks);
+    if (threadIdx.x == 0) sqsum[0] = s;
+}
+
+// norm = |grad_scale| sqrt(sum), coef = min(max_norm / (norm + 1e-6), 1) in fp64 -> clip[0], clip[1] as fp32.  A NaN coefficient stays NaN
+// (the comparison is false), an infinite norm gives 0: torch's clip_grad_norm_ with error_if_nonfinite=False.  With `status` a non-finite
+// sum - an fp64 sum of fp32 squares is finite exactly when every gradient is - records the verdict of grad_nonfinite_kernel: one thread,
+// plain stores (the step kernels are later launches of the same stream).
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ partials, long nblocks, float grad_scale, float max_norm,
+                                                           float* __restrict__ clip, int* __restrict__ status, int step) {
+    const double s = partials_sum(partials, nblocks);
+    if (threadIdx.x != 0) return;
+    const double norm = fabs((double)grad_scale) * sqrt(s);
+    double coef = (double)max_norm / (norm + 1e-6);
+    if (coef > 1.0) coef = 1.0;
+    clip[0] = (float)norm;
+    clip[1] = (float)coef;
+    if (status && !(s - s == 0.0) && status[0] != step) {
+        status[0] = step;
+        status[1] += 1;
     }
 }
 
@@ -555,6 +656,78 @@ extern "C" int mapdit_grad_nonfinite_check(const float* grads, long n, int* stat
     MD_CHECK(n % 4 == 0 && ((uintptr_t)grads & 15) == 0, "grad_nonfinite_check: n=%ld must be a multiple of 4 and the buffer 16-byte aligned", n);
     const int grid = (int)((n / 4 + 255) / 256 < 2048 ? (n / 4 + 255) / 256 : 2048);
     hipLaunchKernelGGL(grad_nonfinite_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, grads, n, status, step);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+// ---- global gradient-norm clipping (mapdit.h) --------------------------------------------------------------------------------------------
+extern "C" int mapdit_grad_sqnorm(const float* grads, long n, double* partials, void* stream) {
+    MD_CHECK(grads && partials && n > 0, "grad_sqnorm: null/empty argument");
+    MD_CHECK(n % 4 == 0 && ((uintptr_t)grads & 15) == 0 && ((uintptr_t)partials & 7) == 0,
+             "grad_sqnorm: n=%ld must be a multiple of 4, the gradients 16-byte and the partial sums 8-byte aligned", n);
+    const long blocks = (n + 4095) / 4096;
+    MD_CHECK(blocks < (1l << 31), "grad_sqnorm: n=%ld needs too many workgroups", n);
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grads, n, partials);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_grad_sqnorm_ranges(const float* grads, const mapdit_range_t* ranges_dev, int nranges, long total_blocks, double* partials,
+                                         void* stream) {
+    MD_CHECK(grads && ranges_dev && partials && nranges > 0 && total_blocks > 0 && total_blocks < (1l << 31),
+             "grad_sqnorm_ranges: null/empty argument");
+    MD_CHECK(((uintptr_t)grads & 15) == 0 && ((uintptr_t)partials & 7) == 0,
+             "grad_sqnorm_ranges: the gradients must be 16-byte and the partial sums 8-byte aligned");
+    hipLaunchKernelGGL(grad_sqnorm_ranges_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, grads, ranges_dev, nranges,
+                       partials);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_grad_sqnorm_sum(const double* partials, long nblocks, double* sqsum, void* stream) {
+    MD_CHECK(partials && sqsum && nblocks > 0, "grad_sqnorm_sum: null/empty argument");
+    MD_CHECK((((uintptr_t)partials | (uintptr_t)sqsum) & 7) == 0, "grad_sqnorm_sum: the fp64 buffers must be 8-byte aligned");
+    hipLaunchKernelGGL(grad_sqnorm_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nblocks, sqsum);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_grad_clip_coef(const double* partials, long nblocks, float grad_scale, float max_norm, float* clip, int* status, int step,
+                                     void* stream) {
+    MD_CHECK(partials && clip && nblocks > 0, "grad_clip_coef: null/empty argument");
+    MD_CHECK(((uintptr_t)partials & 7) == 0 && ((uintptr_t)clip & 3) == 0, "grad_clip_coef: unaligned pointer");
+    MD_CHECK(max_norm > 0.f, "grad_clip_coef: max_norm=%g must be > 0 (+inf: measure only)", (double)max_norm);      // (false for NaN)
+    MD_CHECK(!status || step > 0, "grad_clip_coef: recording a verdict needs a step number > 0");
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nblocks, grad_scale, max_norm, clip, status,
+                       step);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_adam_ema_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema_a, float* ema_b,
+                                            long n, const mapdit_adam_scalars_t* hyper, float beta1, float beta2, float eps,
+                                            const int* status, int step, const float* clip, void* stream) {
+    MD_CHECK(params && grads && exp_avg && exp_avg_sq && hyper && n > 0, "adam_ema_step_clipped: null/empty argument");
+    MD_CHECK(n % 4 == 0, "adam_ema_step_clipped: n=%ld must be a multiple of 4 (pad the flat buffer)", n);
+    MD_CHECK(!status || step > 0, "adam_ema_step_clipped: the guarded form needs a step number > 0");
+    MD_CHECK(clip, "adam_ema_step_clipped: needs the clip words {norm, coef} of mapdit_grad_clip_coef");
+    const int grid = (int)((n / 4 + 255) / 256 < 4096 ? (n / 4 + 255) / 256 : 4096);
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, ema_a, ema_b, n, (const float*)nullptr, *hyper, beta1, beta2, eps, status, step, clip);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_adam_ema_step_ranges_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema_a,
+                                                   float* ema_b, const mapdit_range_t* ranges_dev, int nranges, long total_blocks,
+                                                   const mapdit_adam_scalars_t* hyper, float beta1, float beta2, float eps, const int* status,
+                                                   int step, const float* clip, void* stream) {
+    MD_CHECK(params && grads && exp_avg && exp_avg_sq && hyper && ranges_dev && nranges > 0 && total_blocks > 0 && total_blocks < (1l << 31),
+             "adam_ema_step_ranges_clipped: null/empty argument");
+    MD_CHECK(!status || step > 0, "adam_ema_step_ranges_clipped: the guarded form needs a step number > 0");
+    MD_CHECK(clip, "adam_ema_step_ranges_clipped: needs the clip words {norm, coef} of mapdit_grad_clip_coef");
+    hipLaunchKernelGGL(adam_ema_ranges_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
+                       ema_a, ema_b, ranges_dev, nranges, *hyper, beta1, beta2, eps, status, step, clip);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }

@@ -44,7 +44,7 @@ class FusedAdamEMA:
     """Adam + LR schedule + two EMA copies over the model's flat parameter / gradient buffers (one kernel launch)."""
 
     def __init__(self, model, lr: float = 1e-2, betas=(0.9, 0.99), eps: float = 1e-8, ema_stds=(0.05, 0.1),
-                 lr_lambda=None, grad_scale: float = 1.0, nonfinite_guard=None):
+                 lr_lambda=None, grad_scale: float = 1.0, nonfinite_guard=None, max_grad_norm: float | None = None):
         assert len(ema_stds) in (0, 2), "the fused kernel carries exactly two EMA copies (or none)"
         self.model = model
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -85,6 +85,20 @@ class FusedAdamEMA:
         self._stuck = 0
         self._poll_every_step = False                # set while refusals are occurring: poll after every step until one is applied
         self.status_sync = None                      # ZeRO-1: all-reduce(MAX) of the status words so that every rank refuses together
+        # Global gradient-norm clipping (mapdit.h, mapdit_grad_clip_coef): torch.nn.utils.clip_grad_norm_(params, max_grad_norm) followed by
+        # the step, on the gradient the optimiser uses - norm = |grad_scale| sqrt(sum g^2) (grad_scale carries 1 / world and 1 / K, so it is
+        # the norm of the averaged gradient), coef = min(max_grad_norm / (norm + 1e-6), 1), the step uses g * grad_scale * coef.  All of it
+        # on the device: one deterministic fp64 reduction over the flat gradient buffer, the coefficient read by the step kernels from
+        # device memory, nothing read back in step().  The ONE difference from torch's in-place clip: the gradient buffer is not
+        # rewritten - p.grad after step() still holds what the backward stored.  With the guard on, the reduction is the non-finite
+        # check too (an fp64 sum of fp32 squares is finite exactly when every gradient is): no second read of the buffer.
+        # None (default): not one launch differs from an optimiser without clipping; float("inf"): measure the norm, never clip.
+        self.max_grad_norm = max_grad_norm
+        self.norm_sync = None                        # ZeRO-1: all-reduce(SUM) of the one fp64 sum of squares (a rank holds its parts only)
+        self._clip_refused = None                    # set by a reducer whose shards cannot be normed (sharded weight passes): the message
+        self._clip = None                            # device {norm, coef} of the last clipped step (fp32)
+        self._sqsum = None                           # device fp64: the sum of squares that norm_sync all-reduces
+        self._partials = None                        # device fp64, one per 4,096-element workgroup
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.model.parameters():
@@ -100,6 +114,9 @@ class FusedAdamEMA:
         m = self.model
         assert m._gflat is not None, "no gradients: call backward() first"
         assert m._pflat.numel() == self.exp_avg.numel(), "the model was re-flattened after the optimiser was built"
+        clipping = self.max_grad_norm is not None
+        if clipping and self._clip_refused:
+            raise L.MapditError(self._clip_refused)
         lr = self.current_lr()                       # LambdaLR: lr for optimiser step k uses lambda(k), k from 0
         self.step_count += 1
         self._launches += 1
@@ -112,7 +129,13 @@ class FusedAdamEMA:
         guard = self.nonfinite_guard
         if guard is None:
             guard = getattr(m, "gemm_precision", "bf16") == "f16"
-        if guard:
+        clip = None
+        if clipping:
+            # the norm pass is the non-finite check as well: with the guard it records the verdict, and no grad_nonfinite_check is launched
+            clip = self._clip_coefficient(launch if guard else 0, guard)
+            if guard and self.status_sync is not None and self.norm_sync is None:
+                self.status_sync(self._status)       # (with norm_sync every rank has seen the same sum and recorded the same verdict)
+        elif guard:
             with torch.cuda.device(m._pflat.device):
                 live = [(lo, hi) for lo, hi in self.shards if hi > lo]
                 if len(live) > 8:
@@ -142,10 +165,14 @@ class FusedAdamEMA:
             # many ranges (sharded weight passes: a rank's rows of every weight + the replicated rest): ONE launch over a device table
             tab, nblk = self._range_table([(lo, hi) for lo, hi, _ in segs])
             with torch.cuda.device(m._pflat.device):
-                L.lib().adam_ema_step_ranges(m._pflat.data_ptr(), m._gflat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                             self.ema[0].data_ptr() if self.ema else None, self.ema[1].data_ptr() if self.ema else None,
-                                             tab.data_ptr(), len(segs), nblk, C.byref(hyper), b1, b2, self.eps,
-                                             self._status.data_ptr() if guard else None, launch if guard else 0, L.cur_stream())
+                args = (m._pflat.data_ptr(), m._gflat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                        self.ema[0].data_ptr() if self.ema else None, self.ema[1].data_ptr() if self.ema else None,
+                        tab.data_ptr(), len(segs), nblk, C.byref(hyper), b1, b2, self.eps,
+                        self._status.data_ptr() if guard else None, launch if guard else 0)
+                if clip is not None:
+                    L.lib().adam_ema_step_ranges_clipped(*args, clip.data_ptr(), L.cur_stream())
+                else:
+                    L.lib().adam_ema_step_ranges(*args, L.cur_stream())
             segs = []
         for lo, hi, with_ema in segs:
             if hi <= lo:
@@ -156,7 +183,10 @@ class FusedAdamEMA:
                 args = (m._pflat.data_ptr() + off, m._gflat.data_ptr() + off, self.exp_avg.data_ptr() + off,
                         self.exp_avg_sq.data_ptr() + off, ema[0].data_ptr() + off if ema else None,
                         ema[1].data_ptr() + off if ema else None, hi - lo, C.byref(hyper), b1, b2, self.eps)
-                if guard:
+                if clip is not None:
+                    L.lib().adam_ema_step_clipped(*args, self._status.data_ptr() if guard else None, launch if guard else 0,
+                                                  clip.data_ptr(), L.cur_stream())
+                elif guard:
                     L.lib().adam_ema_step_guarded(*args, self._status.data_ptr(), launch, L.cur_stream())
                 else:
                     L.lib().adam_ema_step_scalars(*args, L.cur_stream())
@@ -178,6 +208,59 @@ class FusedAdamEMA:
                 blk += (hi - lo + 4095) // 4096
             self._range_cache = (key, torch.tensor(rows, dtype=torch.int64, device=self.model._pflat.device), blk)
         return self._range_cache[1], self._range_cache[2]
+
+    # ---- global gradient-norm clipping ----------------------------------------------------------------------------
+    def _clip_coefficient(self, launch: int, guard: bool):
+        """grad_sqnorm over this rank's shards (the single-range form for at most 8 live ranges, the table form above that, as the guard
+        chooses) -> [grad_sqnorm_sum -> norm_sync ->] grad_clip_coef; returns the device {norm, coef} the step kernels read."""
+        m = self.model
+        g = m._gflat.data_ptr()
+        live = [(lo, hi) for lo, hi in self.shards if hi > lo]
+        nblk = sum((hi - lo + 4095) // 4096 for lo, hi in live)
+        if self._clip is None:
+            self._clip = torch.zeros(2, dtype=torch.float32, device=m._pflat.device)
+            self._sqsum = torch.zeros(1, dtype=torch.float64, device=m._pflat.device)
+        if self._partials is None or self._partials.numel() < max(nblk, 1):
+            self._partials = torch.zeros(max(nblk, 1), dtype=torch.float64, device=m._pflat.device)
+        partials = self._partials.data_ptr()
+        status = self._status.data_ptr() if guard else None
+        with torch.cuda.device(m._pflat.device):
+            if len(live) > 8:
+                tab, tblk = self._range_table(live)
+                assert tblk == nblk
+                L.lib().grad_sqnorm_ranges(g, tab.data_ptr(), len(live), nblk, partials, L.cur_stream())
+            else:
+                blk = 0
+                for lo, hi in live:
+                    assert lo % 4 == 0 and hi % 4 == 0
+                    L.lib().grad_sqnorm(g + lo * 4, hi - lo, partials + blk * 8, L.cur_stream())
+                    blk += (hi - lo + 4095) // 4096
+            nblk = max(nblk, 1)                      # (a rank without a live range: the one zero the buffer was created with)
+            if self.norm_sync is not None:
+                L.lib().grad_sqnorm_sum(partials, nblk, self._sqsum.data_ptr(), L.cur_stream())
+                self.norm_sync(self._sqsum)
+                L.lib().grad_clip_coef(self._sqsum.data_ptr(), 1, self.grad_scale, self.max_grad_norm, self._clip.data_ptr(), status, launch,
+                                       L.cur_stream())
+            else:
+                L.lib().grad_clip_coef(partials, nblk, self.grad_scale, self.max_grad_norm, self._clip.data_ptr(), status, launch,
+                                       L.cur_stream())
+        return self._clip
+
+    def clip_values(self):
+        """(grad_norm(), clip_coef()) of the last step() with max_grad_norm set, in ONE read-back (synchronises: logging cadence)."""
+        if self._clip is None:
+            raise RuntimeError("no clipped step yet: max_grad_norm is None or step() has not run")
+        norm, coef = self._clip.tolist()
+        return norm, coef
+
+    def grad_norm(self) -> float:
+        """Global gradient norm |grad_scale| sqrt(sum g^2) of the last step() with max_grad_norm set (synchronises: call at logging
+        cadence, like overflow_steps()).  A refused step keeps its value readable: it is inf or NaN then."""
+        return self.clip_values()[0]
+
+    def clip_coef(self) -> float:
+        """min(max_grad_norm / (norm + 1e-6), 1) of the last step() with max_grad_norm set (synchronises: logging cadence)."""
+        return self.clip_values()[1]
 
     # ---- non-finite gradient guard ------------------------------------------------------------------------------
     def overflow_steps(self) -> int:

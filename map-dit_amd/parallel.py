@@ -321,6 +321,19 @@ class Zero1Reducer(_NoSync, _ReducerBase):
                 # non-finite guard: a rank checks the gradients of its own parts only - every rank must refuse the step together
                 # (status[0] = last bad step: MAX makes it the current step everywhere if any rank flagged it)
                 opt.status_sync = self._sync_status
+                # gradient-norm clipping (FusedAdamEMA.max_grad_norm): a rank holds the reduced gradient of its own parts only - the
+                # global norm is the all-reduced sum of the ranks' sums of squares, one fp64
+                opt.norm_sync = self._sync_sqsum
+
+    def _sync_sqsum(self, sqsum):
+        # as _sync_status: device-side on RCCL, through the host under a host-staged (gloo) group.  Every rank receives the same bits, so
+        # norm, coefficient and - for a non-finite sum - the refusal are the same everywhere without a second collective.
+        if _host_staged(self.group, sqsum):
+            h = sqsum.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+            sqsum.copy_(h)
+        else:
+            dist.all_reduce(sqsum, op=dist.ReduceOp.SUM, group=self.group)
 
     def _sync_status(self, status):
         # RCCL: one 8-byte device-side all-reduce per step, nothing read back.  A host-staged group (gloo: the CPU rehearsal of the
@@ -390,6 +403,8 @@ class Zero1Reducer(_NoSync, _ReducerBase):
 
 _SHARDED_SUFFIXES = ("attn.qkv_proj.weight", "attn.out_proj.weight", "mlp.net.0.weight", "mlp.net.2.weight", "modulation.1.weight")
 _B_OF = {"attn.qkv_proj.weight": 0, "attn.out_proj.weight": 1, "mlp.net.0.weight": 2, "mlp.net.2.weight": 3, "modulation.1.weight": 4}   # mapdit.h MAPDIT_B_*
+SHARDED_CLIP_ERROR = ("max_grad_norm (global gradient-norm clipping) is not built for sharded weight passes (--grad-comm zero1w / zero1w-bf16): "
+                      "a rank's shards mix owned rows with replicated ranges; use allreduce or zero1")
 
 
 class ShardedPassReducer(_ReducerBase):
@@ -492,6 +507,12 @@ class ShardedPassReducer(_ReducerBase):
         return sorted(out)
 
     def attach(self, opt):
+        # gradient-norm clipping is not built here: this rank's shards mix its rows of the sharded weights with the replicated ranges, and
+        # a sum over ranks would count the replicated ones `world` times.  Refused by name, now and at step() if max_grad_norm is set later.
+        opt._clip_refused = SHARDED_CLIP_ERROR
+        if opt.max_grad_norm is not None:
+            from ._lib import MapditError
+            raise MapditError(SHARDED_CLIP_ERROR)
         self.opt = opt
         if self.world > 1:
             opt.shards = self.parts()

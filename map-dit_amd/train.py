@@ -10,7 +10,8 @@ checkpoints/NNNNNNN.pt with {"model", "opt"}, ema/{std:.3f}_{t:07d}.pt fp16 snap
 Added: --synthetic (N(0,1) latents, no dataset), the README's --use-* flags (accepted; the snapshot hard-wires all of
 them on, SURVEY F5 — turning one off is refused), data parallelism when launched under torchrun (global batch =
 --batch-size, sharded evenly; gradients summed over RCCL and averaged), and --grad-accum-steps K: one optimiser step over K
-micro-batches per rank (the activations of --batch-size / (world * K) samples are alive at a time).
+micro-batches per rank (the activations of --batch-size / (world * K) samples are alive at a time), and --max-grad-norm F: global
+gradient-norm clipping on the device, fused into the optimiser step (optim.FusedAdamEMA.max_grad_norm).
 """
 import argparse
 import contextlib
@@ -119,6 +120,10 @@ def build_parser():
                         "parts without a gradient exchange).  Steps, schedules, checkpoints and steps/sec count optimiser steps; "
                         "activation memory is that of one part.  Not with --grad-comm zero1w / zero1w-bf16 or --precision bf16x3 under "
                         "data parallelism")
+    p.add_argument("--max-grad-norm", type=float, default=None,
+                   help="clip the global gradient norm (torch.nn.utils.clip_grad_norm_ semantics on the averaged gradient) on the device, "
+                        "fused into the optimiser step; `inf` only measures.  The log line gains the norm and the coefficient of the step "
+                        "it is written at.  Not with --grad-comm zero1w / zero1w-bf16")
     for f in MP_FLAGS:
         p.add_argument(f"--use-{f}", dest="use_" + f.replace("-", "_"), action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--use-rotation-modulation", action=argparse.BooleanOptionalAction, default=False,
@@ -214,7 +219,8 @@ def main(argv=None):
                        lr_lambda=create_lr_lambda(args.num_lin_warmup, args.start_decay),
                        # K micro-batches: every micro-loss is the plain mean of its micro-batch (the magnitude the automatic fp16 loss
                        # scale is chosen for) and the gradients are SUMMED over the K backwards - the mean over them is taken here
-                       grad_scale=reducer.grad_scale if K == 1 else reducer.grad_scale / K)
+                       grad_scale=reducer.grad_scale if K == 1 else reducer.grad_scale / K,
+                       max_grad_norm=args.max_grad_norm)
     reducer.attach(opt)
 
     def batches():
@@ -268,7 +274,10 @@ def main(argv=None):
                 torch.distributed.all_reduce(avg)
                 avg /= world
             sps = log_steps / (time() - start)
-            log(f"(step={train_steps:07d}) train loss: {avg.item():.4f}, train steps/sec: {sps:.2f}")
+            clip_msg = ""
+            if args.max_grad_norm is not None:   # the values of this step: one read-back per log line
+                clip_msg = ", grad norm: {:.4f}, clip: {:.3f}".format(*opt.clip_values())
+            log(f"(step={train_steps:07d}) train loss: {avg.item():.4f}, train steps/sec: {sps:.2f}{clip_msg}")
             running.zero_()
             log_steps, start = 0, time()
         if train_steps % args.ckpt_every == 0 or (args.ema_snapshot_every and train_steps % args.ema_snapshot_every == 0):
