@@ -457,7 +457,7 @@ int mapdit_cond_combine_fwd(const float* temb, const float* table, const int64_t
 int mapdit_cond_combine_bwd(const float* c, const float* dcs, const float* dcd, const int64_t* y, uint16_t* dtemb,
                             float* dtable, int n, int D, int table_rows, void* stream);
 /* Synchronises `stream`, returns MAPDIT_ERR_ARG (with a message naming the index kind) if any kernel since the last poll saw an
- * out-of-range label or timestep, and clears the record.  Not capturable: call it outside hipGraph capture. */
+ * out-of-range label or timestep (or a schedule sampler weight that is not positive and finite), and clears the record.  Not capturable: call it outside hipGraph capture. */
 int mapdit_device_error_poll(void* stream);
 int mapdit_final_out_fwd(const float* lin, int ldl, const float* a_mean, const float* a_sigma, const float* ref_mean,
                          const float* ref_sigma, float* out, int N, int C, int S, int p, void* stream);
@@ -563,6 +563,34 @@ int mapdit_obj_vb_terms(const float* model_out, const float* x0, const float* xt
 /* _prior_bpd (:789-803) [N]; with vb [N][nsteps] given, total [N] = sum over t of vb + prior (calc_bpd_loop's total_bpd). */
 int mapdit_prior_bpd(const float* x0, const float* tab, const float* otab, int nsteps, const float* vb, float* prior, float* total,
                      int N, int per_sample, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Loss-aware timestep sampling (diffusion/timestep_sampler.py), additive within abi 5.  The state of LossSecondMomentResampler
+ * lives on the device - hist fp64 [T][H] (a row = the last H losses of its timestep, oldest first: the reference's layout),
+ * counts int32 [T], prob / cdf fp64 [T] - and nothing is read back.  Every value that decides a probability is fp64, every sum
+ * has a fixed order, there are no atomics: two runs give the same bits.  Everything that changes from step to step is a device
+ * pointer.  1 <= T <= 16,384, 1 <= H <= 64, any N, M >= 1.
+ *   mapdit_tsampler_update: update_with_all_losses (:139-147) over the M entries (ts int64, losses fp32) in index order; several
+ *     entries of one batch may name the same timestep.  Two deviations: an entry with t outside [0, T) is skipped and recorded for
+ *     mapdit_device_error_poll (the reference indexes numpy with it); an entry whose loss is inf / NaN is skipped (the reference
+ *     stores it, and weights() is NaN until H further losses of that timestep arrived).
+ *   mapdit_tsampler_prepare: weights() (:130-137) and the table of sample() (:53-54).  warmed = all(counts == H), decided on the
+ *     device.  Warmed: w_i = sqrt(mean_j hist[i][j]^2), prob = w / sum(w) * (1 - uniform_prob) + uniform_prob / T; not warmed, or
+ *     sum(w) zero or not finite (the reference raises inside numpy): prob = 1 / T.  cdf = cumsum(prob) / cumsum(prob)[T - 1], the
+ *     table np.random.choice(p=prob) builds; cdf[T - 1] is exactly 1.  One workgroup.
+ *   mapdit_tsampler_prepare_weights: prob = weights / sum(weights) and the same cdf from a caller's fp64 weights [T] (a subclass
+ *     that overrides weights()).  A weight that is <= 0 or not finite is recorded for mapdit_device_error_poll and gives the
+ *     uniform table.  weights must not alias prob / cdf.
+ *   mapdit_tsampler_draw: for uniforms u [N] fp64 in [0, 1): t_out[i] = min(#{k : cdf[k] <= u[i]}, T - 1) by binary search
+ *     (searchsorted(cdf, u, side="right"), np.random.choice's draw) as int64, w_out[i] = (float)(1 / (T prob[t])) (:57-58), the
+ *     quotient taken in fp64.
+ * ------------------------------------------------------------------------------------------------------------ */
+int mapdit_tsampler_update(double* hist, int* counts, int T, int H, const int64_t* ts, const float* losses, long M, void* stream);
+int mapdit_tsampler_prepare(const double* hist, const int* counts, int T, int H, double uniform_prob, double* prob, double* cdf,
+                            void* stream);
+int mapdit_tsampler_prepare_weights(const double* weights, int T, double* prob, double* cdf, void* stream);
+int mapdit_tsampler_draw(const double* prob, const double* cdf, int T, const double* u, int64_t* t_out, float* w_out, long N,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Engine: the whole DiT forward / backward sequenced from C++ on one stream (src/dit.py:70-105 and its autograd).

@@ -124,6 +124,8 @@ __device__ __forceinline__ float dmpsilu_f(float x) {
 // the poll entry point ORs them together.
 #define MAPDIT_DEVERR_LABEL 1
 #define MAPDIT_DEVERR_TIMESTEP 2
+#define MAPDIT_DEVERR_WEIGHT 4       /* a schedule sampler weight that is <= 0 or not finite (timestep_sampler.hip) */
+#define MAPDIT_DEVERR_SAMPLER_T 8    /* a timestep outside [0, T) in a loss-history update: the entry was skipped, not clamped */
 #define MAPDIT_DEFINE_DEV_ERROR(TU)                                                                    \
     __device__ int g_dev_error_##TU = 0;                                                               \
     int mapdit_dev_error_take_##TU(hipStream_t st, int* out) {                                         \
@@ -148,6 +150,7 @@ int mapdit_dev_error_take_embed(hipStream_t st, int* out);
 int mapdit_dev_error_take_embed_f16(hipStream_t st, int* out);
 int mapdit_dev_error_take_diffusion(hipStream_t st, int* out);
 int mapdit_dev_error_take_precise(hipStream_t st, int* out);
+int mapdit_dev_error_take_tsampler(hipStream_t st, int* out);
 
 // Error plumbing shared by the C-ABI entry points (thread-local last-error string).
 void mapdit_set_error(const char* fmt, ...);

@@ -11,7 +11,9 @@ Added: --synthetic (N(0,1) latents, no dataset), the README's --use-* flags (acc
 them on, SURVEY F5 — turning one off is refused), data parallelism when launched under torchrun (global batch =
 --batch-size, sharded evenly; gradients summed over RCCL and averaged), and --grad-accum-steps K: one optimiser step over K
 micro-batches per rank (the activations of --batch-size / (world * K) samples are alive at a time), and --max-grad-norm F: global
-gradient-norm clipping on the device, fused into the optimiser step (optim.FusedAdamEMA.max_grad_norm).
+gradient-norm clipping on the device, fused into the optimiser step (optim.FusedAdamEMA.max_grad_norm), and --schedule-sampler
+loss-second-moment: improved-DDPM's loss-aware timestep resampling with importance weights, state and draw on the device
+(diffusion/timestep_sampler.py; the checkpoint then gains a "schedule_sampler" key).
 """
 import argparse
 import contextlib
@@ -25,6 +27,7 @@ import yaml
 
 from . import parallel
 from .diffusion import create_diffusion
+from .diffusion.timestep_sampler import create_named_schedule_sampler
 from .optim import FusedAdamEMA, create_lr_lambda
 from .src.models import DIT_MODELS
 
@@ -124,6 +127,11 @@ def build_parser():
                    help="clip the global gradient norm (torch.nn.utils.clip_grad_norm_ semantics on the averaged gradient) on the device, "
                         "fused into the optimiser step; `inf` only measures.  The log line gains the norm and the coefficient of the step "
                         "it is written at.  Not with --grad-comm zero1w / zero1w-bf16")
+    p.add_argument("--schedule-sampler", choices=["uniform", "loss-second-moment"], default="uniform",
+                   help="how a step draws its timesteps: uniform (default: torch.randint, the reference's train.py) or loss-second-moment "
+                        "(diffusion/timestep_sampler.py: p(t) follows the second moment of each timestep's last 10 losses once every "
+                        "timestep has 10, the loss is weighted by 1 / (T p(t)); history, table and draw stay on the device, ranks share one "
+                        "history).  Individual weights reach 1 / uniform_prob = 1000 in the worst case: see INTEGRATION.md on --precision f16")
     for f in MP_FLAGS:
         p.add_argument(f"--use-{f}", dest="use_" + f.replace("-", "_"), action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--use-rotation-modulation", action=argparse.BooleanOptionalAction, default=False,
@@ -222,6 +230,15 @@ def main(argv=None):
                        grad_scale=reducer.grad_scale if K == 1 else reducer.grad_scale / K,
                        max_grad_norm=args.max_grad_norm)
     reducer.attach(opt)
+    # the default draws with torch.randint below, exactly as before; the sampler object exists only with the flag
+    t_sampler = create_named_schedule_sampler(args.schedule_sampler, diffusion) if args.schedule_sampler != "uniform" else None
+
+    def weighted_loss(xb, yb):
+        """Mean over the batch of weight x loss at timesteps drawn by the schedule sampler; the history takes the unweighted losses."""
+        t, w = t_sampler.sample(xb.shape[0], dev)
+        losses = diffusion.training_losses(model, xb, t, dict(y=yb))
+        t_sampler.update_with_local_losses(t, losses["loss"].detach())
+        return (losses["loss"] * w).mean()
 
     def batches():
         if loader is None:
@@ -241,8 +258,11 @@ def main(argv=None):
     log(f"training for {args.num_steps} steps...")
     for x, y in batches():
         if K == 1:
-            t = torch.randint(0, diffusion.num_timesteps, (x.shape[0],), device=dev)
-            loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
+            if t_sampler is None:
+                t = torch.randint(0, diffusion.num_timesteps, (x.shape[0],), device=dev)
+                loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
+            else:
+                loss = weighted_loss(x, y)
             opt.zero_grad()
             loss.backward()
         else:
@@ -252,8 +272,11 @@ def main(argv=None):
             loss = torch.zeros((), device=dev)
             for k in range(K):
                 xk, yk = x[k * micro:(k + 1) * micro], y[k * micro:(k + 1) * micro]
-                t = torch.randint(0, diffusion.num_timesteps, (micro,), device=dev)              # each micro-batch draws its own
-                part = diffusion.training_losses(model, xk, t, dict(y=yk))["loss"].mean()        # NOT divided by K: see grad_scale above
+                if t_sampler is None:
+                    t = torch.randint(0, diffusion.num_timesteps, (micro,), device=dev)          # each micro-batch draws its own
+                    part = diffusion.training_losses(model, xk, t, dict(y=yk))["loss"].mean()    # NOT divided by K: see grad_scale above
+                else:
+                    part = weighted_loss(xk, yk)
                 with (reducer.no_sync() if k < K - 1 else contextlib.nullcontext()):
                     part.backward()
                 loss = loss + part.detach()
@@ -283,8 +306,10 @@ def main(argv=None):
         if train_steps % args.ckpt_every == 0 or (args.ema_snapshot_every and train_steps % args.ema_snapshot_every == 0):
             reducer.gather_state()               # ZeRO-1: Adam moments / EMA copies are sharded; complete them (collective)
         if rank == 0 and train_steps % args.ckpt_every == 0:
-            torch.save({"model": model.state_dict(), "opt": opt.state_dict()},                 # reference train.py:125-132
-                       os.path.join(exp, "checkpoints", f"{train_steps:07d}.pt"))
+            ckpt = {"model": model.state_dict(), "opt": opt.state_dict()}                      # reference train.py:125-132
+            if t_sampler is not None:
+                ckpt["schedule_sampler"] = t_sampler.state_dict()
+            torch.save(ckpt, os.path.join(exp, "checkpoints", f"{train_steps:07d}.pt"))
         if rank == 0 and args.ema_snapshot_every and train_steps % args.ema_snapshot_every == 0:
             for std in opt.ema_stds:                                   # reference src/ema.py:143-155
                 sd = {k: v.cpu().half() for k, v in opt.ema_state_dict(std).items()}
