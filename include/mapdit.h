@@ -593,6 +593,44 @@ int mapdit_tsampler_draw(const double* prob, const double* cdf, int T, const dou
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Rectified flow (the linear-interpolant / flow-matching velocity objective of SiT and SD3; not in the reference), additive
+ * within abi 5.  Timestep index k in [0, T) stands for flow time sig[k] (fp32 [T], strictly increasing in (0, 1], sig[T-1] = 1 =
+ * pure noise; built on the host in fp64 and uploaded once):
+ *     x_s = (1 - s) x0 + s eps,    velocity dx/ds = eps - x0,    x0 = x_s - s v.
+ * The model predicts the velocity on its first C output channels; `groups` = 1 (C channels) or 2 (2C: the second C are ignored
+ * and receive an exactly zero gradient).  fp32, 1 <= T <= 16,384; a timestep outside [0, T) is clamped and recorded for
+ * mapdit_device_error_poll.  Where per_sample % 4 == 0 and the tensors are 16-byte aligned the kernels move 16 bytes per lane.
+ *   mapdit_flow_q_sample: xt = (1 - sig[t]) x0 + sig[t] noise; xt overlaps neither input.
+ *   mapdit_flow_loss_fwd: loss [N] = mean over the sample of (v - (noise - x0))^2 (one block per sample, fixed summation order);
+ *     G (model_out's shape) = d loss / d model_out = 2 (v - (noise - x0)) / per_sample on the first C channels and zeros, written,
+ *     on the rest.  The target does not depend on t: no table is read.  The backward is mapdit_obj_loss_bwd(G, g_loss, NULL, NULL,
+ *     dout, N, per_sample, groups, stream).
+ *   mapdit_flow_draw_timesteps: the logit-normal timestep density (SD3): t_out[i] = min(floor(sigmoid(loc + scale z[i]) T), T - 1)
+ *     for standard normal draws z fp64 [N], evaluated in fp64 without fused multiply-add.  loc finite, scale finite and > 0.  A NaN
+ *     z draws index 0 and is recorded under the timestep kind.
+ *   mapdit_flow_step: one model evaluation of the Euler / Heun sampler.  The plan is J rows (tau int64 [J]: the timestep the model
+ *     was evaluated at; ctab fp32 [J][2] = (c_h, c_v); flags int32 [J], bit 0 = predictor row), built on the host in fp64; step [N]
+ *     int64 on the device names each sample's row (the evaluation with `step` more to follow runs row `step`: a captured graph
+ *     decrements it between replays).  A step outside [0, J) is clamped and recorded.  With v = the first C channels of model_out:
+ *         out = base + c_h hist + c_v v;    sample <- out
+ *         predictor row:    hist <- v, base kept           (Heun: c_h = 0, c_v = h;  out is the Euler point the corrector evaluates)
+ *         committing row:   base_out <- out (nullable)     (Euler: c_h = 0, c_v = h;  Heun corrector: c_h = c_v = h / 2)
+ *         pred_xstart <- x_eval - sig[tau[row]] v          (nullable; needs x_eval, the point the model was evaluated at)
+ *     with h = s_b - s_a < 0 the step of flow time.  hist is read only where c_h != 0.  Every element is read, then written, by the
+ *     same thread: sample may be base itself on a committing row (on a predictor row that would destroy the base: the caller knows its
+ *     plan), base_out may be base, x_eval may be base or sample; hist and pred_xstart overlap nothing, and no partial overlap is
+ *     accepted anywhere.
+ * ------------------------------------------------------------------------------------------------------------ */
+int mapdit_flow_q_sample(const float* x0, const float* noise, const int64_t* t, const float* sig, int T, float* xt, int N,
+                         int per_sample, void* stream);
+int mapdit_flow_loss_fwd(const float* model_out, const float* x0, const float* noise, float* loss, float* G, int N, int per_sample,
+                         int groups, void* stream);
+int mapdit_flow_draw_timesteps(const double* z, double loc, double scale, int T, int64_t* t_out, long N, void* stream);
+int mapdit_flow_step(const float* model_out, const float* x_eval, const float* base, float* hist, const int64_t* step,
+                     const int64_t* tau, const float* ctab, const int* flags, int J, const float* sig, int T, float* sample,
+                     float* base_out, float* pred_xstart, int N, int per_sample, int groups, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Engine: the whole DiT forward / backward sequenced from C++ on one stream (src/dit.py:70-105 and its autograd).
  * ------------------------------------------------------------------------------------------------------------ */
 enum { MAPDIT_OFF_MP_SILU = 1, MAPDIT_OFF_MP_RESIDUAL = 2, MAPDIT_OFF_MP_POS_ENC = 4, MAPDIT_OFF_MP_EMBEDDING = 8,

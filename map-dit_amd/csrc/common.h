@@ -151,6 +151,7 @@ int mapdit_dev_error_take_embed_f16(hipStream_t st, int* out);
 int mapdit_dev_error_take_diffusion(hipStream_t st, int* out);
 int mapdit_dev_error_take_precise(hipStream_t st, int* out);
 int mapdit_dev_error_take_tsampler(hipStream_t st, int* out);
+int mapdit_dev_error_take_flow(hipStream_t st, int* out);
 
 // Error plumbing shared by the C-ABI entry points (thread-local last-error string).
 void mapdit_set_error(const char* fmt, ...);

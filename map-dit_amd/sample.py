@@ -40,6 +40,7 @@ def main(argv=None):
         torch.manual_seed(args.seed)
     device = torch.device("cuda")
     train_args = S.load_train_args(args.result_dir)
+    S.check_objective(args.sampler, train_args)                           # a velocity model and a diffusion sampler (or the reverse): refused here
     model = get_model(train_args).to(device)
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=True)
     model.gemm_precision = args.precision
@@ -52,7 +53,7 @@ def main(argv=None):
     y = torch.tensor([args.class_label] * n, device=device)
     z = torch.cat([z, z], dim=0)                                          # CFG batch: conditional | null class
     y = torch.cat([y, torch.tensor([train_args["num_classes"]] * n, device=device)], dim=0)
-    diffusion, solver = S.make_diffusion(args)
+    diffusion, solver = S.make_diffusion(args, train_args)
     samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=not args.no_graph, progress=True, **solver)
     samples, _ = samples.chunk(2, dim=0)
     samples = S.denormalize(samples, train_args)

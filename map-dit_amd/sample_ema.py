@@ -36,10 +36,11 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     device = torch.device("cuda")
     train_args = S.load_train_args(args.result_dir)
+    S.check_objective(args.sampler, train_args)                           # a velocity model and a diffusion sampler (or the reverse): refused here
     model = get_model(train_args).to(device).eval()
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device) if args.use_vae else None
-    diffusion, solver = S.make_diffusion(args)
+    diffusion, solver = S.make_diffusion(args, train_args)
     n = 8
     shape = (2 * n, train_args["in_channels"], train_args["input_size"], train_args["input_size"])
     if not 0 <= args.class_label < int(train_args["num_classes"]):       # the reference fails inside F.embedding (IndexError)

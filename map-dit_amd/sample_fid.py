@@ -45,6 +45,7 @@ def main(argv=None):
         torch.manual_seed(args.seed)
     device = torch.device("cuda")
     train_args = S.load_train_args(args.result_dir)
+    S.check_objective(args.sampler, train_args)                           # a velocity model and a diffusion sampler (or the reverse): refused here
     if args.num_classes is None:
         args.num_classes = int(train_args["num_classes"])
     elif args.num_classes != int(train_args["num_classes"]):
@@ -54,7 +55,7 @@ def main(argv=None):
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=False)
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device) if args.use_vae else None
-    diffusion, solver = S.make_diffusion(args)
+    diffusion, solver = S.make_diffusion(args, train_args)
 
     n = args.batch_size
     use_cfg = args.cfg_scale > 1.0

@@ -9,6 +9,10 @@ the map and the step counter live on the device, and a replay is a single graph 
 ``sampler="dpm++"`` captures one step of ``dpm_solver_sample_loop`` instead (the multistep DPM-Solver++, not in the reference):
 the lookup of the solver's timestep, the DiT forward, ``mapdit_dpm_step`` and ``step -= 1``, replayed once per solver step.  The
 previous x0 prediction, the step index and the solver's tables live on the device; no randomness is drawn.
+
+``sampler="flow"`` takes a ``flow.RectifiedFlow`` in the diffusion's place and captures one model evaluation of its Euler / Heun loop
+(``flow.sample_loop``): the lookup of the evaluation's timestep, the DiT forward, ``mapdit_flow_step`` and ``step -= 1``, replayed once
+per evaluation.  The solver's state, Heun's first velocity and the evaluation counter live on the device.
 """
 from __future__ import annotations
 
@@ -24,14 +28,23 @@ class GraphedSampler:
     model.forward_with_cfg (y must then hold [labels, null labels], as sample_fid.py:56-66 builds it).
 
     sampler: "ancestral" (p_sample, one replay per timestep of the diffusion) or "dpm++" (DPM-Solver++ with num_steps / order / spacing /
-    lower_order_final as ``diffusion.dpm_solver_sample_loop`` takes them; one replay per solver step, ``self.num_replays`` of them)."""
+    lower_order_final as ``diffusion.dpm_solver_sample_loop`` takes them; one replay per solver step, ``self.num_replays`` of them), or
+    "flow": `diffusion` is a ``flow.RectifiedFlow`` and num_steps / order (1 Euler, 2 Heun) are ``flow.sample_loop``'s; one replay per
+    model evaluation.  A RectifiedFlow with another sampler, or "flow" with a GaussianDiffusion, is refused; clip_denoised does not apply."""
 
     def __init__(self, model, diffusion, shape, y, cfg_scale=None, clip_denoised=False, sampler="ancestral", num_steps=20, order=2,
                  spacing="logsnr", lower_order_final=True):
         assert not model.training, "sampling runs the model in eval mode"
+        if sampler not in ("ancestral", "dpm++", "flow"):
+            raise ValueError(f'sampler must be "ancestral", "dpm++" or "flow"; got {sampler!r}')
+        from .flow import RectifiedFlow
+        if isinstance(diffusion, RectifiedFlow) != (sampler == "flow"):
+            raise ValueError(f'sampler="flow" runs a flow.RectifiedFlow and "ancestral" / "dpm++" a GaussianDiffusion; got sampler={sampler!r} '
+                             f"with a {type(diffusion).__name__}")
+        self.flow = None
+        if sampler == "flow":
+            return self._init_flow(model, diffusion, shape, y, cfg_scale, num_steps, order)
         diffusion._supported()
-        if sampler not in ("ancestral", "dpm++"):
-            raise ValueError(f'sampler must be "ancestral" or "dpm++"; got {sampler!r}')
         if diffusion.model_var_type.name != "LEARNED_RANGE":
             raise NotImplementedError(f"GraphedSampler drives a DiT, whose output carries learned-range variance channels; a "
                                       f"{diffusion.model_var_type.name} diffusion needs a model with C output channels "
@@ -54,6 +67,10 @@ class GraphedSampler:
         # the default objective replays mapdit_psample_step; x0 prediction (START_X) the generalised mapdit_obj_step
         self.otab = None if diffusion._is_default() else diffusion._obj_tables(dev)
         self.tmap = torch.tensor(diffusion.timestep_map, device=dev, dtype=torch.int64)
+        self._capture()
+
+    def _capture(self):
+        dev = self.dev
         self.graph = None
         with torch.no_grad():
             # eager warm-up on a side stream (allocates the engine workspace, builds the cached bf16 weight images)
@@ -70,8 +87,45 @@ class GraphedSampler:
             with torch.cuda.graph(self.graph):
                 self._step()
 
+    def _init_flow(self, model, flow, shape, y, cfg_scale, num_steps, order):
+        """The "flow" sampler's buffers and capture: img is the evaluation point (and what sample() returns), base the solver's state
+        (Euler: img itself), hist Heun's first velocity, t the evaluation counter (J - 1 down to 0)."""
+        self.model, self.diffusion = model, flow
+        dev = next(model.parameters()).device
+        self.dev = dev
+        self.dpm = None
+        self.flow = flow._plan_tables(dev, num_steps, order)
+        self.num_replays = len(self.flow[3])
+        self.img = torch.zeros(*shape, device=dev)
+        self.base = self.img if order == 1 else torch.zeros_like(self.img)
+        self.hist = torch.zeros_like(self.img)
+        self.t = torch.full((shape[0],), self.num_replays - 1, device=dev, dtype=torch.int64)
+        self.y = y.to(dev).clone()
+        self.cfg_scale, self.clip = cfg_scale, False
+        self.tab = flow._tables(dev)
+        self._capture()
+
+    def _flow_step(self):
+        f = self.diffusion
+        tau, ctab, flags = self.flow[:3]
+        t = tau[self.t.clamp(0, self.num_replays - 1)]
+        if self.cfg_scale is None:
+            out = self.model.forward(self.img, t, self.y)
+        else:
+            out = self.model.forward_with_cfg(self.img, t, self.y, self.cfg_scale)
+        out = out.contiguous().float()
+        # in place: the evaluation point is overwritten by the next one; Heun keeps the state in base (written on committing rows)
+        heun = self.base is not self.img
+        L.lib().flow_step(out.data_ptr(), None, self.base.data_ptr(), self.hist.data_ptr(), self.t.data_ptr(), tau.data_ptr(), ctab.data_ptr(),
+                          flags.data_ptr(), self.num_replays, self.tab.data_ptr(), f.num_timesteps, self.img.data_ptr(),
+                          self.base.data_ptr() if heun else None, None, self.img.shape[0], self.img[0].numel(),
+                          out[0].numel() // self.img[0].numel(), L.cur_stream())
+        self.t.sub_(1)
+
     def _step(self):
         d = self.diffusion
+        if self.flow is not None:
+            return self._flow_step()
         if self.dpm is not None:
             return self._dpm_step()
         mapped = self.tmap[self.t.clamp_min(0)]
@@ -127,6 +181,8 @@ class GraphedSampler:
             self.img.normal_()
         else:
             self.img.copy_(noise)
+        if self.flow is not None and self.base is not self.img:
+            self.base.copy_(self.img)
         self.t.fill_(n - 1)
         for _ in range(steps):
             self.graph.replay()
@@ -164,6 +220,16 @@ def dpm_solver_sample_loop_graphed(diffusion, model, shape, noise=None, clip_den
     assert not kw, f"unsupported model_kwargs: {sorted(kw)}"
     return GraphedSampler(model, diffusion, shape, y, cfg, clip_denoised, sampler="dpm++", num_steps=num_steps, order=order,
                           spacing=spacing, lower_order_final=lower_order_final).sample(noise)
+
+
+def flow_sample_loop_graphed(flow, model, shape, noise=None, model_kwargs=None, device=None, *, num_steps=50, order=1):
+    """Drop-in for ``flow.sample_loop(model.forward[_with_cfg], shape, noise, model_kwargs=..., num_steps=..., order=...)`` with the model
+    evaluation and its mapdit_flow_step replayed from a hipGraph.  ``model`` is the DiT module itself."""
+    kw = dict(model_kwargs or {})
+    y = kw.pop("y")
+    cfg = kw.pop("cfg_scale", None)
+    assert not kw, f"unsupported model_kwargs: {sorted(kw)}"
+    return GraphedSampler(model, flow, shape, y, cfg, sampler="flow", num_steps=num_steps, order=order).sample(noise)
 
 
 # ---- shared pieces of the sampler CLIs (reference sample.py / sample_fid.py / sample_ema.py) ---------------------------
@@ -218,22 +284,43 @@ def load_vae(vae_path: str | None, device):
     return AutoencoderKL.from_pretrained(vae_path or "stabilityai/sd-vae-ft-mse").to(device)
 
 
-SAMPLERS = ("ancestral", "dpm++")
+SAMPLERS = ("ancestral", "dpm++", "flow-euler", "flow-heun")
+FLOW_SAMPLERS = {"flow-euler": 1, "flow-heun": 2}          # -> the order of flow.sample_loop
 
 
 def add_sampler_flags(parser):
     """The sampler choice shared by the three CLIs.  Under ``dpm++`` ``--num-sampling-steps`` is the solver's num_steps and the
-    diffusion is the full schedule, which the solver subsamples itself (``make_diffusion``)."""
+    diffusion is the full schedule, which the solver subsamples itself (``make_diffusion``); under ``flow-euler`` / ``flow-heun`` (a
+    run trained with ``--objective flow``) it is the num_steps of ``flow.sample_loop``."""
     parser.add_argument("--sampler", choices=SAMPLERS, default="ancestral",
-                        help="ancestral: the reference's p_sample_loop; dpm++: DPM-Solver++ (deterministic, ~20 steps)")
+                        help="ancestral: the reference's p_sample_loop; dpm++: DPM-Solver++ (deterministic, ~20 steps); flow-euler / "
+                             "flow-heun: the ODE sampler of a run trained with --objective flow")
     parser.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="dpm++ only: 1 (DDIM) or 2 (2M)")
     parser.add_argument("--solver-spacing", choices=["logsnr", "uniform"], default="logsnr", help="dpm++ only: how its steps are chosen")
     return parser
 
 
-def make_diffusion(args):
-    """create_diffusion for a CLI's arguments and the GraphedSampler / run_sampler keywords that select its sampler."""
+def check_objective(sampler: str, train_args: dict | None):
+    """A run directory's objective (config.yaml: "diffusion" where the key is missing, as every run before the key existed) against
+    the sampler asked for: a velocity model means nothing to the diffusion samplers, and the reverse."""
+    objective = (train_args or {}).get("objective", "diffusion")
+    if objective == "flow" and sampler not in FLOW_SAMPLERS:
+        raise ValueError(f"this run was trained with --objective flow: its model predicts a velocity, which --sampler {sampler} cannot read; "
+                         "pass --sampler flow-euler or --sampler flow-heun")
+    if objective != "flow" and sampler in FLOW_SAMPLERS:
+        raise ValueError(f"this run was trained with --objective {objective}: its model predicts eps, which --sampler {sampler} cannot read; "
+                         "pass --sampler ancestral or --sampler dpm++")
+
+
+def make_diffusion(args, train_args: dict | None = None):
+    """create_diffusion (or create_flow) for a CLI's arguments and the GraphedSampler / run_sampler keywords that select its sampler.
+    train_args: the run's config.yaml, whose objective must fit the sampler (check_objective)."""
     from .diffusion import create_diffusion
+    check_objective(args.sampler, train_args)
+    if args.sampler in FLOW_SAMPLERS:
+        from .flow import create_flow
+        return (create_flow(shift=float((train_args or {}).get("flow_shift", 1.0))),
+                dict(sampler="flow", num_steps=args.num_sampling_steps, order=FLOW_SAMPLERS[args.sampler]))
     if args.sampler == "dpm++":
         return create_diffusion(""), dict(sampler="dpm++", num_steps=args.num_sampling_steps, order=args.solver_order,
                                           spacing=args.solver_spacing)
@@ -244,9 +331,21 @@ def run_sampler(model, diffusion, z, y, cfg_scale, use_graph: bool = True, progr
                 num_steps: int = 20, order: int = 2, spacing: str = "logsnr"):
     """``diffusion.p_sample_loop(model.forward[_with_cfg], z.shape, z, clip_denoised=False, ...)`` - through the captured
     hipGraph (default) or the eager loop; with ``sampler="dpm++"``, ``diffusion.dpm_solver_sample_loop`` (num_steps, order,
-    spacing) the same two ways."""
-    if sampler not in SAMPLERS:
-        raise ValueError(f"sampler must be one of {SAMPLERS}; got {sampler!r}")
+    spacing) the same two ways; with ``sampler="flow"`` (or the CLI names "flow-euler" / "flow-heun", which fix the order), `diffusion`
+    is a RectifiedFlow and the loop is its ``sample_loop(num_steps=, order=1 | 2)``."""
+    if sampler not in SAMPLERS + ("flow",):
+        raise ValueError(f"sampler must be one of {SAMPLERS + ('flow',)}; got {sampler!r}")
+    if sampler == "flow" or sampler in FLOW_SAMPLERS:
+        order = FLOW_SAMPLERS.get(sampler, order)
+        if use_graph:
+            return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, sampler="flow", num_steps=num_steps, order=order).sample(z)
+        from .flow import RectifiedFlow
+        if not isinstance(diffusion, RectifiedFlow):
+            raise ValueError(f'sampler="flow" runs a flow.RectifiedFlow and "ancestral" / "dpm++" a GaussianDiffusion; got sampler={sampler!r} '
+                             f"with a {type(diffusion).__name__}")
+        kw = dict(y=y) if cfg_scale is None else dict(y=y, cfg_scale=cfg_scale)
+        fn = model.forward if cfg_scale is None else model.forward_with_cfg
+        return diffusion.sample_loop(fn, z.shape, z, model_kwargs=kw, progress=progress, device=z.device, num_steps=num_steps, order=order)
     solver = dict(num_steps=num_steps, order=order, spacing=spacing) if sampler == "dpm++" else {}
     if use_graph:
         return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, clip_denoised=False, sampler=sampler, **solver).sample(z)

@@ -13,7 +13,9 @@ them on, SURVEY F5 — turning one off is refused), data parallelism when launch
 micro-batches per rank (the activations of --batch-size / (world * K) samples are alive at a time), and --max-grad-norm F: global
 gradient-norm clipping on the device, fused into the optimiser step (optim.FusedAdamEMA.max_grad_norm), and --schedule-sampler
 loss-second-moment: improved-DDPM's loss-aware timestep resampling with importance weights, state and draw on the device
-(diffusion/timestep_sampler.py; the checkpoint then gains a "schedule_sampler" key).
+(diffusion/timestep_sampler.py; the checkpoint then gains a "schedule_sampler" key), and --objective flow: the rectified-flow velocity
+objective (flow/__init__.py) in the diffusion objective's place, with --flow-shift and --flow-timestep-density; config.yaml records it
+and the sampler CLIs read it.
 """
 import argparse
 import contextlib
@@ -28,6 +30,7 @@ import yaml
 from . import parallel
 from .diffusion import create_diffusion
 from .diffusion.timestep_sampler import create_named_schedule_sampler
+from .flow import create_flow
 from .optim import FusedAdamEMA, create_lr_lambda
 from .src.models import DIT_MODELS
 
@@ -132,6 +135,14 @@ def build_parser():
                         "(diffusion/timestep_sampler.py: p(t) follows the second moment of each timestep's last 10 losses once every "
                         "timestep has 10, the loss is weighted by 1 / (T p(t)); history, table and draw stay on the device, ranks share one "
                         "history).  Individual weights reach 1 / uniform_prob = 1000 in the worst case: see INTEGRATION.md on --precision f16")
+    p.add_argument("--objective", choices=["diffusion", "flow"], default="diffusion",
+                   help="diffusion (default): the reference's eps objective with learned-range variances; flow: the rectified-flow velocity "
+                        "objective on the same timestep grid (x_s = (1 - s) x0 + s eps, target eps - x0; the variance channels are ignored). "
+                        "Sample such a run with --sampler flow-euler / flow-heun")
+    p.add_argument("--flow-shift", type=float, default=1.0, help="--objective flow: SD3's resolution shift of flow time (1: none)")
+    p.add_argument("--flow-timestep-density", choices=["uniform", "logit-normal"], default="uniform",
+                   help="--objective flow: how the default (uniform) schedule sampler draws timesteps (logit-normal: SD3's, loc 0, scale 1); "
+                        "under --schedule-sampler loss-second-moment that sampler draws them and this flag changes nothing")
     for f in MP_FLAGS:
         p.add_argument(f"--use-{f}", dest="use_" + f.replace("-", "_"), action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--use-rotation-modulation", action=argparse.BooleanOptionalAction, default=False,
@@ -172,6 +183,11 @@ def main(argv=None):
         raise NotImplementedError("--activation-recompute is built for the f16 / bf16 engines without the LayerNorm form (--no-use-no-layernorm)")
     if not args.use_no_layernorm and args.use_rotation_modulation:
         raise NotImplementedError("--no-use-no-layernorm (the LayerNorm form) is built for the AdaLN modulation, not with --use-rotation-modulation")
+    flow_mode = args.objective == "flow"
+    if not flow_mode and (args.flow_shift != 1.0 or args.flow_timestep_density != "uniform"):
+        raise ValueError("--flow-shift / --flow-timestep-density belong to --objective flow")
+    if flow_mode:
+        create_flow(shift=args.flow_shift)                               # (a bad --flow-shift fails here, before any device work)
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -207,7 +223,8 @@ def main(argv=None):
             logf.write(msg + "\n")
             logf.flush()
 
-    diffusion = create_diffusion(timestep_respacing="")
+    # --objective flow: a RectifiedFlow stands where the diffusion stood (num_timesteps, training_losses); nothing below looks inside
+    diffusion = create_flow(shift=args.flow_shift) if flow_mode else create_diffusion(timestep_respacing="")
     model = get_model(args).to(dev).train()
     model.gemm_precision = args.precision
     model.activation_recompute = args.activation_recompute
@@ -232,6 +249,11 @@ def main(argv=None):
     reducer.attach(opt)
     # the default draws with torch.randint below, exactly as before; the sampler object exists only with the flag
     t_sampler = create_named_schedule_sampler(args.schedule_sampler, diffusion) if args.schedule_sampler != "uniform" else None
+
+    def draw_t(n):
+        if flow_mode:
+            return diffusion.sample_timesteps(n, dev, density=args.flow_timestep_density)
+        return torch.randint(0, diffusion.num_timesteps, (n,), device=dev)
 
     def weighted_loss(xb, yb):
         """Mean over the batch of weight x loss at timesteps drawn by the schedule sampler; the history takes the unweighted losses."""
@@ -259,7 +281,7 @@ def main(argv=None):
     for x, y in batches():
         if K == 1:
             if t_sampler is None:
-                t = torch.randint(0, diffusion.num_timesteps, (x.shape[0],), device=dev)
+                t = draw_t(x.shape[0])
                 loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
             else:
                 loss = weighted_loss(x, y)
@@ -273,7 +295,7 @@ def main(argv=None):
             for k in range(K):
                 xk, yk = x[k * micro:(k + 1) * micro], y[k * micro:(k + 1) * micro]
                 if t_sampler is None:
-                    t = torch.randint(0, diffusion.num_timesteps, (micro,), device=dev)          # each micro-batch draws its own
+                    t = draw_t(micro)                                                            # each micro-batch draws its own
                     part = diffusion.training_losses(model, xk, t, dict(y=yk))["loss"].mean()    # NOT divided by K: see grad_scale above
                 else:
                     part = weighted_loss(xk, yk)
