@@ -631,6 +631,41 @@ int mapdit_flow_step(const float* model_out, const float* x_eval, const float* b
                      float* base_out, float* pred_xstart, int N, int per_sample, int groups, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Device-resident latent data set (data.py, train.py --data-loader device), additive within abi 5: the epoch shuffle, the gather
+ * of a batch and the draw from each sample's posterior as ONE launch and as a pure function of (seed, epoch, position).  No state,
+ * no buffer, no per-epoch work, no host read, no allocation: every entry is capturable.  THE LAYOUT BELOW IS A CONTRACT:
+ * reproducing a run depends on it.
+ *   Generator: Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85,
+ *     key = (seed & 0xffffffff, seed >> 32); counter and output are four 32-bit words (c0..c3 -> w0..w3).
+ *   Normals from the four words: u_k = ((w_k >> 8) + 0.5) 2^-24 (never 0, never 1),
+ *         z0, z1 = r0 cos(2 pi u_1), r0 sin(2 pi u_1), r0 = sqrt(-2 ln u_0);     z2, z3 likewise from u_2 (radius) and u_3 (angle).
+ *     |z| <= sqrt(50 ln 2) = 5.89: the tail beyond it is cut off (4e-9 of the mass per draw).  Evaluated with the accurate library
+ *     functions on exact arguments: below 1/2 u has 24 significant bits and logf(u), sincospif(2u) take it as it is; above, 1 - u has
+ *     them and ln u = log1pf(-(1 - u)), (sin, cos)(2 pi u) = (-sin, cos)(pi (2 - 2u)).  Every value is within 8 ulp of the real one.
+ *   Epoch permutation perm_{seed,epoch,N} of [0, N), N < 2^32: a balanced Feistel network over [0, 2^b), b = the smallest even number
+ *     >= max(2, bit length of N - 1), L = the high b/2 bits of the value and R the low ones, four rounds (round = 0..3)
+ *         (L, R) <- (R, L ^ (philox(counter = (R, round, epoch, TAG_PERM), key)[0] & (2^(b/2) - 1))),    value <- L 2^(b/2) + R,
+ *     applied again until the value is < N (cycle walking; 2^b <= 4N).  TAG_PERM = 0x5045524D.
+ *   Noise of a sample: element i of the sample at in-epoch position p is normal i & 3 of philox(counter = (i >> 2, p, epoch, TAG_NOISE)),
+ *     TAG_NOISE = 0x4E4F4953: independent of batch size, rank and slot in the batch, fresh on every visit (the epoch is in the counter).
+ *
+ *   mapdit_philox_normal: out[i] = normal i & 3 of counter (i >> 2, c1, c2, c3), any 1 <= n <= 2^34.
+ *   mapdit_data_perm: idx[j] = perm_{seed,epoch,N}(first + j) for j < count; 0 <= first, count >= 1, first + count <= N.
+ *   mapdit_data_batch: for j < count, k = perm(first + j), c = the channel of element i (i / hw):
+ *         f = means[k][i] + eps * stds[k][i]  (two roundings),   x[j][i] = (f - ch_mean[c]) / ch_std[c]  (correctly rounded
+ *     subtraction and division: transforms.Normalize),   y[j] = labels[k],   idx_out[j] = k (nullable).
+ *     eps is the sample's noise above, or eps_in[j][i] where eps_in (fp32 [count][C * hw]) is given: a caller's own noise.  means /
+ *     stds fp32 [N][C][hw], labels int64 [N] (copied as they are), ch_mean / ch_std fp32 [C] (a zero or non-finite ch_std is the
+ *     caller's to refuse).  C * hw is any value >= 1; where it is a multiple of 4 and the tensors are 16-byte aligned the kernel moves
+ *     16 bytes per lane.  Same range rule as mapdit_data_perm.
+ * ------------------------------------------------------------------------------------------------------------ */
+int mapdit_philox_normal(uint64_t seed, uint32_t c1, uint32_t c2, uint32_t c3, float* out, long n, void* stream);
+int mapdit_data_perm(uint64_t seed, uint32_t epoch, long N, long first, long count, int64_t* idx, void* stream);
+int mapdit_data_batch(const float* means, const float* stds, const int64_t* labels, long N, int C, int hw, const float* ch_mean,
+                      const float* ch_std, uint64_t seed, uint32_t epoch, long first, int count, const float* eps_in, float* x,
+                      int64_t* y, int64_t* idx_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Engine: the whole DiT forward / backward sequenced from C++ on one stream (src/dit.py:70-105 and its autograd).
  * ------------------------------------------------------------------------------------------------------------ */
 enum { MAPDIT_OFF_MP_SILU = 1, MAPDIT_OFF_MP_RESIDUAL = 2, MAPDIT_OFF_MP_POS_ENC = 4, MAPDIT_OFF_MP_EMBEDDING = 8,

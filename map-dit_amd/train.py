@@ -15,7 +15,8 @@ gradient-norm clipping on the device, fused into the optimiser step (optim.Fused
 loss-second-moment: improved-DDPM's loss-aware timestep resampling with importance weights, state and draw on the device
 (diffusion/timestep_sampler.py; the checkpoint then gains a "schedule_sampler" key), and --objective flow: the rectified-flow velocity
 objective (flow/__init__.py) in the diffusion objective's place, with --flow-shift and --flow-timestep-density; config.yaml records it
-and the sampler CLIs read it.
+and the sampler CLIs read it, and --data-loader device: the data set lives in HBM and a step's batch is one launch, a function of
+(--seed, step) alone (data.py); the default, host, is the reference's DataLoader.
 """
 import argparse
 import contextlib
@@ -28,6 +29,7 @@ import torch
 import yaml
 
 from . import parallel
+from .data import DeviceLatentDataset
 from .diffusion import create_diffusion
 from .diffusion.timestep_sampler import create_named_schedule_sampler
 from .flow import create_flow
@@ -102,6 +104,11 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     p.add_argument("--num-workers", type=int, default=4)
+    p.add_argument("--data-loader", choices=["host", "device"], default="host",
+                   help="host (default): the reference's DataLoader over --data-path, --num-workers processes per rank; device: the data "
+                        "set is uploaded once and every batch - epoch shuffle, gather, posterior draw, standardisation - is one launch, a "
+                        "function of (--seed, optimiser step) alone: the same data for any world size and --grad-accum-steps "
+                        "(data.DeviceLatentDataset; --num-workers is ignored; the data set must fit HBM)")
     p.add_argument("--log-every", type=int, default=100)
     p.add_argument("--ckpt-every", type=int, default=50_000)
     p.add_argument("--num-lin-warmup", type=int, default=None)
@@ -183,6 +190,8 @@ def main(argv=None):
         raise NotImplementedError("--activation-recompute is built for the f16 / bf16 engines without the LayerNorm form (--no-use-no-layernorm)")
     if not args.use_no_layernorm and args.use_rotation_modulation:
         raise NotImplementedError("--no-use-no-layernorm (the LayerNorm form) is built for the AdaLN modulation, not with --use-rotation-modulation")
+    if args.data_loader == "device" and args.synthetic:
+        raise ValueError("--data-loader device draws from the data set under --data-path; --synthetic has none")
     flow_mode = args.objective == "flow"
     if not flow_mode and (args.flow_shift != 1.0 or args.flow_timestep_density != "uniform"):
         raise ValueError("--flow-shift / --flow-timestep-density belong to --objective flow")
@@ -201,10 +210,13 @@ def main(argv=None):
         loader = None
     else:
         assert args.data_path, "--data-path or --synthetic"
-        ds = LatentDataset(args.data_path)
-        sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True, drop_last=True) if world > 1 else None
-        loader = torch.utils.data.DataLoader(ds, batch_size=per_rank, num_workers=args.num_workers, shuffle=sampler is None,
-                                             sampler=sampler, pin_memory=True, drop_last=True)
+        if args.data_loader == "device":
+            ds, loader = DeviceLatentDataset(args.data_path, dev, seed=args.seed), None
+        else:
+            ds = LatentDataset(args.data_path)
+            sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True, drop_last=True) if world > 1 else None
+            loader = torch.utils.data.DataLoader(ds, batch_size=per_rank, num_workers=args.num_workers, shuffle=sampler is None,
+                                                 sampler=sampler, pin_memory=True, drop_last=True)
         args.in_channels, args.input_size = ds.channels, ds.data_size
         args.stats_std = [float(v) for v in ds.stats["std"]]
         args.stats_mean = [float(v) for v in ds.stats["mean"]]
@@ -263,6 +275,9 @@ def main(argv=None):
         return (losses["loss"] * w).mean()
 
     def batches():
+        if args.data_loader == "device":
+            while True:                          # train_steps: optimiser steps taken so far = the 0-based step this batch belongs to
+                yield ds.batch(train_steps, args.batch_size, rank, world)
         if loader is None:
             g = torch.Generator(device=dev).manual_seed(args.seed + 1 + rank)
             while True:
