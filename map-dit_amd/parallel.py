@@ -23,6 +23,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import _lib as _L
+
 
 def init_from_env(backend: str | None = None):
     """Rendezvous from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* (torchrun).  Returns (rank, world, local_rank)."""
@@ -401,8 +403,9 @@ class Zero1Reducer(_NoSync, _ReducerBase):
                 _verify_gather(p[lo:hi], (hi - lo) // self.world, self.world, before, self.group)
 
 
-_SHARDED_SUFFIXES = ("attn.qkv_proj.weight", "attn.out_proj.weight", "mlp.net.0.weight", "mlp.net.2.weight", "modulation.1.weight")
-_B_OF = {"attn.qkv_proj.weight": 0, "attn.out_proj.weight": 1, "mlp.net.0.weight": 2, "mlp.net.2.weight": 3, "modulation.1.weight": 4}   # mapdit.h MAPDIT_B_*
+_B_OF = {"attn.qkv_proj.weight": _L.B_QKV, "attn.out_proj.weight": _L.B_PROJ, "mlp.net.0.weight": _L.B_FC1, "mlp.net.2.weight": _L.B_FC2,
+         "modulation.1.weight": _L.B_MOD}                     # a block's sharded weights -> their slot (mapdit.h MAPDIT_B_*)
+_SHARDED_SUFFIXES = tuple(_B_OF)
 SHARDED_CLIP_ERROR = ("max_grad_norm (global gradient-norm clipping) is not built for sharded weight passes (--grad-comm zero1w / zero1w-bf16): "
                       "a rank's shards mix owned rows with replicated ranges; use allreduce or zero1")
 

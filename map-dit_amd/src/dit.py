@@ -447,15 +447,21 @@ class DiT(nn.Module):
         return accumulate
 
     def _param_table(self):
-        """Tensors in the order of the engine's parameter table (include/mapdit.h: MAPDIT_P_*, MAPDIT_B_*)."""
-        f = self.final_layer
-        tab = [self.x_embedder.weight, self.t_embedder.mlp.net[0].weight, self.t_embedder.mlp.net[2].weight,
-               self.y_embedder.embedding.weight, f.linear.weight, f.modulation[1].weight, f.mean_scale.linear.weight,
-               f.mean_scale.reference, f.sigma_scale.linear.weight, f.sigma_scale.reference, f.gain_mod,
-               self.t_embedder.embedding.scale, self.t_embedder.embedding.shift, self.pos_embed]
-        for b in self.blocks:
-            tab += [b.attn.qkv_proj.weight, b.attn.out_proj.weight, b.mlp.net[0].weight, b.mlp.net[2].weight,
-                    b.modulation[1].weight, b.gain_msa, b.gain_mlp]
+        """Tensors in the order of the engine's parameter table, each put into the slot include/mapdit.h names (MAPDIT_P_*, MAPDIT_B_*)."""
+        f, t = self.final_layer, self.t_embedder
+        tab = [None] * (L.NUM_GLOBAL + len(self.blocks) * L.NUM_BLOCK)
+        tab[L.P_X_EMB], tab[L.P_T0], tab[L.P_T2] = self.x_embedder.weight, t.mlp.net[0].weight, t.mlp.net[2].weight
+        tab[L.P_Y_EMB], tab[L.P_F_LIN], tab[L.P_F_MOD] = self.y_embedder.embedding.weight, f.linear.weight, f.modulation[1].weight
+        tab[L.P_MS_LIN], tab[L.P_MS_REF] = f.mean_scale.linear.weight, f.mean_scale.reference
+        tab[L.P_SS_LIN], tab[L.P_SS_REF] = f.sigma_scale.linear.weight, f.sigma_scale.reference
+        tab[L.P_F_GAIN], tab[L.P_FOURIER_SCALE], tab[L.P_FOURIER_SHIFT] = f.gain_mod, t.embedding.scale, t.embedding.shift
+        tab[L.P_POS_EMBED] = self.pos_embed
+        for i, b in enumerate(self.blocks):
+            at = L.NUM_GLOBAL + i * L.NUM_BLOCK
+            tab[at + L.B_QKV], tab[at + L.B_PROJ] = b.attn.qkv_proj.weight, b.attn.out_proj.weight
+            tab[at + L.B_FC1], tab[at + L.B_FC2] = b.mlp.net[0].weight, b.mlp.net[2].weight
+            tab[at + L.B_MOD], tab[at + L.B_GAIN_MSA], tab[at + L.B_GAIN_MLP] = b.modulation[1].weight, b.gain_msa, b.gain_mlp
+        assert all(x is not None for x in tab), "mapdit.h names a parameter slot that _param_table does not fill"
         return tab
 
     def _grad_table(self):

@@ -151,7 +151,7 @@ def test_rmb_column_split_equals_the_whole_width_pass(L):
     dx_w, dy_w, dmod_w, dmu_w, part_w = mk()
     a = args(gm, dx_w, dy_w, dmod_w, dmu_w, part_w)
     npart = C.c_int(0)
-    a.gain_partials_out = C.pointer(npart)
+    a.gain_partials_out = C.addressof(npart)
     L.lib().resid_mod_bwd(C.byref(a), st())
     dgain_w = torch.zeros((), device=DEV)
     L.lib().reduce_partials(p(part_w), npart.value, p(dgain_w), 0, st())
@@ -173,7 +173,7 @@ def test_rmb_column_split_equals_the_whole_width_pass(L):
     part2 = torch.zeros(4096, device=DEV)
     a2 = args(gm2, dx_s, dy_s, dmod_s, dmu_s, part2, c0=D1, width=128, ldx=D)
     npart2 = C.c_int(0)
-    a2.gain_partials_out = C.pointer(npart2)
+    a2.gain_partials_out = C.addressof(npart2)
     L.lib().resid_mod_bwd(C.byref(a2), st())
     torch.cuda.synchronize()
     part_s[n1:n1 + npart2.value] = part2[:npart2.value]
@@ -789,7 +789,7 @@ def test_modulate_and_fused_backward(L):
     part8 = torch.full((8 * N * (D // 128),), float("nan"), device=DEV)
     nparts = C.c_int(0)
     dmod2, dmod_up2, dx2, dy2 = torch.zeros_like(dmod), torch.zeros_like(dmod_up), torch.zeros_like(dx), torch.zeros_like(dy)
-    a.part_scratch, a.part_scratch_bytes, a.gain_partials_out = p(scratch), scratch.numel() * 4, C.pointer(nparts)
+    a.part_scratch, a.part_scratch_bytes, a.gain_partials_out = p(scratch), scratch.numel() * 4, C.addressof(nparts)
     a.dgain_part, a.dx, a.dy_up = p(part8), p(dx2), p(dy2)
     a.dshift, a.dscale = dmod2.data_ptr() + 4 * 3 * D, dmod2.data_ptr() + 4 * 4 * D
     a.dg_up = dmod_up2.data_ptr() + 4 * 5 * D
