@@ -127,8 +127,8 @@ int mapdit_gemm_tile_size_ex(int M, int N, int split_k_launch);
  * ~50 K-tiles takes the 128 edge.  Size split_k with this one when K is at hand. */
 int mapdit_gemm_tile_size_k(int M, int N, int K, int split_k_launch);
 /* Benchmarking hook: force the tile edge (0 = by shape, 128, 256), the K-loop schedule (2 | 4 phases per K-tile) and the
- * band width of the tile order (0 = derived from K).  The environment (MAPDIT_GEMM_TILE / _PHASES / _BAND) is read once, at the
- * first launch; this overrides it afterwards. */
+ * band width of the tile order (0 = derived from K).  These are three fields of the library's switch table (csrc/switches.h), which is
+ * filled from the environment (MAPDIT_GEMM_TILE / _PHASES / _BAND) once, at first use; this overrides it afterwards. */
 void mapdit_gemm_tuning(int tile, int phases, long band);
 /* How a launch stages its operand tiles (host logic, no GPU call).  mapdit_gemm_dma_fast: 1 if a launch of this shape on tiles of `tile`
  * rows (256: 256 x 256, 128: 128 x 128, 64: 64 x 128) issues its LDS-DMA from a scalar base and 32-bit lane offsets -

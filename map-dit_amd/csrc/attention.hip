@@ -16,9 +16,9 @@
 // dK/dV pass builds transposed images in LDS while staging (16-byte global loads, 2-byte transposed LDS stores).
 // The backward is two passes (7 products instead of 5) so no cross-wave reduction and no atomics are needed:
 // attention is ~5 % of the block's FLOPs.
-#include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 MD_NS_OPEN
 
@@ -417,11 +417,8 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn_bwd_dkv_kernel(const bf16_t*
         sdo1_.store(dos_, dots_, tid);
     }
     __syncthreads();
-#ifndef ATTN_PROBE
-#define ATTN_PROBE 0
-#endif
 #pragma unroll 1
-    for (int qt = 0; qt < (ATTN_PROBE == 1 ? 0 : G::NT); ++qt) {
+    for (int qt = 0; qt < G::NT; ++qt) {
         f32x16_t s = {}, dp = {};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -606,11 +603,8 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn_bwd_fused_kernel(const bf16_
         for (int e = 0; e < CW; e += 2) op[e >> 1] = pack16(sc * g[e] - x[e] * cc, sc * g[e + 1] - x[e + 1] * cc);
     };
 
-#ifndef ATTN_PROBE
-#define ATTN_PROBE 0
-#endif
 #pragma unroll 1
-    for (int qt = 0; qt < (ATTN_PROBE == 1 ? 0 : G::NT); ++qt) {
+    for (int qt = 0; qt < G::NT; ++qt) {
         f32x16_t s = {}, dp = {};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -620,13 +614,9 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn_bwd_fused_kernel(const bf16_
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int qr = 32 * qt + acc_row(i, lane);
-#if ATTN_PROBE == 4
-            (void)qr;
-#else
             const float p = __expf(s[i] * scale - lse_s[qr]);
             s[i] = p;
             dp[i] = p * (dp[i] - del_s[qr]) * scale;
-#endif
         }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
@@ -642,9 +632,9 @@ __global__ __launch_bounds__(Geo<T>::NTH) void attn_bwd_fused_kernel(const bf16_
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4)
             *(uint2*)(dsw + 16 * g4) = make_uint2(pack16(dp[4 * g4], dp[4 * g4 + 1]), pack16(dp[4 * g4 + 2], dp[4 * g4 + 3]));
-        if (qt > 0 && ATTN_PROBE != 2) dq_tile(qt - 1);                         // (image of the previous tile: complete since the last barrier)
+        if (qt > 0) dq_tile(qt - 1);                         // (image of the previous tile: complete since the last barrier)
         __syncthreads();
-        if (qt > 0 && ATTN_PROBE != 2 && ATTN_PROBE != 3) dq_store(qt - 1);
+        if (qt > 0) dq_store(qt - 1);
     }
     dq_tile(G::NT - 1);
     __syncthreads();                                         // also: every wave is done with the Q / dO / K tiles
@@ -1092,23 +1082,10 @@ extern "C" int mapdit_debug_attn_stamps(long long* out) { return (int)hipMemcpyF
         default: mapdit_set_error("attention: T=%d unsupported (64, 128, 256 or a multiple of 256)", T_); return MAPDIT_ERR_ARG; \
     }
 
-// Generic-shape path (attention_generic.hip): any head_dim <= 96, any T <= 256.
-extern "C" int MD_SYM(attn_generic_fwd)(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, float*, int, int, int, int, void*);
-extern "C" int MD_SYM(attn_generic_bwd)(const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*,
-                                       const float*, float*, uint16_t*, uint16_t*, uint16_t*, int, int, int, int, void*);
-
+// Everything else takes the generic-shape path (attention_generic.hip): any head_dim <= 96, any T <= 256.
 static bool mfma_shape(int T, int head_dim) { return head_dim == 64 && (T == 64 || T == 128 || (T >= 256 && T % 256 == 0)); }
-// head_dim 72 (DiT-XL): MFMA kernels of attention72.hip; an escape hatch keeps the generic path reachable for A/B runs
-int MD_SYM(attn72_fwd)(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, float*, int, int, int, void*);
-int MD_SYM(attn72_bwd)(const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const float*, float*,
-                      uint16_t*, uint16_t*, uint16_t*, int, int, int, void*);
-int MD_SYM(attn72_bwd_fused)(const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const float*, float*,
-                            const float*, uint16_t*, int, int, int, void*);
-static bool mfma72_shape(int T, int head_dim) {           // (beyond 256 tokens: 256-token tiles, as for head_dim 64)
-    if (head_dim != 72 || !(T == 64 || T == 128 || (T >= 256 && T % 256 == 0 && T <= 16384))) return false;
-    static const bool enabled = [] { const char* e = getenv("MAPDIT_ATTN72"); return !(e && e[0] == '0'); }();   // read once
-    return enabled;
-}
+// head_dim 72 (DiT-XL): the MFMA kernels of attention72.hip (beyond 256 tokens: 256-token tiles, as for head_dim 64)
+static bool mfma72_shape(int T, int head_dim) { return head_dim == 72 && (T == 64 || T == 128 || (T >= 256 && T % 256 == 0 && T <= 16384)); }
 
 extern "C" int MD_SYM(attn_cos_fwd)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v, uint16_t* o, float* lse,
                                    int B, int T, int H, int head_dim, void* stream) {
@@ -1125,8 +1102,6 @@ extern "C" int MD_SYM(attn_cos_fwd)(const uint16_t* qn, const uint16_t* kn, cons
 
 // Plain scaled-dot-product attention (F.scaled_dot_product_attention of attention.py:45 on q, k that were NOT normalised: README.md:58
 // --no-use-cosine-attention; parity unpinned): same layouts and scale as mapdit_attn_cos_fwd, the softmax with its row maximum taken out.
-int MD_SYM(attn72_fwd_max)(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, float*, int, int, int, void*);
-int MD_SYM(attn_generic_fwd_max)(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, float*, int, int, int, int, void*);
 extern "C" int MD_SYM(attn_sdpa_fwd)(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H,
                                     int head_dim, void* stream) {
     MD_CHECK(q && k && v && o && lse, "attn_sdpa_fwd: null argument");
@@ -1170,8 +1145,8 @@ extern "C" int MD_SYM(attn_cos_bwd_fused)(const uint16_t* qn, const uint16_t* kn
     const float* sq = scales;
     const float* sk = scales + (size_t)B * H * T;
     hipStream_t st = (hipStream_t)stream;
-    static const bool two_pass = [] { const char* e = getenv("MAPDIT_ATTN_BWD"); return e && e[0] == '2'; }();   // A/B switch, read once
-    static const int one_head = [] { const char* e = getenv("MAPDIT_ATTN_BWD"); return e && e[0] == '1'; }();       // (the kernel below for T = 256 too)
+    const bool two_pass = mapdit_switches().attn_bwd == 2;
+    const bool one_head = mapdit_switches().attn_bwd == 1;             // (the kernel below for T = 256 too)
     if (T == 256 && !two_pass && !one_head) {              // persistent workgroups, operands streamed
         static const int ncu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
         const int nheads = B * H, grid = nheads < ncu ? nheads : ncu;

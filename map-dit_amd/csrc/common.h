@@ -153,7 +153,23 @@ int mapdit_dev_error_take_precise(hipStream_t st, int* out);
 int mapdit_dev_error_take_tsampler(hipStream_t st, int* out);
 int mapdit_dev_error_take_flow(hipStream_t st, int* out);
 
-// Error plumbing shared by the C-ABI entry points (thread-local last-error string).
+// ---- entry points one translation unit offers another, outside the C ABI (per operand format: MD_SYM) -----------------------------
+// attention72.hip -> attention.hip (the head_dim-72 MFMA kernels behind mapdit_attn_cos_* / mapdit_attn_sdpa_fwd)
+int MD_SYM(attn72_fwd)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H, void* stream);
+int MD_SYM(attn72_fwd_max)(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H, void* stream);
+int MD_SYM(attn72_bwd)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v, const uint16_t* dO, const uint16_t* O, const float* lse,
+                      float* delta, uint16_t* dqn, uint16_t* dkn, uint16_t* dv, int B, int T, int H, void* stream);
+int MD_SYM(attn72_bwd_fused)(const uint16_t* qn, const uint16_t* kn, const uint16_t* v, const uint16_t* dO, const uint16_t* O, const float* lse,
+                            float* delta, const float* scales, uint16_t* dqkv, int B, int T, int H, void* stream);
+// attention_generic.hip -> attention.hip (plain softmax with the row maximum taken out, any head_dim <= 96)
+int MD_SYM(attn_generic_fwd_max)(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int T, int H,
+                                int head_dim, void* stream);
+// attention72.hip -> pointwise.hip (behind mapdit_qkv_split / mapdit_qkv_merge_bwd)
+int MD_SYM(qkv_split72)(const uint16_t* qkv, int B, int T, int H, uint16_t* qn, uint16_t* kn, uint16_t* v, void* stream);
+int MD_SYM(qkv_merge_bwd72)(const uint16_t* qkv, int B, int T, int H, const uint16_t* dqn, const uint16_t* dkn, const uint16_t* dv,
+                           uint16_t* dqkv, void* stream);
+
+// Error plumbing shared by the C-ABI entry points (thread-local last-error string; defined in switches.hip).
 void mapdit_set_error(const char* fmt, ...);
 #define MD_CHECK(cond, ...)                                   \
     do {                                                      \

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "precise.h"
+#include "switches.h"
 
 namespace {
 
@@ -59,8 +60,7 @@ struct mapdit_engine {
     bool generic_attn = false;
     // head_dim 72 with 64 / 128 / 256 tokens (the DiT-XL family): q, k, v leave the QKV GEMM head-major and unnormalised and the
     // attention kernels normalise them while staging (inference: mapdit_attn_cos_fwd_rawqk; training: ..._save keeps the normalised
-    // rows and their scales, and mapdit_attn_cos_bwd_fused applies the Jacobian and writes dqkv).  MAPDIT_ATTN72=0 / MAPDIT_ATTN72_RAW=0
-    // fall back to the split / merge kernels around the attention (A/B runs).
+    // rows and their scales, and mapdit_attn_cos_bwd_fused applies the Jacobian and writes dqkv).
     bool raw72 = false;
     // Off forms of the README's --use-* flags (mapdit_config_t.mp_off; parity unpinned).  Each is a handful of scalars, no kernel:
     //  * plain SiLU = 0.596 x MPSiLU, and every MPSiLU of the network feeds a LINEAR layer (MLP fc2, the modulation linears, the
@@ -210,11 +210,8 @@ const float CA = 0.7f / sqrtf(0.58f), CB = 0.3f / sqrtf(0.58f);   // mp_sum(x, y
 int grad_acc(const mapdit_engine* e) { return e->gacc && !e->ig_only ? 1 : 0; }
 
 // MAPDIT_SIDE_JAC=1 moves the weight-norm Jacobians to a side stream (round 5, measured and NOT the default: see the comment at
-// mapdit_engine::side); read once.
-bool side_jac_wanted() {
-    static const bool on = [] { const char* v = getenv("MAPDIT_SIDE_JAC"); return v && v[0] == '1'; }();
-    return on;
-}
+// mapdit_engine::side).
+bool side_jac_wanted() { return mapdit_switches().side_jac; }
 
 // Lay out every buffer; with base == nullptr this only measures.
 size_t carve(mapdit_engine* e, void* base) {
@@ -479,13 +476,8 @@ void init_dims(mapdit_engine* e) {
     // MFMA attention kernels: head_dim 64 and 64/128/256 tokens; everything else (XL: 72, patch-8: 16 tokens) takes the
     // generic fp32 path of attention_generic.hip
     e->generic_attn = !(e->hd == 64 && (e->T == 64 || e->T == 128 || (e->T >= 256 && e->T % 256 == 0)));
-    {
-        const char* a = getenv("MAPDIT_ATTN72");
-        const char* r = getenv("MAPDIT_ATTN72_RAW");
-        // (beyond 256 tokens the same path: the training forward normalises q, k by a pass of its own first - mapdit_attn_cos_fwd_rawqk_save)
-        e->raw72 = !(a && a[0] == '0') && !(r && r[0] == '0') && e->hd == 72 && (e->T == 64 || e->T == 128 || (e->T >= 256 && e->T % 256 == 0)) &&
-                   e->cfg.precision != MAPDIT_PREC_BF16X3;
-    }
+    // (beyond 256 tokens the same path: the training forward normalises q, k by a pass of its own first - mapdit_attn_cos_fwd_rawqk_save)
+    e->raw72 = e->hd == 72 && (e->T == 64 || e->T == 128 || (e->T >= 256 && e->T % 256 == 0)) && e->cfg.precision != MAPDIT_PREC_BF16X3;
     e->M_max = c.max_batch * e->T;
     const int D = c.hidden;
     e->rot = c.rotation != 0;
@@ -500,10 +492,9 @@ void init_dims(mapdit_engine* e) {
     e->sdpa = (c.mp_off & MAPDIT_OFF_COSINE_ATTN) != 0;
     e->ln = (c.mp_off & MAPDIT_OFF_NO_LAYERNORM) != 0;
     if (e->sdpa) e->raw72 = false;          // (that path normalises q, k while it stages them)
-    {   // 16-bit engines: 16-bit gradient stream between the blocks (MAPDIT_DX16=0: the fp32 stream, for A/B runs; =f: fp16 engine only)
-        const char* v = getenv("MAPDIT_DX16");
-        e->dx16 = c.precision != MAPDIT_PREC_BF16X3 && !(v && v[0] == '0') && (e->f16 || !(v && v[0] == 'f'));
-    }
+    // 16-bit engines: 16-bit gradient stream between the blocks (MAPDIT_DX16=0: the fp32 stream; =f: fp16 engine only)
+    const int dx16 = mapdit_switches().dx16;
+    e->dx16 = c.precision != MAPDIT_PREC_BF16X3 && dx16 != 0 && (e->f16 || dx16 != 2);
     e->MW = (e->rot ? 5 : 6) * D;
     if (e->rot) { e->o_sha = 0; e->o_sca = D / 2; e->o_ga = D / 2 + D; e->o_shm = D / 2 + 2 * D; e->o_scm = 3 * D; e->o_gm = 4 * D; }
     else { e->o_sha = 0; e->o_sca = D; e->o_ga = 2 * D; e->o_shm = 3 * D; e->o_scm = 4 * D; e->o_gm = 5 * D; }
@@ -576,9 +567,10 @@ int pick_split_k(int rows, int cols, int K, long max_slabs) {
     const int units = K / 64;
     // One full round of the chip (256 CUs x 1 workgroup of the 256^2 kernel, x 2 of the 128^2 kernel): every block
     // gets the longest possible K loop and there is no partially filled tail round.  Slab ranges may be uneven.
-    // (MAPDIT_SPLITK_SLOTS128 = workgroups a split launch of the 128^2 kernel aims at, default 512 = two per CU: A/B runs, round 5)
-    static const int slots128 = [] { const char* v = getenv("MAPDIT_SPLITK_SLOTS128"); return v && atoi(v) > 0 ? atoi(v) : 512; }();
-    long want = (edge == 256 ? 256 : slots128) / tiles;
+    // (the 128^2 kernel at two per CU: aiming at 384 / 256 / 768 workgroups cost +0.36 / +1.4 / +0.4 ms at 32 samples per GPU,
+    //  profiles/r05_splitk_slots_sweep.log)
+    constexpr int kSlots256 = 256, kSlots128 = 512;
+    long want = (edge == 256 ? kSlots256 : kSlots128) / tiles;
     if (want > max_slabs) want = max_slabs;
     if (want > units / 4) want = units / 4;                             // keep >= 4 K-tiles per block
     return want < 1 ? 1 : (int)want;
@@ -605,7 +597,7 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
     // separate pass move 16, and wins at every size it applies to (bf16 step at 256 / 128 / 64 samples, same box: 45.10 -> 44.43,
     // 25.59 -> 25.38, 15.00 -> 14.75 ms): default for the engines that run the 16-bit stream.  MAPDIT_FUSED_RMB=0 switches it off,
     // =1 switches it on for fp32 streams up to 32,768 rows (round 2's form), =2 without the row limit.
-    static const int fuse_env = [] { const char* v = getenv("MAPDIT_FUSED_RMB"); return v ? (v[0] - '0') : -1; }();
+    const int fuse_env = mapdit_switches().fused_rmb;
     const bool no_fuse = fuse_env == 0 || (fuse_env < 0 && !e->dx16);
     const bool any_m = fuse_env == 2 || (fuse_env < 0 && e->dx16);
     const int D = e->D;
@@ -650,9 +642,8 @@ int dx_resid_mod_bwd(mapdit_engine* e, int M, int K, const bf16_t* dy, int ld_dy
     // the half-empty fifth column -> the 128^2 kernel, which has no reduce epilogue): plain stores + the separate pass over all 1152
     // columns.  Now the fused epilogue takes the first D - 128 columns and the last 128 go through the 128^2 kernel's plain store and
     // the pass restricted to that column range (mapdit_resid_mod_bwd_t.ldx); the scalar-gain partials of both parts are summed in
-    // order.  MAPDIT_RMB_NSPLIT=0 switches it off (A/B).
-    static const bool nsplit_env = [] { const char* v = getenv("MAPDIT_RMB_NSPLIT"); return !(v && v[0] == '0'); }();
-    if (nsplit_env && !no_fuse && e->T % 64 == 0 && 256 % e->T == 0 && K % 64 == 0 && (M <= 32768 || any_m) && D % 256 == 128 && D >= 384 &&
+    // order.
+    if (!no_fuse && e->T % 64 == 0 && 256 % e->T == 0 && K % 64 == 0 && (M <= 32768 || any_m) && D % 256 == 128 && D >= 384 &&
         mapdit_gemm_tile_size_k(M, D, K, 0) != 256 && mapdit_gemm_tile_size_k(M, D - 128, K, 0) == 256) {
         const int D1 = D - 128;
         mapdit_epilogue_t ep; memset(&ep, 0, sizeof(ep));
@@ -729,7 +720,7 @@ int dw_group_split(mapdit_engine* e, int K) {
     if (e->dw_group_K == K) return e->dw_group_split;
     e->dw_group_K = K;
     e->dw_group_split = 0;
-    static const int mode = [] { const char* v = getenv("MAPDIT_DW_GROUP"); return v ? atoi(v) : 1; }();
+    const int mode = mapdit_switches().dw_group;
     if (mode == 0 || K % 64 != 0 || e->side_jac || e->cfg.precision == MAPDIT_PREC_BF16X3) return 0;
     const int which[4] = {MAPDIT_B_FC2, MAPDIT_B_FC1, MAPDIT_B_QKV, MAPDIT_B_PROJ};
     const double nkt = K / 64;

@@ -19,11 +19,10 @@
 // consecutive columns of one output row; the tile is then bounced through LDS (aliasing the staging
 // buffers) so the epilogue runs on whole 8-column row chunks with fully coalesced 16/32-byte accesses.
 // Block ids are remapped so each XCD (private L2) works on a contiguous band of output tiles.
-#include <stdarg.h>
 #include <type_traits>
-#include <stdio.h>
 
 #include "common.h"
+#include "switches.h"
 
 MD_NS_OPEN
 
@@ -153,6 +152,9 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 // keep: the tensor is the NEXT kernel's operand (e.g. the modulated activations a RESID epilogue hands to the following GEMM, a dX
 // result the residual backward reads at once): a plain store, so that it is still in the L2 / Infinity Cache when that kernel
 // starts - measured in the step: fc1 380 -> 358 us with its A operand stored that way by the preceding epilogue (round 4).
+// Only the modulated activations of RESID leave that way: plain stores of STORE_BF16 / QKV_HEADS / SILU2_GRAD / MUL_AUX results measured
+// no effect on the step.  (The functors keep their run-time `keep` fields; the entry point passes these.)
+constexpr int kKeepResidXm = 1, kKeepStoreBf16 = 0, kKeepQkvHeads = 0, kKeepSilu2Grad = 0, kKeepMulAux = 0;
 __device__ __forceinline__ void store16_stream(void* p, u32x4_t v, bool keep = false) {
     if (keep) *(u32x4_t*)p = v;
     else __builtin_nontemporal_store(v, (u32x4_t*)p);
@@ -310,7 +312,7 @@ struct EpiResid {
     // rot != 0: the next branch's modulate is the rotation form xm = bf16(xout * nscale + pairswap(xout) * nshift), nscale / nshift =
     // the A / B coefficient rows of mapdit_rot_coef_fwd (pointwise.hip; reference README.md:1-3, parity unpinned); ngain is not read
     int rot;
-    int xm_plain;       // A/B (MAPDIT_RESID_XM_PLAIN=1): xm leaves by plain stores - the next GEMM reads it at once, it should stay cached
+    int xm_plain;       // bit 0 (kKeepResidXm, always set): xm leaves by plain stores - the next GEMM reads it at once, it should stay cached
     struct Aux { float4 x0, x1; };
     struct Tile { float4 g0, g1, c0, c1, h0, h1; float ka, kb; int smp; };     // smp < 0: rows of several samples in the tile
     __device__ __forceinline__ void per_sample(int smp, int n, Tile& t) const {
@@ -371,7 +373,7 @@ struct EpiResid {
         float o[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = __builtin_fmaf(cb * g[i], v[i], ca * x[i]);
-        // A/B (MAPDIT_KEEP bit 32, off): the residual checkpoint by non-temporal stores - fc1 3 us faster, the step 0.2 ms slower (the
+        // Measured (xm_plain bit 1, never set): the residual checkpoint by non-temporal stores - fc1 3 us faster, the step 0.2 ms slower (the
         // next branch's residual read and the residual backward find less of it cached): not used
         if (!U && (xm_plain & 2)) {                          // (U: the default store policies as compile-time facts; fast_ok() checks)
             __builtin_nontemporal_store(f32x4_t{o[0], o[1], o[2], o[3]}, (f32x4_t*)rowptr<U>(xout, m, n, ldo, off));
@@ -959,11 +961,14 @@ extern "C" __global__ void mapdit_debug_set_stamps_kernel(long long* p, int bloc
         if (wave == 0)                                                                              \
             for (int i = 0; i < 8; ++i) g_stamps[2 * STAMP_TILES * STAMP_POINTS + i] = stamp_lds[2 * STAMP_TILES * STAMP_POINTS + i]; \
     }
+// (gemm_mfma256w_kernel: one cycle-counter reading into a new local)
+#define GW_STAMP(VAR) __builtin_amdgcn_sched_barrier(0); const long long VAR = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
 #else
 #define G256_STAMP(PT)
 #define G256_TSTAMP(IDX)
 #define G256_RSTAMP(IDX)
 #define G256_STAMPS_OUT()
+#define GW_STAMP(VAR)
 #endif
 
 template <int SIDE> __device__ __forceinline__ int half_map(int i, int h) {
@@ -1641,9 +1646,6 @@ __device__ __forceinline__ void g256_prologue(const GemmP& p, const TileCoord& c
 // Per epilogue: accumulator tiles between the load of its stream operand and the use (kEpiPrefetch), and whether the LDS round trip of
 // tile r+1 is issued ahead of the arithmetic of tile r (kEpiPipeline: a second set of chunk registers).  RESID keeps 24 registers
 // of per-column operands and 8 per chunk of residual stream: both at 2 / true spill (216 bytes of scratch per lane).
-#ifndef MAPDIT_EPI_PD_AUX
-#define MAPDIT_EPI_PD_AUX 2
-#endif
 template <class Epi> constexpr bool kWaveEpilogue = true;          // launch(): take the round-4 kernel for this epilogue
 template <class Epi> constexpr bool kWaveEpilogueAnyK = true;      // ... whatever K is (false: only up to K = 1024 per workgroup)
 template <> constexpr bool kWaveEpilogue<EpiResid> = false;
@@ -1652,8 +1654,7 @@ template <> constexpr bool kWaveEpilogueAnyK<EpiStoreBf16> = false;
 template <class Epi> constexpr int kEpiPrefetch = 2;
 template <class Epi> constexpr bool kEpiPipeline = true;
 template <> constexpr int kEpiPrefetch<EpiResid> = 1;
-template <> constexpr int kEpiPrefetch<EpiMulAux> = MAPDIT_EPI_PD_AUX;      // (4 measured no faster than 2: 900 vs 920 TFLOP/s on fc2-dX)
-template <> constexpr int kEpiPrefetch<EpiDSilu> = MAPDIT_EPI_PD_AUX;
+// (EpiMulAux, EpiDSilu: 4 measured no faster than 2 - 900 vs 920 TFLOP/s on fc2-dX)
 template <> constexpr bool kEpiPipeline<EpiResid> = false;
 // INTERIOR: the tile lies inside the result (every hot shape: M, N multiples of 256) - no predicate anywhere, so the whole
 // epilogue is one basic block and the LDS round trip of accumulator tile r+1 is issued before the arithmetic of tile r (LDS
@@ -1749,9 +1750,6 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma256w_kernel(GemmP p, Epi epi)
     // epilogue}, tiles done; written once at the end: g_wg_times[bid][8 * (wave / 4) + 0..4]   (tools/gemm_phases.py)
     long long ph_[4] = {0, 0, 0, 0};
     int ph_tiles_ = 0;
-#define GW_STAMP(VAR) __builtin_amdgcn_sched_barrier(0); const long long VAR = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
-#else
-#define GW_STAMP(VAR)
 #endif
     for (;;) {
         int tid_ = threadIdx.x;
@@ -1875,8 +1873,6 @@ __global__ void gemm_simple_kernel(const bf16_t* __restrict__ A, long sam, long 
 
 MD_NS_CLOSE
 
-// Output tile edge the dispatcher uses for an [M, N] result: 256 (8-wave staggered kernel, one workgroup per CU) for
-// token-sized problems, 128 for small ones (conditioning path, final linear).  Exposed so callers can size split-K.
 #ifdef MAPDIT_GEMM_STAMPS
 extern "C" void mapdit_debug_set_stamps(long long* p) {
     hipLaunchKernelGGL(mapdit_debug_set_stamps_kernel, dim3(1), dim3(1), 0, 0, p, -1);
@@ -1891,107 +1887,6 @@ extern "C" void mapdit_debug_set_stamps_block(long long* p, int block) {      //
     (void)hipDeviceSynchronize();
 }
 #endif
-
-// The K-loop / kernel selector of the 256^2 path (MAPDIT_GEMM_PHASES, mapdit_gemm_tuning): 2 = default, 4 = one quadrant per phase,
-// 6 = the wave-private-epilogue kernel for every epilogue, 7 = the shared-image kernel for every epilogue; anything else is 2.
-static int gemm_phases_arg(int v) { return v == 4 || v == 6 || v == 7 ? v : 2; }
-
-// A/B switches for benchmarking, read from the environment ONCE (the first launch): the launch path makes no getenv calls.
-// (One instance in the library: the bf16 build of this file owns it, the fp16 build refers to it.)
-struct GemmEnv {
-    int tile = 0;        // MAPDIT_GEMM_TILE   = 128 | 256: force the tile edge
-    int phases = 2;      // MAPDIT_GEMM_PHASES = 4: the quadrant-per-phase schedule; 7: the round-3 kernel (shared-image epilogue, no prefetch across tiles)
-    long band = 0;       // MAPDIT_GEMM_BAND   = column tiles per band (0: derived from K)
-    int old_tile_rule = 0;   // MAPDIT_GEMM_TILE_RULE=old
-    int persist = 256;       // MAPDIT_GEMM_PERSIST = workgroups of the persistent 256^2 launch (0: one workgroup per tile)
-    // MAPDIT_KEEP = bit mask of epilogue outputs that leave by plain instead of non-temporal stores (they are the next kernel's
-    // operand): 1 RESID xm, 2 STORE_BF16 out, 4 QKV_HEADS q^ k^ v, 8 SILU2_GRAD act, 16 MUL_AUX out; 32: RESID xout NON-temporal
-    int keep_mask = 1;
-    int nsplit = 1;          // MAPDIT_GEMM_NSPLIT = 0: no column split of results whose width is an odd multiple of 128
-    int fast_epi = 1;        // MAPDIT_GEMM_FE = 0: never the straight-line epilogue instantiation (RESID; A/B)
-    int band768 = 3;         // MAPDIT_GEMM_BAND768 = column tiles per band of the K <= 768 forward (NT) GEMMs (fc1, QKV)
-    int dma_fast = 1;        // MAPDIT_GEMM_DMA = 0: never the scalar-base staging of interior tiles (A/B)
-    int stagger = -1;        // MAPDIT_GEMM_STAGGER = late start of every second workgroup, units of 8,128 cycles (persistent launches); -1: by epilogue
-    GemmEnv() {
-        if (const char* e = getenv("MAPDIT_GEMM_PERSIST")) persist = atoi(e);
-        if (const char* e = getenv("MAPDIT_KEEP")) keep_mask = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_NSPLIT")) nsplit = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_STAGGER")) stagger = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_BAND768")) band768 = atoi(e) > 0 ? atoi(e) : 3;
-        if (const char* e = getenv("MAPDIT_GEMM_FE")) fast_epi = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_DMA")) dma_fast = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_TILE_RULE")) old_tile_rule = e[0] == 'o';
-        if (const char* e = getenv("MAPDIT_GEMM_TILE")) tile = atoi(e);
-        if (const char* e = getenv("MAPDIT_GEMM_PHASES")) phases = gemm_phases_arg(atoi(e));
-        if (const char* e = getenv("MAPDIT_GEMM_BAND")) band = atol(e);
-    }
-};
-GemmEnv& mapdit_gemm_env_ref();
-static GemmEnv& gemm_env() { return mapdit_gemm_env_ref(); }
-extern "C" int mapdit_gemm_dma_fast(int layout, int M, int N, int K, int lda, int ldb, int tile);
-#if MAPDIT_DT == 0
-GemmEnv& mapdit_gemm_env_ref() {
-    static GemmEnv env;
-    return env;
-}
-// Tuning hook of the benchmarking tools (tools/gemm_bench.py, gemm_band_sweep.py): overrides what the environment said.
-// tile: 0 = by shape | 128 | 256;  phases: 2 | 4 | 6 | 7 (gemm_phases_arg);  band: 0 = derived from K.  Not for use while launches are in flight elsewhere.
-extern "C" void mapdit_gemm_tuning(int tile, int phases, long band) {
-    GemmEnv& e = gemm_env();
-    e.tile = tile;
-    e.phases = gemm_phases_arg(phases);
-    e.band = band;
-}
-
-// 256 (8 waves, one workgroup per CU) for results that give most of the chip a tile, 128 (4 waves, two per CU) otherwise:
-//  * plain launches: fewer than 128 tiles of 256^2 leave more than half the CUs idle (e.g. [8192, 768] = 96 tiles at a per-GPU
-//    batch of 32), while the 128^2 kernel has 4x the tiles for 2x the slots; likewise a launch of little more than one round of the
-//    chip (257 ... 320 tiles: the second round runs at most a quarter full - [8192, 2304] = 288 tiles: 46 vs 59 us);
-//  * split-K launches fill one round through the K cut either way: there the 128^2 kernel wins for the smallest outputs
-//    ([768, 768]: 781 vs 704 TFLOP/s; [3072, 768]: 694 vs 812) and when the cut leaves a workgroup fewer than 24 K-tiles against
-//    the 256^2 tile's fixed cost of ~8 K-tiles (fill + fp32 epilogue; [3072, 768] over 8,192 rows: 52 vs 63 us).
-// A finer occupancy model (useful tile area x last-round occupancy x a per-flop rate of the 128^2 kernel) fitted the isolated
-// launches of tools/gemm_bench.py and LOST in the step at 64 and 128 samples and on DiT-XL/2 (+0.1 ... +0.3 ms): not used.
-// K = 0: reduction length not known (the older entry points).
-extern "C" int mapdit_gemm_tile_size_k(int M, int N, int K, int split_k_launch) {
-    const int force = gemm_env().tile;
-    if (force == 128 || force == 256) return force;
-    if (!(M >= 512 && N >= 256)) return 128;
-    const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
-    if (split_k_launch) {
-        if (t256 < 12) return 128;
-        // round 4: both edges odd multiples of 128 (DiT-XL's [1152, 1152] weight gradients: 25 tiles of 256^2 for 20.25 tiles of
-        // work) - below 85 % useful tile area the 128^2 kernel wins (796 vs 669 TFLOP/s; [4608, 1152] at 90 %: 910 vs 889, left alone)
-        if (!gemm_env().old_tile_rule && (double)M * N < 0.85 * (double)t256 * 65536.0) return 128;
-        if (K > 0 && !gemm_env().old_tile_rule) {
-            const long slabs = 256 / t256 > 0 ? 256 / t256 : 1;
-            if ((K / 64) / slabs < 24) return 128;
-        }
-        return 256;
-    }
-    if (t256 < 128) return 128;
-    if (!gemm_env().old_tile_rule && t256 > 256 && t256 <= 320) return 128;
-    return 256;
-}
-
-// The scalar-base staging (DmaCtx) keeps every offset of an operand but its 64-bit base in 32 bits - the lane offset, the steps between
-// pieces and halves, the advance per K-tile (64 rows of a K-major operand): operands whose extent, rows x ld x 2 bytes, does not fit an
-// unsigned 32-bit byte offset stay on the 64-bit lane addresses of stage_half / stage_tile.
-extern "C" int mapdit_gemm_dma_extent_ok(long rows, long ld) {
-    return rows > 0 && ld > 0 && ld < (1l << 31) && rows < (1l << 32) && (unsigned long)rows * (unsigned long)ld * 2ul < (1ul << 32);
-}
-// 1 if a launch on tiles of `tile` rows (256: 256 x 256, 128: 128 x 128, 64: 64 x 128) stages that way: every tile inside the result (no
-// row or column clamp), no K tail, both operands within the 32-bit extent.  Anything else keeps stage_half / stage_tile.
-extern "C" int mapdit_gemm_dma_fast(int layout, int M, int N, int K, int lda, int ldb, int tile) {
-    if (layout < MAPDIT_NT || layout > MAPDIT_TN || (tile != 256 && tile != 128 && tile != 64)) return 0;
-    const int tn = tile == 256 ? 256 : 128;
-    if (M <= 0 || N <= 0 || K <= 0 || M % tile != 0 || N % tn != 0 || K % 64 != 0) return 0;
-    const bool a_kmaj = layout == MAPDIT_TN, b_kmaj = layout != MAPDIT_NT;
-    return mapdit_gemm_dma_extent_ok(a_kmaj ? K : M, lda) && mapdit_gemm_dma_extent_ok(b_kmaj ? K : N, ldb);
-}
-extern "C" int mapdit_gemm_tile_size_ex(int M, int N, int split_k_launch) { return mapdit_gemm_tile_size_k(M, N, 0, split_k_launch); }
-extern "C" int mapdit_gemm_tile_size(int M, int N) { return mapdit_gemm_tile_size_ex(M, N, 0); }
-#endif   // MAPDIT_DT == 0
 
 MD_NS_OPEN
 
@@ -2020,10 +1915,9 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
     // kernel on the last 128 (same epilogue object: it indexes by absolute column, the second launch hands it n + N - 128; B points at that
     // column block).  DiT-XL/2 at 64 samples: 76.3 -> 74.5 ms.  NOT for tall results: at 65,536 rows the second launch re-streams the whole
     // A operand for 128 columns (DiT-S/2 19.9 -> 20.1 ms, DiT-XL/2 sampling 62.8 -> 64.3 ms with the split everywhere).
-    // MAPDIT_GEMM_NSPLIT=0 switches it off (A/B).
     if constexpr (!kReduce<Epi>) {
-        if (!force128 && n_off == 0 && split_k == 1 && gemm_env().nsplit && N % 256 == 128 && N >= 384 && K % BKT == 0 &&
-            gemm_env().tile != 128 && M >= 512 && (long)cdiv(M, 256) * ((N - 128) / 256) >= 192 &&
+        if (!force128 && n_off == 0 && split_k == 1 && N % 256 == 128 && N >= 384 && K % BKT == 0 &&
+            mapdit_switches().gemm_tile != 128 && M >= 512 && (long)cdiv(M, 256) * ((N - 128) / 256) >= 192 &&
             (long)cdiv(M, 256) * ((N - 128) / 256) <= 256 && !(((uintptr_t)A | (uintptr_t)B) & 15) &&
             lda % 8 == 0 && ldb % 8 == 0 && !(a_kmaj && M % 8 != 0)) {
             // (every condition of the MFMA path below holds for BOTH halves: the non-MFMA fallback knows no column offset, so a split
@@ -2059,10 +1953,10 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
     if (mfma && !force128 && mapdit_gemm_tile_size_k(M, N, K, split_k > 1) == 256) {
         GemmP p{A, B, lda, ldb, M, N, K, cdiv(N, BN2), 0, split_k, 0, 2, 0, 0};
         p.tiles = cdiv(M, BM2) * p.tiles_n;
-        p.phases = gemm_env().phases;
+        p.phases = mapdit_switches().gemm_phases;
         // B sub-panel of one band = band * 256 columns * K * 2 bytes: keep it within ~2.5 MiB of the 4 MiB L2
-        const bool be = gemm_env().band > 0;
-        long band = be ? gemm_env().band : (long)(2.5 * 1024 * 1024) / ((long)BN2 * (K / split_k) * 2);
+        const bool be = mapdit_switches().gemm_band > 0;
+        long band = be ? mapdit_switches().gemm_band : (long)(2.5 * 1024 * 1024) / ((long)BN2 * (K / split_k) * 2);
         // every band re-reads the A panels once more, so banding only pays with wide bands: fewer than 4 column tiles
         // per band (large K) -> one full-width band (measured: band = 1 at K = 3072 costs 25 %)
         if (!be && band < 4) band = p.tiles_n;
@@ -2072,22 +1966,22 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
         // 380 us): the XCD's share of the tile order (an eighth of it) then lies inside one band, and the A panels of its 32
         // concurrent tiles (11 x 393 KB) are what the L2 keeps, the three B tiles with them.  The NN dX GEMM of the same shape
         // (fc2-dX, 346 vs 355 us) keeps six.
-        // (MAPDIT_GEMM_BAND768 = another width for exactly this rule: A/B runs, round 5)
-        if (!be && layout == MAPDIT_NT && split_k == 1 && K <= 768 && p.tiles_n >= 6 && p.tiles_n % gemm_env().band768 == 0) band = gemm_env().band768;
+        constexpr int kBand768 = 3;
+        if (!be && layout == MAPDIT_NT && split_k == 1 && K <= 768 && p.tiles_n >= 6 && p.tiles_n % kBand768 == 0) band = kBand768;
         if (band < 1 || band > p.tiles_n) band = p.tiles_n;
         p.band = (int)band;
         int grid = p.tiles * split_k;
         // one workgroup per CU looping over its tiles, from three rounds of the chip on (fewer: a static split of 1.5 rounds over
         // 256 workgroups only loses to the dispatcher: +0.05 ms on the step at 32 samples per GPU)
-        if (gemm_env().persist && grid >= 3 * gemm_env().persist) {
-            grid = gemm_env().persist;
+        constexpr int kPersistGrid = 256;
+        if (grid >= 3 * kPersistGrid) {
+            grid = kPersistGrid;
             // RESID (10 B per result element of residual stream against 2 B for a plain store) is the launch whose epilogues are HBM
             // bursts: isolated, same box, proj 153 -> 142 us and fc2 303 -> 298 us with two units (1, 3, 4, 6, 8 units and four
             // populations: less or nothing); QKV heads, SiLU + derivative and the saved-factor product lose 1-5 % (VALU-bound
             // epilogues: the late half just ends late).
             // (the fused residual/modulate backward, the other stream-heavy epilogue: step +0.1 ... +0.3 ms with 1-4 units)
-            const int sg = gemm_env().stagger;
-            p.stagger = sg >= 0 ? sg : (std::is_same<Epi, EpiResid>::value ? 2 : 0);
+            p.stagger = std::is_same<Epi, EpiResid>::value ? 2 : 0;
         }
         // Kernel family.  Default: the round-4 kernel (wave-private epilogue, next tile's prologue under it) where it measured faster -
         // the epilogues that are arithmetic (SiLU, per-head normalisation, the saved-factor product): +2 ... +11 % - and the plain bf16
@@ -2100,12 +1994,12 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
             use_w = p.phases == 6 || (p.phases == 2 && kWaveEpilogue<Epi> && (kWaveEpilogueAnyK<Epi> || K / split_k <= 1024));
         if (p.phases == 7 || p.phases == 6) p.phases = 2;       // (both only choose the kernel: its K loop is the two-phase one)
         // The straight-line epilogue (FE) of the shared-image kernel where the launcher can promise what it assumes: every tile inside
-        // the result and, for RESID, inside one sample.  MAPDIT_GEMM_FE=0 keeps the guarded form (A/B).
+        // the result and, for RESID, inside one sample; the guarded form otherwise.
         bool fe = false;
         if constexpr (kFastEpi<Epi>)
-            fe = gemm_env().fast_epi && M % BM2 == 0 && N % BN2 == 0 && epi.fast_ok();
+            fe = M % BM2 == 0 && N % BN2 == 0 && epi.fast_ok();
         // FAST: the K loop stages from a scalar base and one lane offset per operand (DmaCtx) - interior tiles only, never with a K tail
-        const bool fast = gemm_env().dma_fast && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 256);
+        const bool fast = mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 256);
         auto go = [&](auto tail, auto fst) {
             constexpr bool TAIL = decltype(tail)::value, FAST = decltype(fst)::value;
             with_operand_kinds(layout, [&](auto ak, auto bk) {
@@ -2129,14 +2023,13 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
         else go(std::false_type(), std::false_type());
     } else if (mfma) {
         // Round 5: few 128^2 tiles (DiT-XL's 128-column strips: 128 or fewer workgroups on 256 CUs) -> 64-row tiles, twice the workgroups, the
-        // same bits (gemm_mfma64_kernel).  For the epilogues the strips carry.  MAPDIT_GEMM_TILE64=0 switches it off (A/B).
+        // same bits (gemm_mfma64_kernel).  For the epilogues the strips carry.
         if constexpr (std::is_same<Epi, EpiResid>::value || std::is_same<Epi, EpiStoreBf16>::value) {
-            static const bool t64_env = [] { const char* v = getenv("MAPDIT_GEMM_TILE64"); return !(v && v[0] == '0'); }();
             const long t128 = (long)cdiv(M, BM) * cdiv(N, BN);
-            if (t64_env && !a_kmaj && !ktail && split_k == 1 && t128 <= 160 && M >= 256) {
+            if (!a_kmaj && !ktail && split_k == 1 && t128 <= 160 && M >= 256) {
                 GemmP p{A, B, lda, ldb, M, N, K, cdiv(N, BN), 0, 1, 0, 4, n_off, 0};
                 p.tiles = cdiv(M, 64) * p.tiles_n;
-                const bool fast = gemm_env().dma_fast && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 64);
+                const bool fast = mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 64);
                 with_operand_kinds(layout, [&](auto, auto bk) {       // (A is row-major here)
                     if (fast) hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi, true>), dim3(p.tiles), dim3(256), 0, st, p, epi);
                     else hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
@@ -2157,7 +2050,7 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
                 return MAPDIT_OK;
             }
         }
-        const bool fast = gemm_env().dma_fast && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 128);
+        const bool fast = mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 128);
         with_operand_kinds(layout, [&](auto ak, auto bk) {
             if (fast) hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi, false, true>), dim3(grid), dim3(256), 0, st, p, epi);
             else hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
@@ -2178,19 +2071,6 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
 
 MD_NS_CLOSE
 
-#if MAPDIT_DT == 0
-// ---- error plumbing (shared) ---------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void mapdit_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-extern "C" const char* mapdit_last_error(void) { return g_err; }
-extern "C" int mapdit_abi_version(void) { return 5; }
-#endif
-
 // Several TN products out_i[M_i, N_i] (fp32, split_k slabs slab_stride_i apart) = alpha_i * A_i^T B_i over the SAME K rows, one launch of the
 // 256^2 kernel (gemm_mfma256_group_kernel).  Every item must be on the MFMA path (K % 64 == 0, M_i, N_i, lda_i, ldb_i multiples of 8,
 // 16-byte aligned operands); the same accumulation order as a single launch with the same split_k: the same bits.
@@ -2199,7 +2079,7 @@ extern "C" int MD_SYM_GEMM_GROUP(int n, const mapdit_gemm_group_item_t* items, i
     MD_CHECK(K > 0 && K % BKT == 0 && split_k >= 1 && split_k <= K / BKT, "gemm_group: K=%d must be a multiple of 64 and split_k=%d <= K / 64", K, split_k);
     GroupArgs g{};
     g.n = n;
-    bool fast = gemm_env().dma_fast != 0;
+    bool fast = true;
     for (int i = 0; i < n; ++i) {
         const mapdit_gemm_group_item_t& it = items[i];
         MD_CHECK(it.A && it.B && it.out && it.M > 0 && it.N > 0, "gemm_group: item %d: null / empty", i);
@@ -2237,7 +2117,7 @@ extern "C" int MD_SYM_GEMM(int layout, int M, int N, int K, const uint16_t* A, i
     MD_CHECK(e->split_k <= 1 || e->kind == MAPDIT_EPI_STORE_F32, "gemm: split_k is only available with EPI_STORE_F32");
     switch (e->kind) {
         case MAPDIT_EPI_STORE_BF16:
-            return launch(layout, M, N, K, A, lda, B, ldb, EpiStoreBf16{(bf16_t*)e->out, e->ldo, e->alpha, (gemm_env().keep_mask >> 1) & 1}, st);
+            return launch(layout, M, N, K, A, lda, B, ldb, EpiStoreBf16{(bf16_t*)e->out, e->ldo, e->alpha, kKeepStoreBf16}, st);
         case MAPDIT_EPI_STORE_F32:
             MD_CHECK(e->split_k <= 1 || !e->accumulate, "gemm: split_k with accumulate is not supported");
             return launch(layout, M, N, K, A, lda, B, ldb,
@@ -2257,14 +2137,14 @@ extern "C" int MD_SYM_GEMM(int layout, int M, int N, int K, const uint16_t* A, i
             return launch(layout, M, N, K, A, lda, B, ldb,
                           EpiResid{(bf16_t*)e->out, (const float*)e->aux, (float*)e->out2, e->gate, e->ldo, e->ldg,
                                    e->rows_per_sample, e->alpha, e->beta, (bf16_t*)e->out3, e->shift2, e->scale2, e->gain2,
-                                   e->ld2, e->rot2, (gemm_env().keep_mask & 1) | ((gemm_env().keep_mask >> 5) & 1) << 1}, st);
+                                   e->ld2, e->rot2, kKeepResidXm}, st);
         case MAPDIT_EPI_SILU2_GRAD:
             MD_CHECK(e->out2, "gemm: SILU2_GRAD needs out2");
-            if (e->out) return launch(layout, M, N, K, A, lda, B, ldb, EpiSilu2GradT<true>{(bf16_t*)e->out, (bf16_t*)e->out2, e->ldo, (gemm_env().keep_mask >> 3) & 1}, st);
-            return launch(layout, M, N, K, A, lda, B, ldb, EpiSilu2GradT<false>{(bf16_t*)e->out, (bf16_t*)e->out2, e->ldo, (gemm_env().keep_mask >> 3) & 1}, st);
+            if (e->out) return launch(layout, M, N, K, A, lda, B, ldb, EpiSilu2GradT<true>{(bf16_t*)e->out, (bf16_t*)e->out2, e->ldo, kKeepSilu2Grad}, st);
+            return launch(layout, M, N, K, A, lda, B, ldb, EpiSilu2GradT<false>{(bf16_t*)e->out, (bf16_t*)e->out2, e->ldo, kKeepSilu2Grad}, st);
         case MAPDIT_EPI_MUL_AUX:
             MD_CHECK(e->aux, "gemm: MUL_AUX needs aux");
-            return launch(layout, M, N, K, A, lda, B, ldb, EpiMulAux{(bf16_t*)e->out, (const bf16_t*)e->aux, e->ldo, (gemm_env().keep_mask >> 4) & 1}, st);
+            return launch(layout, M, N, K, A, lda, B, ldb, EpiMulAux{(bf16_t*)e->out, (const bf16_t*)e->aux, e->ldo, kKeepMulAux}, st);
         case MAPDIT_EPI_DSILU:
             MD_CHECK(e->aux, "gemm: DSILU needs aux (pre-activation)");
             return launch(layout, M, N, K, A, lda, B, ldb, EpiDSilu{(bf16_t*)e->out, (const bf16_t*)e->aux, e->ldo}, st);
@@ -2302,7 +2182,7 @@ extern "C" int MD_SYM_GEMM(int layout, int M, int N, int K, const uint16_t* A, i
             MD_CHECK(N % 192 == 0 && M % e->rows_per_sample == 0, "gemm: QKV_HEADS needs N = 3 * 64 * heads, M = samples * rows_per_sample");
             const int H = N / 192;
             return launch(layout, M, N, K, A, lda, B, ldb,
-                          EpiQkvHeads{(gemm_env().keep_mask >> 2) & 1, (bf16_t*)e->out, (bf16_t*)e->out2, (bf16_t*)e->out3, (float*)e->out4, e->rows_per_sample, H,
+                          EpiQkvHeads{kKeepQkvHeads, (bf16_t*)e->out, (bf16_t*)e->out2, (bf16_t*)e->out3, (float*)e->out4, e->rows_per_sample, H,
                                       (long)M * H,
                                       (e->rows_per_sample & (e->rows_per_sample - 1)) == 0 ? __builtin_ctz(e->rows_per_sample) : -1}, st);
         }

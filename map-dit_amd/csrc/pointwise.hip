@@ -665,10 +665,7 @@ extern "C" int MD_SYM(resid_mod_bwd)(const mapdit_resid_mod_bwd_t* a, void* stre
             Z *= 2;
     }
     p.part = Z > 1 ? a->part_scratch : nullptr;
-#ifndef MAPDIT_RMB_WIDE
-#define MAPDIT_RMB_WIDE 1
-#endif
-    const bool wide = MAPDIT_RMB_WIDE && Z == 1 && a->D % 256 == 0;          // 256 columns per block: 1-KiB row segments
+    const bool wide = Z == 1 && a->D % 256 == 0;          // 256 columns per block: 1-KiB row segments
     const int cblocks = wide ? a->D / 256 : a->D / 128;
     if (wide) {
         if (p.rot) hipLaunchKernelGGL((resid_mod_bwd_kernel<true, 64>), dim3(a->n_samples, cblocks, 1), dim3(256), 0, (hipStream_t)stream, p);
@@ -752,14 +749,7 @@ extern "C" int mapdit_reduce_partials(const float* part, int count, float* out, 
 }
 #endif
 
-extern "C" int MD_SYM(qkv_split_generic)(const uint16_t*, int, int, int, int, uint16_t*, uint16_t*, uint16_t*, void*);
-extern "C" int MD_SYM(qkv_merge_bwd_generic)(const uint16_t*, int, int, int, int, const uint16_t*, const uint16_t*, const uint16_t*,
-                                            uint16_t*, void*);
-
-// head_dim 72 (DiT-XL): coalesced chunk-per-thread kernels of attention72.hip
-int MD_SYM(qkv_split72)(const uint16_t*, int, int, int, uint16_t*, uint16_t*, uint16_t*, void*);
-int MD_SYM(qkv_merge_bwd72)(const uint16_t*, int, int, int, const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, void*);
-
+// head_dim 72 (DiT-XL): coalesced chunk-per-thread kernels of attention72.hip; other shapes: attention_generic.hip
 extern "C" int MD_SYM(qkv_split)(const uint16_t* qkv, int B, int T, int H, int head_dim, uint16_t* qn, uint16_t* kn,
                                 uint16_t* v, void* stream) {
     MD_CHECK(qkv && qn && kn && v, "qkv_split: null argument");

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B builds of one translation unit of libmapdit_hip.so with an extra -D flag, linked against the objects of the current build:
-#   tools/build_probe.sh attention SB_PROBE 1 2 3      ->  tools/_ab/lib_SB_PROBE1.so ...   (run with MAPDIT_LIB=<that file>)
+#   tools/build_probe.sh attention SB_STAMP 1           ->  tools/_ab/lib_SB_STAMP1.so       (run with MAPDIT_LIB=<that file>)
 set -e
 cd "$(dirname "$0")/../map-dit_amd/csrc"
 tu=$1; flag=$2; shift 2

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timeline of the 256x256 GEMM's K-tile loop from in-kernel shader-clock stamps (guide: 'In-kernel stamps').
 
-Builds gemm.hip with -DMAPDIT_GEMM_STAMPS into tools/_stamps/libgemm_stamps.so (a separate library; the product library has
+Builds gemm.hip (and switches.hip, the host-only code it calls) with -DMAPDIT_GEMM_STAMPS into tools/_stamps/libgemm_stamps.so (a separate library; the product library has
 no instrumentation), runs one NN GEMM [65536,3072] x [3072,768] and one TN GEMM, and prints, for a wave of each of the two
 wave groups, the cycles spent per K-tile in: LOAD A (fragment reads + DMA issue | DMA wait | barrier), MFMA A, LOAD B, MFMA B.
 
@@ -21,9 +21,9 @@ SO = os.path.join(OUT, "libgemm_stamps.so")
 
 def build():
     os.makedirs(OUT, exist_ok=True)
-    src = os.path.join(ROOT, "map-dit_amd", "csrc", "gemm.hip")
+    src = [os.path.join(ROOT, "map-dit_amd", "csrc", f) for f in ("gemm.hip", "switches.hip")]
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=fast",
-                           "-fno-slp-vectorize", "-DMAPDIT_GEMM_STAMPS", "-Wno-unused-function", src, "-o", SO])
+                           "-fno-slp-vectorize", "-DMAPDIT_GEMM_STAMPS", "-Wno-unused-function", *src, "-o", SO])
     print("built", SO)
 
 

@@ -4,7 +4,8 @@
 Picks the K-th last interval between two adam_ema_kernel dispatches (default: the last complete one) and prints
   * per kernel family AND launch geometry (grid size tells proj from fc2 etc.): launches, average / total duration;
   * the time the GPU had no kernel in flight (gaps), and the time two kernels were in flight together (side-stream overlap);
-  * with --full every dispatch: start offset, duration, gap to the previous end, queue, short name.
+  * with --full every dispatch: start offset, duration, gap to the previous end, queue, workgroups, workgroup size, short name
+    (from "grid" on a line carries no time: the ordered launch list that two builds of the library can be diffed by).
 """
 import csv
 import re
@@ -30,7 +31,7 @@ def main():
     rows = []
     for r in csv.DictReader(open(path)):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1),
-                     r["Queue_Id"], int(r["VGPR_Count"])))
+                     r["Queue_Id"], int(r["VGPR_Count"]), int(r["Workgroup_Size_X"])))
     rows.sort()
     adam = [i for i, r in enumerate(rows) if "adam_ema_kernel" in r[2] or "adam_ema_ranges_kernel" in r[2]]
     # optimiser launches of one step may be several (EMA ranges): step boundary = gap of > 50 dispatches between adam launches
@@ -44,7 +45,7 @@ def main():
     busy_end = t0
     gaps = 0
     overlap = 0
-    for i, (s, e, n, g, q, v) in enumerate(step):
+    for i, (s, e, n, g, q, v, w) in enumerate(step):
         key = (short(n), g, v)
         fam[key][0] += 1
         fam[key][1] += e - s
@@ -53,7 +54,7 @@ def main():
         else:
             overlap += min(e, busy_end) - s
         if full:
-            print(f"{(s - t0) / 1e3:10.1f} us  dur {(e - s) / 1e3:8.1f}  gap {(s - busy_end) / 1e3:7.1f}  q{q}  grid {g:6d}  {short(n)[:90]}")
+            print(f"{(s - t0) / 1e3:10.1f} us  dur {(e - s) / 1e3:8.1f}  gap {(s - busy_end) / 1e3:7.1f}  q{q}  grid {g:6d}  wg {w:4d}  {short(n)[:90]}")
         busy_end = max(busy_end, e)
     wall = busy_end - t0
     tot = sum(v[1] for v in fam.values())
