@@ -832,6 +832,72 @@ int mapdit_reduce_scatter_bucket(mapdit_comm_t* comm, float* buf, long count, vo
 int mapdit_allgather_bucket(mapdit_comm_t* comm, float* buf, long count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * VAE decoder (additive within abi 5): latents to pixels, the reference's `vae.decode(samples).sample` (sample.py:72-74,
+ * sample_fid.py:83-84, sample_ema.py:73) for AutoencoderKL-layout weights (Stable Diffusion's decoder; defaults =
+ * stabilityai/sd-vae-ft-mse).  Activations are fp32 NHWC, GEMM operands 16 bits (bf16; _f16 twins below), accumulation fp32.
+ * PARITY WITH THE HUB WEIGHTS UNPINNED: the network is restated from its public description (tests/vae_reference.py).
+ * ------------------------------------------------------------------------------------------------------------ */
+/* Convolution, k in {1, 3}, stride 1, "same" zero padding, as an implicit GEMM over M = N*H*W output pixels:
+ *   out[n, y, x, co] = bias[co] + sum_{ky, kx, c} in[n, y + ky - k/2, x + kx - k/2, c] * w[co][ky][kx][c]  (+ res[n, y, x, co])
+ * w is 16-bit, packed [Cout][k][k][Cin]; bias fp32 [Cout]; res (may be NULL) fp32 NHWC [N, H, W, Cout] and may alias out.
+ * in_kind: how `in` is stored; the fp32 kinds are rounded to the operand format (fp16: saturated at +-65504) while they are staged.
+ * up2 != 0: `in` is [N, H/2, W/2, Cin] and is read through a nearest-neighbour 2x upsample (H, W even): the gather reads
+ * (y >> 1, x >> 1), the upsampled tensor is never written.  out_kind: fp32 NHWC, fp32 NCHW (no res), or 16-bit NHWC.
+ * Cin % 64 == 0 and Cout % 64 == 0 with NHWC on both sides run on the MFMA (128 x 128 output tiles when Cout % 128 == 0, else
+ * 128 x 64 - the same bits either way; 64-wide K tiles that never straddle a tap); every other shape takes a plain kernel.  Out-of-image taps are zeros that are never loaded. */
+enum { MAPDIT_VAE_IN_16 = 0, MAPDIT_VAE_IN_F32 = 1, MAPDIT_VAE_IN_F32_NCHW = 2 };
+enum { MAPDIT_VAE_OUT_F32 = 0, MAPDIT_VAE_OUT_F32_NCHW = 1, MAPDIT_VAE_OUT_16 = 2 };
+typedef struct {
+    const void* in;
+    int in_kind;
+    const uint16_t* w;
+    const float* bias;
+    const float* res;
+    void* out;
+    int out_kind;
+    int N, H, W, Cin, Cout, k, up2;
+} mapdit_vae_conv_t;
+int mapdit_vae_conv(const mapdit_vae_conv_t* args, void* stream);
+/* GroupNorm over NHWC (+ SiLU when silu != 0): x fp32 [N, HW, C], G groups of C / G adjacent channels, biased variance;
+ * out 16-bit [N, HW, C] = act((x - mean) * rstd * gamma + beta); stats (may be NULL) fp32 [N][G][2] = (mean, rstd).
+ * Statistics: one pass over x - x[first element of the group] with fp64 sums, a fixed summation order, no atomics.
+ * scratch (may be NULL): N * ceil(HW / 1024) * G * 16 bytes or more, 8-byte aligned, select the split form for C = 4 * 2^j <= 1024
+ * (64, 128, 256, 512 among them) with G <= 256 - partial sums per 1,024-pixel chunk, then one pass that adds them in chunk order and normalises; both stages
+ * read whole pixel rows and fill the chip, where the one-launch form (one workgroup per sample and group) reads C / G channels of each. */
+int mapdit_vae_groupnorm(const float* x, const float* gamma, const float* beta, float eps, int silu, uint16_t* out, float* stats,
+                         int N, int HW, int C, int G, void* scratch, size_t scratch_bytes, void* stream);
+/* Row softmax with the row maximum subtracted: scores fp32 [rows][T] (row stride lds) -> probabilities 16-bit [rows][T] (stride ldp). */
+int mapdit_vae_softmax(const float* scores, int lds, uint16_t* probs, int ldp, int rows, int T, void* stream);
+
+/* The decoder.  block_out_channels = (ch0 .. ch{num_blocks-1}) in the ENCODER's order, as the config file lists them; the decoder
+ * walks them reversed.  Weight table: MAPDIT_VAE_NUM_GLOBAL global slots, then MAPDIT_VAE_NUM_RESNET slots per resnet in execution
+ * order (mid_block.resnets.0, .1, then up_blocks.i.resnets.j), then MAPDIT_VAE_NUM_UP slots per upsampler (up_blocks.i, i < num_blocks - 1).
+ * Conv / linear weights are 16-bit in the packing of mapdit_vae_conv, everything else fp32.  ATTN_QKV_W / _B: to_q, to_k, to_v stacked
+ * [3C][C] / [3C].  R_SC_W / R_SC_B are NULL for a resnet whose input and output widths agree. */
+enum { MAPDIT_VAE_W_PQ_W = 0, MAPDIT_VAE_W_PQ_B, MAPDIT_VAE_W_CONV_IN_W, MAPDIT_VAE_W_CONV_IN_B, MAPDIT_VAE_W_ATTN_GN_G,
+       MAPDIT_VAE_W_ATTN_GN_B, MAPDIT_VAE_W_ATTN_QKV_W, MAPDIT_VAE_W_ATTN_QKV_B, MAPDIT_VAE_W_ATTN_OUT_W, MAPDIT_VAE_W_ATTN_OUT_B,
+       MAPDIT_VAE_W_NORM_OUT_G, MAPDIT_VAE_W_NORM_OUT_B, MAPDIT_VAE_W_CONV_OUT_W, MAPDIT_VAE_W_CONV_OUT_B, MAPDIT_VAE_NUM_GLOBAL };
+enum { MAPDIT_VAE_R_N1_G = 0, MAPDIT_VAE_R_N1_B, MAPDIT_VAE_R_C1_W, MAPDIT_VAE_R_C1_B, MAPDIT_VAE_R_N2_G, MAPDIT_VAE_R_N2_B,
+       MAPDIT_VAE_R_C2_W, MAPDIT_VAE_R_C2_B, MAPDIT_VAE_R_SC_W, MAPDIT_VAE_R_SC_B, MAPDIT_VAE_NUM_RESNET };
+enum { MAPDIT_VAE_U_W = 0, MAPDIT_VAE_U_B, MAPDIT_VAE_NUM_UP };
+typedef struct {
+    int latent_channels, out_channels;
+    int num_blocks;           /* 1..4: how many of ch0..ch3 are used */
+    int ch0, ch1, ch2, ch3;
+    int layers_per_block;
+    int norm_num_groups;
+    float norm_eps;
+} mapdit_vae_config_t;
+/* Bytes mapdit_vae_decode needs for N latents of h x w: 14 * E + 6 * N * h * w * C + 6 * (h * w)^2 + the GroupNorm scratch (+ alignment), E = the largest
+ * N * H * W * channels of any activation, C = the mid-block width.  0 with a message in mapdit_last_error() when the shape is refused
+ * (N, h, w <= 0; h * w not a multiple of 8: the attention GEMMs' operand alignment; a width that is no multiple of the group count or of 8). */
+size_t mapdit_vae_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int h, int w);
+/* z fp32 [N, latent_channels, h, w] (de-normalised by the caller) -> out fp32 [N, out_channels, h * 2^(num_blocks-1), w * 2^(num_blocks-1)], NCHW,
+ * unclamped.  Every launch goes to `stream`; no allocation, no synchronisation, no host read-back.  weights_host: the table above. */
+int mapdit_vae_decode(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* z, float* out, int N, int h, int w,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
  * holds fp16 bits instead of bf16 bits.  (mapdit_weightnorm_fwd*_f16: w_bf16 receives fp16; the w_split3 image stays a bf16
  * split - the fp32-accurate conditioning GEMMs run on bf16 terms in every engine.)
@@ -896,6 +962,12 @@ int mapdit_final_out_bwd_f16(const float* dout, const float* lin, int ldl, const
                              const float* ref_mean, const float* ref_sigma, uint16_t* dlin, int ldd, uint16_t* da_f16,
                              float* dref_part, float* dref_mean, float* dref_sigma, float grad_scale, int N, int C, int S, int p,
                              void* stream);
+int mapdit_vae_conv_f16(const mapdit_vae_conv_t* args, void* stream);
+int mapdit_vae_groupnorm_f16(const float* x, const float* gamma, const float* beta, float eps, int silu, uint16_t* out, float* stats,
+                             int N, int HW, int C, int G, void* scratch, size_t scratch_bytes, void* stream);
+int mapdit_vae_softmax_f16(const float* scores, int lds, uint16_t* probs, int ldp, int rows, int T, void* stream);
+int mapdit_vae_decode_f16(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* z, float* out, int N, int h, int w,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,654 @@
+// VAE decoder (AutoencoderKL layout): convolution as an implicit GEMM on the MFMA, GroupNorm(+SiLU) over NHWC, a row softmax, and the
+// host plan that sequences a decode on one stream (mapdit.h, "VAE decoder").  Built once per 16-bit operand format (csrc/Makefile).
+//
+// Convolution.  out[m][co] = sum_K A[m][K] * w[co][K] with m = (n, y, x) flattened and K = (ky, kx, c): the weight is a plain row-major
+// [Cout][k*k*Cin] B operand, the A operand is gathered.  A workgroup (4 waves) owns 128 pixels x 64 or 128 output channels; a K tile is 64
+// channels of ONE tap (Cin % 64 == 0), so a thread's 16 staged channels share one (ky, kx) and one bounds decision.  A tile of 128
+// consecutive m straddles image rows and, for small images, samples: each staged row derives (n, y, x) from its own m once and
+// tests y + ky - pad, x + kx - pad against the image - never the flat index.  An out-of-image tap (or a row past M) stages zeros
+// without forming its address.  Global -> registers -> LDS -> v_mfma_f32_16x16x32 (the two tile forms: at the kernel).  LDS rows are
+// padded to 72 elements (144 B: 16-byte aligned, consecutive rows 4 banks apart).
+// The K order of every output element is fixed and does not depend on where its pixel falls in a tile: a sample decoded alone and
+// in a batch gives the same bits.
+#include "common.h"
+
+MD_NS_OPEN
+
+// fp32 -> operand format; fp16 saturates at its largest finite value instead of becoming inf (NaN stays NaN)
+__device__ __forceinline__ float sat16f(float v) {
+#if MAPDIT_DT == 1
+    v = v > 65504.f ? 65504.f : v;
+    v = v < -65504.f ? -65504.f : v;
+#endif
+    return v;
+}
+__device__ __forceinline__ bf16_t cvt16s(float v) { return cvt16(sat16f(v)); }
+__device__ __forceinline__ uint32_t pack16s(float lo, float hi) { return pack16(sat16f(lo), sat16f(hi)); }
+
+struct ConvP {
+    const void* in;
+    const bf16_t* w;
+    const float* bias;
+    const float* res;
+    void* out;
+    int N, H, W, Cin, Cout, k, up2;
+    long M;
+};
+
+constexpr int CBM = 128, CBK = 64, CLD = CBK + 8;
+
+// 16 consecutive channels of one input pixel as 16-bit operands (8 packed words)
+template <int IN_F32> __device__ __forceinline__ void load16(const void* in, size_t elem, uint4& lo, uint4& hi) {
+    if constexpr (IN_F32) {
+        const float4* p = (const float4*)((const float*)in + elem);
+        const float4 a = p[0], b = p[1], c = p[2], d = p[3];
+        lo = uint4{pack16s(a.x, a.y), pack16s(a.z, a.w), pack16s(b.x, b.y), pack16s(b.z, b.w)};
+        hi = uint4{pack16s(c.x, c.y), pack16s(c.z, c.w), pack16s(d.x, d.y), pack16s(d.z, d.w)};
+    } else {
+        const uint4* p = (const uint4*)((const bf16_t*)in + elem);
+        lo = p[0];
+        hi = p[1];
+    }
+}
+
+// BN = 64: each wave 32 x 64 (2 x 4 MFMA tiles), two LDS buffers and one barrier per K tile.  BN = 128 (Cout % 128 == 0): the waves form
+// 2 x 2, each 64 x 64 (4 x 4 tiles: half the LDS reads per MFMA), ONE LDS buffer (two would pass the 64 KiB of static LDS) and two
+// barriers per K tile, the next tile's global loads in flight across the compute.  Same K order: the two forms give the same bits.
+template <int IN_F32, int OUT16, int BN>
+__global__ __launch_bounds__(256) void vae_conv_mfma_kernel(const ConvP p) {
+    constexpr int NBUF = BN == 128 ? 1 : 2, NB = BN / 64, WI = BN == 128 ? 4 : 2;
+    __shared__ __attribute__((aligned(16))) bf16_t As[NBUF][CBM * CLD];
+    __shared__ __attribute__((aligned(16))) bf16_t Bs[NBUF][BN * CLD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, q = lane >> 4;
+    const long m0 = (long)blockIdx.x * CBM;
+    const int co0 = blockIdx.y * BN;
+    const int wr0 = BN == 128 ? (wave & 1) * 64 : wave * 32, wc0 = BN == 128 ? (wave >> 1) * 64 : 0;      // the wave's corner in the tile
+    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.k >> 1;
+    const int Hs = p.up2 ? H >> 1 : H, Ws = p.up2 ? W >> 1 : W;
+    const int cpt = Cin / CBK, nk = k * k * cpt;
+    const size_t Ktot = (size_t)k * k * Cin;
+
+    // staging role: rows srow and srow + 64 of the A tile, row srow (and srow + 64: BN = 128) of the B tile, 16 channels at kq
+    const int srow = tid >> 2, kq = (tid & 3) * 16;
+    int pn[2], py[2], px[2];
+    bool pv[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const long m = m0 + srow + 64 * t;
+        pv[t] = m < p.M;
+        const long mm = pv[t] ? m : 0;
+        pn[t] = (int)(mm / ((long)H * W));
+        const int rem = (int)(mm % ((long)H * W));
+        py[t] = rem / W;
+        px[t] = rem % W;
+    }
+    const bf16_t* wrow = p.w + (size_t)(co0 + srow) * Ktot + kq;
+
+    uint4 ra[2][2], rb[NB][2];
+    auto fetch = [&](int kt) {
+        const int tap = kt / cpt, c0 = (kt - tap * cpt) * CBK + kq;
+        const int ky = tap / k, kx = tap - ky * k;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int yy = py[t] + ky - pad, xx = px[t] + kx - pad;
+            ra[t][0] = uint4{0u, 0u, 0u, 0u};
+            ra[t][1] = uint4{0u, 0u, 0u, 0u};
+            if (pv[t] && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                const int ys = p.up2 ? yy >> 1 : yy, xs = p.up2 ? xx >> 1 : xx;
+                load16<IN_F32>(p.in, (((size_t)pn[t] * Hs + ys) * Ws + xs) * Cin + c0, ra[t][0], ra[t][1]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const uint4* wp = (const uint4*)(wrow + (size_t)t * 64 * Ktot + (size_t)kt * CBK);
+            rb[t][0] = wp[0];
+            rb[t][1] = wp[1];
+        }
+    };
+    auto stash = [&](int buf) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            uint4* d = (uint4*)(&As[buf][(srow + 64 * t) * CLD + kq]);
+            d[0] = ra[t][0];
+            d[1] = ra[t][1];
+        }
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            uint4* d = (uint4*)(&Bs[buf][(srow + 64 * t) * CLD + kq]);
+            d[0] = rb[t][0];
+            d[1] = rb[t][1];
+        }
+    };
+
+    f32x4_t acc[WI][4];
+#pragma unroll
+    for (int i = 0; i < WI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    fetch(0);
+    stash(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = NBUF == 2 ? kt & 1 : 0;
+        if (kt + 1 < nk) fetch(kt + 1);
+#pragma unroll
+        for (int ks = 0; ks < CBK / 32; ++ks) {
+            bf16x8_t a[WI], b[4];
+#pragma unroll
+            for (int i = 0; i < WI; ++i) a[i] = *(const bf16x8_t*)(&As[buf][(wr0 + i * 16 + r) * CLD + ks * 32 + q * 8]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = *(const bf16x8_t*)(&Bs[buf][(wc0 + j * 16 + r) * CLD + ks * 32 + q * 8]);
+#pragma unroll
+            for (int i = 0; i < WI; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(a[i], b[j], acc[i][j]);
+        }
+        if constexpr (NBUF == 1) __syncthreads();       // one buffer: every wave has read K tile kt before it is overwritten
+        // (two buffers: the other one was last read by the compute of K tile kt - 1, which every wave left before the previous barrier)
+        if (kt + 1 < nk) stash(NBUF == 2 ? buf ^ 1 : 0);
+        __syncthreads();
+    }
+
+    // accumulator element e of a lane: pixel row 4 q + e of the 16 x 16 tile, output channel r
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int co = co0 + wc0 + j * 16 + r;
+        const float bv = p.bias[co];
+#pragma unroll
+        for (int i = 0; i < WI; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long m = m0 + wr0 + i * 16 + q * 4 + e;
+                if (m >= p.M) continue;
+                const size_t o = (size_t)m * p.Cout + co;
+                float v = acc[i][j][e] + bv;
+                if (p.res) v += p.res[o];
+                if constexpr (OUT16) ((bf16_t*)p.out)[o] = cvt16s(v);
+                else ((float*)p.out)[o] = v;
+            }
+    }
+}
+
+// Every other shape (conv_in: K = 36; conv_out: 3 outputs, NCHW store; post_quant_conv: 4 -> 4 from NCHW): one thread per output
+// element, the same operand rounding, a serial fp32 sum in (ky, kx, c) order.
+__global__ __launch_bounds__(256) void vae_conv_plain_kernel(const ConvP p, int in_kind, int out_kind) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.M * p.Cout) return;
+    const int co = (int)(idx % p.Cout);
+    const long m = idx / p.Cout;
+    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.k >> 1;
+    const int Hs = p.up2 ? H >> 1 : H, Ws = p.up2 ? W >> 1 : W;
+    const int n = (int)(m / ((long)H * W)), rem = (int)(m % ((long)H * W)), y = rem / W, x = rem % W;
+    const bf16_t* wr = p.w + (size_t)co * k * k * Cin;
+    float acc = 0.f;
+    for (int ky = 0; ky < k; ++ky) {
+        const int yy = y + ky - pad;
+        if (yy < 0 || yy >= H) continue;
+        for (int kx = 0; kx < k; ++kx) {
+            const int xx = x + kx - pad;
+            if (xx < 0 || xx >= W) continue;
+            const int ys = p.up2 ? yy >> 1 : yy, xs = p.up2 ? xx >> 1 : xx;
+            const bf16_t* wt = wr + (size_t)(ky * k + kx) * Cin;
+            if (in_kind == MAPDIT_VAE_IN_16) {
+                const bf16_t* ip = (const bf16_t*)p.in + (((size_t)n * Hs + ys) * Ws + xs) * Cin;
+                int c = 0;
+                if (Cin % 8 == 0 && !(((uintptr_t)ip | (uintptr_t)wt) & 15))        // eight channels per 16-byte load, the same serial order
+                    for (; c < Cin; c += 8) {
+                        const uint4 xv = *(const uint4*)(ip + c), wv = *(const uint4*)(wt + c);
+                        const uint32_t xw[4] = {xv.x, xv.y, xv.z, xv.w}, ww[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            acc = fmaf(lo16(xw[e]), lo16(ww[e]), acc);
+                            acc = fmaf(hi16(xw[e]), hi16(ww[e]), acc);
+                        }
+                    }
+                for (; c < Cin; ++c) acc = fmaf(up16(ip[c]), up16(wt[c]), acc);
+            } else if (in_kind == MAPDIT_VAE_IN_F32) {
+                const float* ip = (const float*)p.in + (((size_t)n * Hs + ys) * Ws + xs) * Cin;
+                for (int c = 0; c < Cin; ++c) acc = fmaf(up16(cvt16s(ip[c])), up16(wt[c]), acc);
+            } else {
+                const float* ip = (const float*)p.in + ((size_t)n * Cin * Hs + ys) * Ws + xs;
+                for (int c = 0; c < Cin; ++c) acc = fmaf(up16(cvt16s(ip[(size_t)c * Hs * Ws])), up16(wt[c]), acc);
+            }
+        }
+    }
+    float v = acc + p.bias[co];
+    if (out_kind == MAPDIT_VAE_OUT_F32_NCHW) {
+        ((float*)p.out)[(((size_t)n * p.Cout + co) * H + y) * W + x] = v;
+        return;
+    }
+    if (p.res) v += p.res[idx];
+    if (out_kind == MAPDIT_VAE_OUT_16) ((bf16_t*)p.out)[idx] = cvt16s(v);
+    else ((float*)p.out)[idx] = v;
+}
+
+// ---- GroupNorm (+ SiLU) over NHWC -----------------------------------------------------------------------------------------------
+// One workgroup per (sample, group).  Statistics in ONE pass over d = x - x[first element of the group] with fp64 sums of d and d * d
+// (the shift keeps d small for channels with a large mean; fp64 keeps the sum of squares exact far beyond what the bounds ask), added
+// in a fixed order: thread (pixel stride 256), wave (xor shuffles), the four waves through LDS.  The second pass normalises in fp32.
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void vae_groupnorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float eps, int silu, bf16_t* __restrict__ out,
+                                                          float* __restrict__ stats, int HW, int C, int G) {
+    __shared__ double red[2][4];
+    __shared__ float ms[2];
+    const int n = blockIdx.x / G, g = blockIdx.x % G, cpg = C / G;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t base = (size_t)n * HW * C + (size_t)g * cpg;
+    const float* xb = x + base;
+    const float shift = xb[0];
+    double s = 0.0, ss = 0.0;
+    for (int px = tid; px < HW; px += 256) {
+        const float* xp = xb + (size_t)px * C;
+        for (int c = 0; c < cpg; ++c) {
+            const double d = (double)(xp[c] - shift);
+            s += d;
+            ss += d * d;
+        }
+    }
+    s = wave_sum_d(s);
+    ss = wave_sum_d(ss);
+    if (lane == 0) {
+        red[0][wave] = s;
+        red[1][wave] = ss;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double cnt = (double)HW * cpg;
+        const double sd = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        const double sq = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        const double md = sd / cnt;
+        double var = sq / cnt - md * md;
+        var = var > 0.0 ? var : 0.0;
+        const float mean = (float)((double)shift + md), rstd = (float)(1.0 / sqrt(var + (double)eps));
+        ms[0] = mean;
+        ms[1] = rstd;
+        if (stats) {
+            stats[((size_t)n * G + g) * 2] = mean;
+            stats[((size_t)n * G + g) * 2 + 1] = rstd;
+        }
+    }
+    __syncthreads();
+    const float mean = ms[0], rstd = ms[1];
+    bf16_t* ob = out + base;
+    for (int px = tid; px < HW; px += 256) {
+        const float* xp = xb + (size_t)px * C;
+        bf16_t* op = ob + (size_t)px * C;
+        for (int c = 0; c < cpg; ++c) {
+            float v = (xp[c] - mean) * rstd * gamma[g * cpg + c] + beta[g * cpg + c];
+            if (silu) v = v / (1.f + __expf(-v));
+            op[c] = cvt16s(v);
+        }
+    }
+}
+
+// The split form, for tensors large enough to matter (one workgroup per (sample, group) reads 4 * C/G bytes of every C * 4-byte pixel
+// row: an eighth of each cache line at C = 128, and N * G workgroups in all).  Both stages read whole pixel rows: thread = (pixel lane,
+// four adjacent channels), 256 / (C / 4) pixel lanes.  Stage 1: a workgroup owns GN_PX pixels of one sample and writes, per group, its
+// fp64 sums of d and d * d (d = x - the group's first element of the sample, as above) - thread, then the workgroup through LDS in
+// (pixel lane, channel) order.  Stage 2: every workgroup adds the partials of its sample in chunk order (the same few KB for all of
+// them), then normalises its own GN_PX pixels.  No atomics; a sample's statistics do not depend on the batch it is in.
+constexpr int GN_PX = 1024;
+
+__global__ __launch_bounds__(256) void vae_gn_stats_kernel(const float* __restrict__ x, double* __restrict__ part, int HW, int C, int G) {
+    __shared__ double ls[2][1024];                        // [pixel lane][channel]: 256 / (C / 4) * C = 1024 entries
+    const int tid = threadIdx.x, cols = C >> 2, col = tid % cols, pl = tid / cols, lanes = 256 / cols, cpg = C / G;
+    const int chunk = blockIdx.x, n = blockIdx.y;
+    const float* xb = x + (size_t)n * HW * C;
+    float sh[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sh[e] = xb[((col * 4 + e) / cpg) * cpg];
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
+    const int p0 = chunk * GN_PX, p1 = p0 + GN_PX < HW ? p0 + GN_PX : HW;
+    for (int px = p0 + pl; px < p1; px += lanes) {
+        const float4 v = *(const float4*)(xb + (size_t)px * C + col * 4);
+        const float ve[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double d = (double)(ve[e] - sh[e]);
+            s[e] += d;
+            ss[e] += d * d;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        ls[0][pl * C + col * 4 + e] = s[e];
+        ls[1][pl * C + col * 4 + e] = ss[e];
+    }
+    __syncthreads();
+    if (tid < G) {
+        double a = 0.0, b = 0.0;
+        for (int l = 0; l < lanes; ++l)
+            for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) {
+                a += ls[0][l * C + c];
+                b += ls[1][l * C + c];
+            }
+        double* o = part + (((size_t)n * gridDim.x + chunk) * G + tid) * 2;
+        o[0] = a;
+        o[1] = b;
+    }
+}
+
+__global__ __launch_bounds__(256) void vae_gn_apply_kernel(const float* __restrict__ x, const double* __restrict__ part,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int silu,
+                                                         bf16_t* __restrict__ out, float* __restrict__ stats, int HW, int C, int G) {
+    __shared__ float ms[2][256];
+    const int tid = threadIdx.x, cols = C >> 2, col = tid % cols, pl = tid / cols, lanes = 256 / cols, cpg = C / G;
+    const int chunk = blockIdx.x, n = blockIdx.y, nchunks = gridDim.x;
+    const float* xb = x + (size_t)n * HW * C;
+    if (tid < G) {
+        double a = 0.0, b = 0.0;
+        for (int k = 0; k < nchunks; ++k) {
+            const double* pp = part + (((size_t)n * nchunks + k) * G + tid) * 2;
+            a += pp[0];
+            b += pp[1];
+        }
+        const double cnt = (double)HW * cpg, md = a / cnt;
+        double var = b / cnt - md * md;
+        var = var > 0.0 ? var : 0.0;
+        const float mean = (float)((double)xb[tid * cpg] + md), rstd = (float)(1.0 / sqrt(var + (double)eps));
+        ms[0][tid] = mean;
+        ms[1][tid] = rstd;
+        if (stats && chunk == 0) {
+            stats[((size_t)n * G + tid) * 2] = mean;
+            stats[((size_t)n * G + tid) * 2 + 1] = rstd;
+        }
+    }
+    __syncthreads();
+    float mu[4], rs[4], ga[4], be[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int c = col * 4 + e;
+        mu[e] = ms[0][c / cpg];
+        rs[e] = ms[1][c / cpg];
+        ga[e] = gamma[c];
+        be[e] = beta[c];
+    }
+    bf16_t* ob = out + (size_t)n * HW * C;
+    const int p0 = chunk * GN_PX, p1 = p0 + GN_PX < HW ? p0 + GN_PX : HW;
+    for (int px = p0 + pl; px < p1; px += lanes) {
+        const float4 v = *(const float4*)(xb + (size_t)px * C + col * 4);
+        const float ve[4] = {v.x, v.y, v.z, v.w};
+        float y[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            y[e] = (ve[e] - mu[e]) * rs[e] * ga[e] + be[e];
+            if (silu) y[e] = y[e] / (1.f + __expf(-y[e]));
+        }
+        *(uint2*)(ob + (size_t)px * C + col * 4) = uint2{pack16s(y[0], y[1]), pack16s(y[2], y[3])};
+    }
+}
+
+// ---- row softmax --------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vae_softmax_kernel(const float* __restrict__ sc, int lds, bf16_t* __restrict__ pr, int ldp, int T) {
+    __shared__ float red[4];
+    __shared__ float bc;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* row = sc + (size_t)blockIdx.x * lds;
+    bf16_t* orow = pr + (size_t)blockIdx.x * ldp;
+    float mx = -INFINITY;
+    for (int i = tid; i < T; i += 256) mx = fmaxf(mx, row[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    if (tid == 0) bc = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    mx = bc;
+    float s = 0.f;
+    for (int i = tid; i < T; i += 256) s += __expf(row[i] - mx);
+    s = wave_sum(s);
+    __syncthreads();                      // red is free again: thread 0 has read it
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    const float inv = 1.f / (((red[0] + red[1]) + red[2]) + red[3]);
+    for (int i = tid; i < T; i += 256) orow[i] = cvt16(__expf(row[i] - mx) * inv);
+}
+
+MD_NS_CLOSE
+
+// ---- entry points -----------------------------------------------------------------------------------------------------------------
+extern "C" int MD_SYM(vae_conv)(const mapdit_vae_conv_t* a, void* stream) {
+    MD_CHECK(a && a->in && a->w && a->bias && a->out, "vae_conv: null argument");
+    MD_CHECK(a->k == 1 || a->k == 3, "vae_conv: k=%d (1 or 3)", a->k);
+    MD_CHECK(a->N > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, "vae_conv: empty shape N=%d H=%d W=%d Cin=%d Cout=%d", a->N, a->H,
+             a->W, a->Cin, a->Cout);
+    MD_CHECK(a->in_kind >= MAPDIT_VAE_IN_16 && a->in_kind <= MAPDIT_VAE_IN_F32_NCHW, "vae_conv: bad in_kind %d", a->in_kind);
+    MD_CHECK(a->out_kind >= MAPDIT_VAE_OUT_F32 && a->out_kind <= MAPDIT_VAE_OUT_16, "vae_conv: bad out_kind %d", a->out_kind);
+    MD_CHECK(!a->up2 || (a->H % 2 == 0 && a->W % 2 == 0), "vae_conv: up2 needs even H=%d, W=%d", a->H, a->W);
+    MD_CHECK(!(a->res && a->out_kind == MAPDIT_VAE_OUT_F32_NCHW), "vae_conv: no residual with the NCHW store");
+    const long M = (long)a->N * a->H * a->W;
+    MD_CHECK(M * a->Cout < (1L << 40) && M < (1L << 31), "vae_conv: %ld output pixels are too many", M);
+    hipStream_t st = (hipStream_t)stream;
+    const ConvP p{a->in, (const bf16_t*)a->w, a->bias, a->res, a->out, a->N, a->H, a->W, a->Cin, a->Cout, a->k, a->up2 ? 1 : 0, M};
+    const bool aligned = !(((uintptr_t)a->in | (uintptr_t)a->w) & 15);
+    if (a->Cin % CBK == 0 && a->Cout % 64 == 0 && a->in_kind != MAPDIT_VAE_IN_F32_NCHW && a->out_kind != MAPDIT_VAE_OUT_F32_NCHW && aligned) {
+        const bool f32 = a->in_kind == MAPDIT_VAE_IN_F32, o16 = a->out_kind == MAPDIT_VAE_OUT_16, wide = a->Cout % 128 == 0;
+        const dim3 grid((unsigned)cdiv(M, CBM), (unsigned)(a->Cout / (wide ? 128 : 64)));
+#define VAE_CONV_GO(F, O)                                                          \
+    do {                                                                           \
+        if (wide) vae_conv_mfma_kernel<F, O, 128><<<grid, 256, 0, st>>>(p);        \
+        else vae_conv_mfma_kernel<F, O, 64><<<grid, 256, 0, st>>>(p);              \
+    } while (0)
+        if (f32 && o16) VAE_CONV_GO(1, 1);
+        else if (f32) VAE_CONV_GO(1, 0);
+        else if (o16) VAE_CONV_GO(0, 1);
+        else VAE_CONV_GO(0, 0);
+#undef VAE_CONV_GO
+    } else {
+        MD_CHECK(M * a->Cout < (1L << 38), "vae_conv: %ld x %d outputs are too many for the plain kernel", M, a->Cout);
+        vae_conv_plain_kernel<<<cdiv(M * a->Cout, 256), 256, 0, st>>>(p, a->in_kind, a->out_kind);
+    }
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(vae_groupnorm)(const float* x, const float* gamma, const float* beta, float eps, int silu, uint16_t* out, float* stats,
+                                     int N, int HW, int C, int G, void* scratch, size_t scratch_bytes, void* stream) {
+    MD_CHECK(x && gamma && beta && out, "vae_groupnorm: null argument");
+    MD_CHECK(N > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "vae_groupnorm: N=%d HW=%d C=%d must be positive and C a multiple of G=%d", N, HW, C, G);
+    MD_CHECK((long)N * G < (1L << 31) && N < 65536, "vae_groupnorm: too many samples / groups");
+    hipStream_t st = (hipStream_t)stream;
+    const int nchunks = cdiv(HW, GN_PX);
+    const bool split = scratch && scratch_bytes >= (size_t)N * nchunks * G * 2 * sizeof(double) && !((uintptr_t)scratch & 7) && C % 4 == 0 &&
+                       C / 4 <= 256 && 256 % (C / 4) == 0 && G <= 256 && !((uintptr_t)x & 15) && !((uintptr_t)out & 7);
+    if (split) {
+        const dim3 grid((unsigned)nchunks, (unsigned)N);
+        vae_gn_stats_kernel<<<grid, 256, 0, st>>>(x, (double*)scratch, HW, C, G);
+        vae_gn_apply_kernel<<<grid, 256, 0, st>>>(x, (const double*)scratch, gamma, beta, eps, silu, (bf16_t*)out, stats, HW, C, G);
+    } else {
+        vae_groupnorm_kernel<<<N * G, 256, 0, st>>>(x, gamma, beta, eps, silu, (bf16_t*)out, stats, HW, C, G);
+    }
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(vae_softmax)(const float* scores, int lds, uint16_t* probs, int ldp, int rows, int T, void* stream) {
+    MD_CHECK(scores && probs && rows > 0 && T > 0 && lds >= T && ldp >= T, "vae_softmax: null / empty argument (rows=%d T=%d lds=%d ldp=%d)", rows, T,
+             lds, ldp);
+    vae_softmax_kernel<<<rows, 256, 0, (hipStream_t)stream>>>(scores, lds, (bf16_t*)probs, ldp, T);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+// ---- the decoder plan -------------------------------------------------------------------------------------------------------------
+namespace {
+struct VaePlan {
+    int C[4];          // widths in the decoder's order (reversed block_out_channels)
+    int nb;
+    size_t maxE;       // largest activation, elements
+    size_t off_x, off_y, off_h, off_a, off_qkv, off_s, off_p, off_gn, gn_bytes, total;
+};
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// 0 = ok; otherwise the message is set
+int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
+    MD_CHECK(cfg, "vae: null config");
+    MD_CHECK(N > 0 && h > 0 && w > 0, "vae: N=%d, h=%d, w=%d must be positive", N, h, w);
+    MD_CHECK(cfg->num_blocks >= 1 && cfg->num_blocks <= 4, "vae: num_blocks=%d (1..4 block widths)", cfg->num_blocks);
+    MD_CHECK(cfg->latent_channels > 0 && cfg->out_channels > 0 && cfg->layers_per_block >= 1 && cfg->layers_per_block <= 16,
+             "vae: latent_channels=%d, out_channels=%d, layers_per_block=%d", cfg->latent_channels, cfg->out_channels, cfg->layers_per_block);
+    MD_CHECK(cfg->norm_num_groups > 0, "vae: norm_num_groups=%d must be positive", cfg->norm_num_groups);
+    const int ch[4] = {cfg->ch0, cfg->ch1, cfg->ch2, cfg->ch3};
+    pl->nb = cfg->num_blocks;
+    for (int i = 0; i < pl->nb; ++i) {
+        const int c = ch[pl->nb - 1 - i];
+        MD_CHECK(c > 0 && c % cfg->norm_num_groups == 0, "vae: channel width %d is not a multiple of the norm groups (%d)", c, cfg->norm_num_groups);
+        MD_CHECK(c % 8 == 0, "vae: channel width %d is not a multiple of 8 (16-bit operand rows of 16 bytes)", c);
+        pl->C[i] = c;
+    }
+    MD_CHECK((long)h * w % 8 == 0, "vae: h*w = %ld tokens in the mid-block attention must be a multiple of 8 (operand alignment of its GEMMs)", (long)h * w);
+    MD_CHECK((long)N * h * w * (1L << (2 * (pl->nb - 1))) < (1L << 31), "vae: N=%d latents of %d x %d are too many output pixels for one call", N, h, w);
+    size_t px = (size_t)N * h * w, maxE = px * (size_t)pl->C[0];
+    int cin = pl->C[0];
+    for (int i = 0; i < pl->nb; ++i) {
+        const size_t e = px * (size_t)(cin > pl->C[i] ? cin : pl->C[i]);
+        maxE = e > maxE ? e : maxE;
+        cin = pl->C[i];
+        if (i < pl->nb - 1) {
+            px *= 4;
+            maxE = px * (size_t)cin > maxE ? px * (size_t)cin : maxE;
+        }
+    }
+    pl->maxE = maxE;
+    const size_t T = (size_t)h * w;
+    size_t o = 0;
+    pl->off_x = o; o += up256(maxE * 4);
+    pl->off_y = o; o += up256(maxE * 4);
+    pl->off_h = o; o += up256(maxE * 4);
+    pl->off_a = o; o += up256(maxE * 2);
+    pl->off_qkv = o; o += up256((size_t)N * T * 3 * pl->C[0] * 2);
+    pl->off_s = o; o += up256(T * T * 4);
+    pl->off_p = o; o += up256(T * T * 2);
+    // partial sums of the split GroupNorm: per sample, 1,024-pixel chunk of the largest image and group, two fp64
+    pl->gn_bytes = (size_t)N * (size_t)cdiv((long)(px / N), GN_PX) * cfg->norm_num_groups * 2 * sizeof(double);
+    pl->off_gn = o; o += up256(pl->gn_bytes);
+    pl->total = o;
+    return MAPDIT_OK;
+}
+}  // namespace
+
+#if MAPDIT_DT == 0
+extern "C" size_t mapdit_vae_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int h, int w) {
+    VaePlan pl;
+    return vae_plan(cfg, N, h, w, &pl) == MAPDIT_OK ? pl.total : 0;
+}
+#endif
+
+#define VAE_TRY(call)                    \
+    do {                                 \
+        const int rc_ = (call);          \
+        if (rc_ != MAPDIT_OK) return rc_; \
+    } while (0)
+
+extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* const* wt, const float* z, float* out, int N, int h, int w,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    VaePlan pl;
+    VAE_TRY(vae_plan(cfg, N, h, w, &pl));
+    MD_CHECK(wt && z && out && workspace, "vae_decode: null argument");
+    MD_CHECK(workspace_bytes >= pl.total, "vae_decode: workspace of %zu bytes, %zu needed (mapdit_vae_workspace_bytes)", workspace_bytes, pl.total);
+    MD_CHECK(!((uintptr_t)workspace & 255), "vae_decode: the workspace must be 256-byte aligned");
+    const int nres = 2 + pl.nb * (cfg->layers_per_block + 1);
+    const int nslots = MAPDIT_VAE_NUM_GLOBAL + nres * MAPDIT_VAE_NUM_RESNET + (pl.nb - 1) * MAPDIT_VAE_NUM_UP;
+    for (int i = 0; i < nslots; ++i) {
+        const int rs = i - MAPDIT_VAE_NUM_GLOBAL;
+        const bool optional = rs >= 0 && rs < nres * MAPDIT_VAE_NUM_RESNET &&
+                              (rs % MAPDIT_VAE_NUM_RESNET == MAPDIT_VAE_R_SC_W || rs % MAPDIT_VAE_NUM_RESNET == MAPDIT_VAE_R_SC_B);
+        MD_CHECK(wt[i] || optional, "vae_decode: weight slot %d is null", i);
+    }
+    char* ws = (char*)workspace;
+    float* X = (float*)(ws + pl.off_x);
+    float* Y = (float*)(ws + pl.off_y);
+    float* Hb = (float*)(ws + pl.off_h);
+    uint16_t* A16 = (uint16_t*)(ws + pl.off_a);
+    uint16_t* QKV = (uint16_t*)(ws + pl.off_qkv);
+    float* S = (float*)(ws + pl.off_s);
+    uint16_t* P = (uint16_t*)(ws + pl.off_p);
+    const int G = cfg->norm_num_groups;
+    const float eps = cfg->norm_eps;
+
+    auto conv = [&](const void* in, int in_kind, const void* wgt, const void* bias, const float* res, void* o, int out_kind, int H, int W, int Cin,
+                    int Cout, int k, int up2) {
+        const mapdit_vae_conv_t a{in, in_kind, (const uint16_t*)wgt, (const float*)bias, res, o, out_kind, N, H, W, Cin, Cout, k, up2};
+        return MD_SYM(vae_conv)(&a, stream);
+    };
+    auto gn = [&](const float* x, const void* g, const void* b, int silu, int HW, int C) {
+        return MD_SYM(vae_groupnorm)(x, (const float*)g, (const float*)b, eps, silu, A16, nullptr, N, HW, C, G, ws + pl.off_gn, pl.gn_bytes, stream);
+    };
+    int rix = 0;      // resnets in execution order
+    // X [N, H, W, cin] -> X [N, H, W, cout]
+    auto resnet = [&](int H, int W, int cin, int cout) {
+        const void* const* r = wt + MAPDIT_VAE_NUM_GLOBAL + (rix++) * MAPDIT_VAE_NUM_RESNET;
+        const bool sc = cin != cout;
+        MD_CHECK(!sc || (r[MAPDIT_VAE_R_SC_W] && r[MAPDIT_VAE_R_SC_B]), "vae_decode: resnet %d maps %d -> %d channels and has no conv_shortcut", rix - 1, cin, cout);
+        VAE_TRY(gn(X, r[MAPDIT_VAE_R_N1_G], r[MAPDIT_VAE_R_N1_B], 1, H * W, cin));
+        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C1_W], r[MAPDIT_VAE_R_C1_B], nullptr, Hb, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 3, 0));
+        VAE_TRY(gn(Hb, r[MAPDIT_VAE_R_N2_G], r[MAPDIT_VAE_R_N2_B], 1, H * W, cout));
+        if (sc) VAE_TRY(conv(X, MAPDIT_VAE_IN_F32, r[MAPDIT_VAE_R_SC_W], r[MAPDIT_VAE_R_SC_B], nullptr, Y, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 1, 0));
+        // (same widths: the residual is read and the sum written in place, element by element, by the thread that owns it)
+        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C2_W], r[MAPDIT_VAE_R_C2_B], sc ? Y : X, X, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 0));
+        return (int)MAPDIT_OK;
+    };
+
+    int H = h, W = w;
+    const int C0 = pl.C[0], L = cfg->latent_channels;
+    // post_quant_conv (reads z as NCHW) and conv_in
+    VAE_TRY(conv(z, MAPDIT_VAE_IN_F32_NCHW, wt[MAPDIT_VAE_W_PQ_W], wt[MAPDIT_VAE_W_PQ_B], nullptr, Hb, MAPDIT_VAE_OUT_F32, H, W, L, L, 1, 0));
+    VAE_TRY(conv(Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_CONV_IN_W], wt[MAPDIT_VAE_W_CONV_IN_B], nullptr, X, MAPDIT_VAE_OUT_F32, H, W, L, C0, 3, 0));
+    // mid block
+    VAE_TRY(resnet(H, W, C0, C0));
+    {
+        const int T = H * W;
+        VAE_TRY(gn(X, wt[MAPDIT_VAE_W_ATTN_GN_G], wt[MAPDIT_VAE_W_ATTN_GN_B], 0, T, C0));
+        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_ATTN_QKV_W], wt[MAPDIT_VAE_W_ATTN_QKV_B], nullptr, QKV, MAPDIT_VAE_OUT_16, H, W, C0, 3 * C0, 1, 0));
+        for (int n = 0; n < N; ++n) {
+            const uint16_t* qn = QKV + (size_t)n * T * 3 * C0;
+            mapdit_epilogue_t e{};
+            e.kind = MAPDIT_EPI_STORE_F32;
+            e.out = S;
+            e.ldo = T;
+            e.alpha = 1.f / sqrtf((float)C0);
+            VAE_TRY(MD_SYM_GEMM(MAPDIT_NT, T, T, C0, qn, 3 * C0, qn + C0, 3 * C0, &e, stream));
+            VAE_TRY(MD_SYM(vae_softmax)(S, T, P, T, T, T, stream));
+            mapdit_epilogue_t e2{};
+            e2.kind = MAPDIT_EPI_STORE_F32;
+            e2.out = Hb + (size_t)n * T * C0;
+            e2.ldo = C0;
+            e2.alpha = 1.f;
+            VAE_TRY(MD_SYM_GEMM(MAPDIT_NN, T, C0, T, P, T, qn + 2 * C0, 3 * C0, &e2, stream));
+        }
+        VAE_TRY(conv(Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_ATTN_OUT_W], wt[MAPDIT_VAE_W_ATTN_OUT_B], X, X, MAPDIT_VAE_OUT_F32, H, W, C0, C0, 1, 0));
+    }
+    VAE_TRY(resnet(H, W, C0, C0));
+    // up blocks
+    int cin = C0;
+    const void* const* ups = wt + MAPDIT_VAE_NUM_GLOBAL + nres * MAPDIT_VAE_NUM_RESNET;
+    for (int i = 0; i < pl.nb; ++i) {
+        const int cout = pl.C[i];
+        for (int j = 0; j <= cfg->layers_per_block; ++j) {
+            VAE_TRY(resnet(H, W, cin, cout));
+            cin = cout;
+        }
+        if (i < pl.nb - 1) {
+            const void* const* u = ups + i * MAPDIT_VAE_NUM_UP;
+            H *= 2;
+            W *= 2;
+            VAE_TRY(conv(X, MAPDIT_VAE_IN_F32, u[MAPDIT_VAE_U_W], u[MAPDIT_VAE_U_B], nullptr, Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 1));
+            float* t = X;
+            X = Y;
+            Y = t;
+        }
+    }
+    VAE_TRY(gn(X, wt[MAPDIT_VAE_W_NORM_OUT_G], wt[MAPDIT_VAE_W_NORM_OUT_B], 1, H * W, cin));
+    VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_CONV_OUT_W], wt[MAPDIT_VAE_W_CONV_OUT_B], nullptr, out, MAPDIT_VAE_OUT_F32_NCHW, H, W, cin,
+                 cfg->out_channels, 3, 0));
+    return MAPDIT_OK;
+}

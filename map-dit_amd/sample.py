@@ -1,9 +1,10 @@
 """MI355X counterpart of the reference's ``sample.py``: four class-conditional samples with classifier-free guidance
 from the post-hoc EMA weights of a results directory, written as an image grid.  Same flags and defaults
 (reference sample.py:83-96) plus ``--vae-path`` / ``--no-graph`` / ``--precision`` and ``--sampler dpm++`` with ``--solver-order`` /
-``--solver-spacing`` (DPM-Solver++ on the full schedule, ``--num-sampling-steps`` model evaluations; default: the ancestral sampler).  The VAE decoder is not part of this
-engine: with ``--use-vae false`` the de-normalised latents are written (PNG grid of the 4 latent channels
-as RGBA + ``<output>.npy``)."""
+``--solver-spacing`` (DPM-Solver++ on the full schedule, ``--num-sampling-steps`` model evaluations; default: the ancestral sampler).
+``--vae-weights FILE`` (with ``--vae-precision`` / ``--vae-norm-groups``) decodes the latents with the native VAE decoder
+(map-dit_amd/vae.py) and writes an RGB grid; with ``--use-vae false`` the de-normalised latents are written (PNG grid of the 4 latent
+channels as RGBA + ``<output>.npy``); ``--use-vae true`` without weights asks for the ``diffusers`` package, as before."""
 from __future__ import annotations
 
 import argparse
@@ -30,12 +31,14 @@ def build_parser():
     p.add_argument("--no-graph", action="store_true", help="eager p_sample_loop instead of the captured hipGraph")
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
     S.add_sampler_flags(p)
+    S.add_vae_flags(p)
     return p
 
 
 @torch.no_grad()          # the reference switches autograd off globally (torch.set_grad_enabled(False)); scoped here
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    S.check_vae_flags(args)                                               # a missing --vae-weights file ends the run before any model is built
     if args.seed is not None:
         torch.manual_seed(args.seed)
     device = torch.device("cuda")
@@ -44,7 +47,7 @@ def main(argv=None):
     model = get_model(train_args).to(device)
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=True)
     model.gemm_precision = args.precision
-    vae = S.load_vae(args.vae_path, device) if args.use_vae else None
+    vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
 
     n = 4                                                                  # sample.py:40
     z = torch.randn(n, train_args["in_channels"], train_args["input_size"], train_args["input_size"], device=device)

@@ -28,18 +28,20 @@ def build_parser():
     p.add_argument("--no-graph", action="store_true", help="eager p_sample_loop instead of the captured hipGraph")
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
     S.add_sampler_flags(p)
+    S.add_vae_flags(p)
     return p
 
 
 @torch.no_grad()          # the reference switches autograd off globally (torch.set_grad_enabled(False)); scoped here
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    S.check_vae_flags(args)                                               # a missing --vae-weights file ends the run before any model is built
     device = torch.device("cuda")
     train_args = S.load_train_args(args.result_dir)
     S.check_objective(args.sampler, train_args)                           # a velocity model and a diffusion sampler (or the reverse): refused here
     model = get_model(train_args).to(device).eval()
     model.gemm_precision = args.precision
-    vae = S.load_vae(args.vae_path, device) if args.use_vae else None
+    vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
     diffusion, solver = S.make_diffusion(args, train_args)
     n = 8
     shape = (2 * n, train_args["in_channels"], train_args["input_size"], train_args["input_size"])

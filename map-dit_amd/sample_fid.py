@@ -2,7 +2,8 @@
 random labels (classifier-free guidance when ``--cfg-scale`` > 1), stored as one uint8 NHWC array ``arr_0`` in
 ``<result-dir>/fid_samples/<output-file>`` (reference sample_fid.py:48-97; flags :100-114).  One hipGraph is captured for
 the batch shape and replayed for every batch (``--sampler dpm++``: DPM-Solver++ with ``--num-sampling-steps`` model evaluations).  Without a VAE (``--use-vae false``) the array holds the de-normalised
-latents clamped to [-1, 1] and quantised the same way."""
+latents clamped to [-1, 1] and quantised the same way; with ``--vae-weights FILE`` the native VAE decoder (map-dit_amd/vae.py) turns
+them into pixels first (``arr_0``: [n, 8S, 8S, 3])."""
 from __future__ import annotations
 
 import argparse
@@ -35,12 +36,14 @@ def build_parser():
     p.add_argument("--no-graph", action="store_true", help="eager p_sample_loop instead of the captured hipGraph")
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
     S.add_sampler_flags(p)
+    S.add_vae_flags(p)
     return p
 
 
 @torch.no_grad()          # the reference switches autograd off globally (torch.set_grad_enabled(False)); scoped here
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    S.check_vae_flags(args)                                               # a missing --vae-weights file ends the run before any model is built
     if args.seed is not None:
         torch.manual_seed(args.seed)
     device = torch.device("cuda")
@@ -54,7 +57,7 @@ def main(argv=None):
     model = get_model(train_args).to(device)
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=False)
     model.gemm_precision = args.precision
-    vae = S.load_vae(args.vae_path, device) if args.use_vae else None
+    vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
     diffusion, solver = S.make_diffusion(args, train_args)
 
     n = args.batch_size

@@ -273,9 +273,29 @@ def denormalize(samples: torch.Tensor, train_args: dict) -> torch.Tensor:
     return samples * std + mean
 
 
-def load_vae(vae_path: str | None, device):
+def add_vae_flags(parser):
+    """The native decoder's flags, shared by the three CLIs (``load_vae``)."""
+    parser.add_argument("--vae-weights", type=str, default=None,
+                        help="AutoencoderKL weights (.safetensors, or a torch state dict): decode with the native HIP decoder")
+    parser.add_argument("--vae-precision", choices=["f16", "bf16"], default="f16", help="16-bit operand format of the native decoder")
+    parser.add_argument("--vae-norm-groups", type=int, default=32, help="norm_num_groups of the VAE config (not recoverable from the weights)")
+    return parser
+
+
+def check_vae_flags(args):
+    """Before anything is built: a ``--vae-weights`` that names no file ends the run here, not after sampling."""
+    import os
+    if getattr(args, "vae_weights", None) and not os.path.isfile(args.vae_weights):
+        raise FileNotFoundError(f"--vae-weights {args.vae_weights}: no such file")
+
+
+def load_vae(vae_path: str | None, device, weights: str | None = None, precision: str = "f16", norm_groups: int = 32):
     """The reference decodes latents with diffusers' AutoencoderKL("stabilityai/sd-vae-ft-mse") fetched from the hub
-    (sample.py:72-74).  No network here: the decoder is out of scope - a local copy can be passed."""
+    (sample.py:72-74).  ``weights`` (``--vae-weights``): the native decoder (map-dit_amd/vae.py) on that weight file - no package,
+    no network.  Without it: the ``diffusers`` package on a local copy (``--vae-path``), as before."""
+    if weights is not None:
+        from .vae import VAEDecoder
+        return VAEDecoder.from_file(weights, device, precision=precision, norm_num_groups=norm_groups)
     try:
         from diffusers import AutoencoderKL
     except ImportError as e:
