@@ -832,10 +832,13 @@ int mapdit_reduce_scatter_bucket(mapdit_comm_t* comm, float* buf, long count, vo
 int mapdit_allgather_bucket(mapdit_comm_t* comm, float* buf, long count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
- * VAE decoder (additive within abi 5): latents to pixels, the reference's `vae.decode(samples).sample` (sample.py:72-74,
- * sample_fid.py:83-84, sample_ema.py:73) for AutoencoderKL-layout weights (Stable Diffusion's decoder; defaults =
- * stabilityai/sd-vae-ft-mse).  Activations are fp32 NHWC, GEMM operands 16 bits (bf16; _f16 twins below), accumulation fp32.
- * PARITY WITH THE HUB WEIGHTS UNPINNED: the network is restated from its public description (tests/vae_reference.py).
+ * VAE (additive within abi 5), for AutoencoderKL-layout weights (Stable Diffusion's; defaults = stabilityai/sd-vae-ft-mse).
+ * Decoder: latents to pixels, the reference's `vae.decode(samples).sample` (sample.py:72-74, sample_fid.py:83-84,
+ * sample_ema.py:73).  Encoder: images to posterior latents, `vae.encode(imgs).latent_dist` of download_data.py, with the image
+ * preparation and the data set's mixture statistics ("The encoder", below).  Activations are fp32 NHWC, GEMM operands 16 bits
+ * (bf16; _f16 twins below), accumulation fp32.
+ * PARITY WITH THE HUB WEIGHTS UNPINNED: the network is restated from its public description (tests/vae_reference.py,
+ * tests/vae_encoder_reference.py).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Convolution, k in {1, 3}, stride 1, "same" zero padding, as an implicit GEMM over M = N*H*W output pixels:
  *   out[n, y, x, co] = bias[co] + sum_{ky, kx, c} in[n, y + ky - k/2, x + kx - k/2, c] * w[co][ky][kx][c]  (+ res[n, y, x, co])
@@ -858,6 +861,13 @@ typedef struct {
     int N, H, W, Cin, Cout, k, up2;
 } mapdit_vae_conv_t;
 int mapdit_vae_conv(const mapdit_vae_conv_t* args, void* stream);
+/* The stride-2 downsample of AutoencoderKL's Downsample2D (padding = 0): F.pad(x, (0, 1, 0, 1)) - one zero row at the bottom, one zero
+ * column at the right, nothing at the top or left - then a 3 x 3 convolution of stride 2 without padding:
+ *   out[n, y, x, co] = bias[co] + sum_{ky, kx, c} in[n, 2 y + ky, 2 x + kx, c] * w[co][ky][kx][c]
+ * `in` is [N, Hin, Win, Cin] (Hin, Win >= 2); args->H, args->W are the OUTPUT size and must equal Hin / 2, Win / 2 (rounded down);
+ * k == 3, up2 == 0.  A tap with 2 y + ky >= Hin or 2 x + kx >= Win is a zero that is never loaded (for an odd size the pad row is
+ * never touched).  The kernels, tile forms, K order and path selection are mapdit_vae_conv's; only the gather's coordinates differ. */
+int mapdit_vae_conv_down(const mapdit_vae_conv_t* args, int Hin, int Win, void* stream);
 /* GroupNorm over NHWC (+ SiLU when silu != 0): x fp32 [N, HW, C], G groups of C / G adjacent channels, biased variance;
  * out 16-bit [N, HW, C] = act((x - mean) * rstd * gamma + beta); stats (may be NULL) fp32 [N][G][2] = (mean, rstd).
  * Statistics: one pass over x - x[first element of the group] with fp64 sums, a fixed summation order, no atomics.
@@ -896,6 +906,41 @@ size_t mapdit_vae_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int h, 
  * unclamped.  Every launch goes to `stream`; no allocation, no synchronisation, no host read-back.  weights_host: the table above. */
 int mapdit_vae_decode(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* z, float* out, int N, int h, int w,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* The encoder.  Image preparation: img uint8 [N, H, W, C] as PIL / numpy hold it -> out fp32 NHWC, ((float)u / 255 - 0.5) / 0.5 in that
+ * order with IEEE division: bit-equal to ToTensor + Normalize(0.5, 0.5) (the one-multiply form u * (2 / 255) - 1 is not).  flip (may be
+ * NULL): [N] bytes, a non-zero entry mirrors that sample left-right; the decision is the caller's. */
+int mapdit_vae_prepare_u8(const uint8_t* img, const uint8_t* flip, float* out, int N, int H, int W, int C, void* stream);
+/* The posterior head (DiagonalGaussianDistribution).  moments fp32 NHWC [N, hw, 2L]: channels 0..L-1 the mean, L..2L-1 the raw
+ * log-variance.  mean, std, logvar (may be NULL) fp32 NCHW [N, L, hw]: logvar = clamp(raw, -30, 20), std = expf(0.5f * logvar) (the
+ * library function, not the fast intrinsic).  NaN propagates. */
+int mapdit_vae_posterior(const float* moments, float* mean, float* std, float* logvar, int N, int hw, int L, void* stream);
+/* Weight table of mapdit_vae_encode: MAPDIT_VAE_E_NUM_GLOBAL global slots, then MAPDIT_VAE_NUM_RESNET slots per resnet in execution
+ * order (down_blocks.i.resnets.j, then mid_block.resnets.0, .1), then MAPDIT_VAE_NUM_DOWN slots per downsampler (down_blocks.i,
+ * i < num_blocks - 1).  Packing and formats as in the decoder's table. */
+enum { MAPDIT_VAE_E_CONV_IN_W = 0, MAPDIT_VAE_E_CONV_IN_B, MAPDIT_VAE_E_ATTN_GN_G, MAPDIT_VAE_E_ATTN_GN_B, MAPDIT_VAE_E_ATTN_QKV_W,
+       MAPDIT_VAE_E_ATTN_QKV_B, MAPDIT_VAE_E_ATTN_OUT_W, MAPDIT_VAE_E_ATTN_OUT_B, MAPDIT_VAE_E_NORM_OUT_G, MAPDIT_VAE_E_NORM_OUT_B,
+       MAPDIT_VAE_E_CONV_OUT_W, MAPDIT_VAE_E_CONV_OUT_B, MAPDIT_VAE_E_QUANT_W, MAPDIT_VAE_E_QUANT_B, MAPDIT_VAE_E_NUM_GLOBAL };
+enum { MAPDIT_VAE_D_W = 0, MAPDIT_VAE_D_B, MAPDIT_VAE_NUM_DOWN };
+/* Bytes mapdit_vae_encode needs for N images of H x W (the decoder's formula with E, the token count and the GroupNorm scratch taken
+ * from the encoder's activations).  0 with a message in mapdit_last_error() when the shape is refused: the decoder's refusals, H or W
+ * not a multiple of 2^(num_blocks-1), or a latent token count (H / s) * (W / s) that is no multiple of 8. */
+size_t mapdit_vae_encode_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int H, int W);
+/* x fp32, x_kind MAPDIT_VAE_IN_F32 ([N, H, W, C]: what mapdit_vae_prepare_u8 writes) or MAPDIT_VAE_IN_F32_NCHW ([N, C, H, W]: a torch
+ * image batch), C = cfg->out_channels, values in [-1, 1] -> mean, std fp32 [N, latent_channels, H / s, W / s], s = 2^(num_blocks-1).
+ * conv_in; per block layers_per_block resnets (the decoder runs one more) and, but for the last, the downsample; the mid block;
+ * conv_norm_out + SiLU; conv_out; quant_conv; the posterior head.  Every launch goes to `stream`; no allocation, no synchronisation,
+ * no host read-back. */
+int mapdit_vae_encode(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* x, int x_kind, float* mean, float* std,
+                      int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+/* Mixture statistics of a latent data set (download_data.py:56-58): mean_c = E[m], var_c = E[s^2] + E[(m - mean_c)^2] over samples and
+ * pixels.  accumulate adds one batch's per-channel fp64 sums of m, m^2 and s^2 (mean, std fp32 [N, L, hw]) to acc[L][3] (zeroed by the
+ * caller before the first batch): a fixed summation order, no atomics, each sample's partial added to the running sum by one thread
+ * in sample order - so the sums are a function of the sequence of samples, whatever batches it is cut into.
+ * finish: ch_mean = sum m / count, ch_std = sqrt(sum s^2 / count + sum m^2 / count - ch_mean^2) in fp64, stored as fp32 [L];
+ * count = samples * hw.  Nothing is read back. */
+int mapdit_vae_stats_accumulate(const float* mean, const float* std, int N, int L, int hw, double* acc, void* stream);
+int mapdit_vae_stats_finish(const double* acc, double count, float* ch_mean, float* ch_std, int L, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
@@ -968,6 +1013,9 @@ int mapdit_vae_groupnorm_f16(const float* x, const float* gamma, const float* be
 int mapdit_vae_softmax_f16(const float* scores, int lds, uint16_t* probs, int ldp, int rows, int T, void* stream);
 int mapdit_vae_decode_f16(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* z, float* out, int N, int h, int w,
                           void* workspace, size_t workspace_bytes, void* stream);
+int mapdit_vae_conv_down_f16(const mapdit_vae_conv_t* args, int Hin, int Win, void* stream);
+int mapdit_vae_encode_f16(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* x, int x_kind, float* mean, float* std,
+                          int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import re
 from typing import NamedTuple
 
 SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
-           "uint16_t": C.c_uint16, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "int64_t": C.c_int64}
+           "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "int64_t": C.c_int64}
 
 
 class AbiError(ValueError):

@@ -1,5 +1,6 @@
-// VAE decoder (AutoencoderKL layout): convolution as an implicit GEMM on the MFMA, GroupNorm(+SiLU) over NHWC, a row softmax, and the
-// host plan that sequences a decode on one stream (mapdit.h, "VAE decoder").  Built once per 16-bit operand format (csrc/Makefile).
+// VAE (AutoencoderKL layout), both directions: convolution as an implicit GEMM on the MFMA, GroupNorm(+SiLU) over NHWC, a row softmax,
+// the encoder's pointwise kernels (image preparation, posterior head, latent statistics) and the two host plans that sequence a decode
+// or an encode on one stream (mapdit.h, "VAE").  Built once per 16-bit operand format (csrc/Makefile).
 //
 // Convolution.  out[m][co] = sum_K A[m][K] * w[co][K] with m = (n, y, x) flattened and K = (ky, kx, c): the weight is a plain row-major
 // [Cout][k*k*Cin] B operand, the A operand is gathered.  A workgroup (4 waves) owns 128 pixels x 64 or 128 output channels; a K tile is 64
@@ -10,6 +11,11 @@
 // padded to 72 elements (144 B: 16-byte aligned, consecutive rows 4 banks apart).
 // The K order of every output element is fixed and does not depend on where its pixel falls in a tile: a sample decoded alone and
 // in a batch gives the same bits.
+// One coordinate map serves the three forms: output pixel (y, x), tap (ky, kx) reads logical input (y * st + ky - pad, x * st + kx - pad),
+// tested against the logical extent (Hb, Wb), and stored at (yy >> up2, xx >> up2) of a [N, Hs, Ws, Cin] source.  "Same" convolution:
+// st = 1, pad = k / 2, extent = the output size.  up2: the extent is the upsampled size, the source half of it.  Stride-2 downsample
+// (F.pad(x, (0, 1, 0, 1)) + a 3 x 3 convolution of stride 2 without padding): st = 2, pad = 0, extent = source = (Hin, Win) - the pad row
+// and column are the taps at 2 y + ky == Hin, 2 x + kx == Win, zeros that are never loaded; nothing is added at the top or left.
 #include "common.h"
 
 MD_NS_OPEN
@@ -33,6 +39,7 @@ struct ConvP {
     void* out;
     int N, H, W, Cin, Cout, k, up2;
     long M;
+    int st, pad, Hb, Wb, Hs, Ws;      // the coordinate map (above)
 };
 
 constexpr int CBM = 128, CBK = 64, CLD = CBK + 8;
@@ -64,8 +71,8 @@ __global__ __launch_bounds__(256) void vae_conv_mfma_kernel(const ConvP p) {
     const long m0 = (long)blockIdx.x * CBM;
     const int co0 = blockIdx.y * BN;
     const int wr0 = BN == 128 ? (wave & 1) * 64 : wave * 32, wc0 = BN == 128 ? (wave >> 1) * 64 : 0;      // the wave's corner in the tile
-    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.k >> 1;
-    const int Hs = p.up2 ? H >> 1 : H, Ws = p.up2 ? W >> 1 : W;
+    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.pad, st = p.st;
+    const int Hb = p.Hb, Wb = p.Wb, Hs = p.Hs, Ws = p.Ws;
     const int cpt = Cin / CBK, nk = k * k * cpt;
     const size_t Ktot = (size_t)k * k * Cin;
 
@@ -91,10 +98,10 @@ __global__ __launch_bounds__(256) void vae_conv_mfma_kernel(const ConvP p) {
         const int ky = tap / k, kx = tap - ky * k;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const int yy = py[t] + ky - pad, xx = px[t] + kx - pad;
+            const int yy = py[t] * st + ky - pad, xx = px[t] * st + kx - pad;
             ra[t][0] = uint4{0u, 0u, 0u, 0u};
             ra[t][1] = uint4{0u, 0u, 0u, 0u};
-            if (pv[t] && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+            if (pv[t] && yy >= 0 && yy < Hb && xx >= 0 && xx < Wb) {
                 const int ys = p.up2 ? yy >> 1 : yy, xs = p.up2 ? xx >> 1 : xx;
                 load16<IN_F32>(p.in, (((size_t)pn[t] * Hs + ys) * Ws + xs) * Cin + c0, ra[t][0], ra[t][1]);
             }
@@ -178,17 +185,17 @@ __global__ __launch_bounds__(256) void vae_conv_plain_kernel(const ConvP p, int 
     if (idx >= p.M * p.Cout) return;
     const int co = (int)(idx % p.Cout);
     const long m = idx / p.Cout;
-    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.k >> 1;
-    const int Hs = p.up2 ? H >> 1 : H, Ws = p.up2 ? W >> 1 : W;
+    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.pad, st = p.st;
+    const int Hb = p.Hb, Wb = p.Wb, Hs = p.Hs, Ws = p.Ws;
     const int n = (int)(m / ((long)H * W)), rem = (int)(m % ((long)H * W)), y = rem / W, x = rem % W;
     const bf16_t* wr = p.w + (size_t)co * k * k * Cin;
     float acc = 0.f;
     for (int ky = 0; ky < k; ++ky) {
-        const int yy = y + ky - pad;
-        if (yy < 0 || yy >= H) continue;
+        const int yy = y * st + ky - pad;
+        if (yy < 0 || yy >= Hb) continue;
         for (int kx = 0; kx < k; ++kx) {
-            const int xx = x + kx - pad;
-            if (xx < 0 || xx >= W) continue;
+            const int xx = x * st + kx - pad;
+            if (xx < 0 || xx >= Wb) continue;
             const int ys = p.up2 ? yy >> 1 : yy, xs = p.up2 ? xx >> 1 : xx;
             const bf16_t* wt = wr + (size_t)(ky * k + kx) * Cin;
             if (in_kind == MAPDIT_VAE_IN_16) {
@@ -412,22 +419,126 @@ __global__ __launch_bounds__(256) void vae_softmax_kernel(const float* __restric
     for (int i = tid; i < T; i += 256) orow[i] = cvt16(__expf(row[i] - mx) * inv);
 }
 
+#if MAPDIT_DT == 0
+// ---- the encoder's pointwise kernels: fp32 and bytes only, so they are built once (no _f16 twin) -------------------------------------
+// uint8 [N, H, W, C] -> fp32 NHWC, ToTensor + Normalize(0.5, 0.5): ((float)u / 255 - 0.5) / 0.5 in that order, IEEE division (the
+// one-multiply form u * (2 / 255) - 1 rounds differently on 111 of the 256 bytes).  flip[n] != 0 mirrors sample n left-right.
+__global__ __launch_bounds__(256) void vae_prepare_u8_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ flip,
+                                                            float* __restrict__ out, long total, int H, int W, int C) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx % C);
+    const long pix = idx / C;
+    const int x = (int)(pix % W);
+    const long row = pix / W;                              // n * H + y
+    const int n = (int)(row / H);
+    const int xs = flip && flip[n] ? W - 1 - x : x;
+    const float u = (float)img[(row * W + xs) * C + c];
+    out[idx] = (u / 255.f - 0.5f) / 0.5f;
+}
+
+// DiagonalGaussianDistribution: moments fp32 NHWC [N, hw, 2L] -> mean, std (, logvar) fp32 NCHW [N, L, hw]; one thread per output element.
+// The clamp is written with comparisons so that a NaN log-variance stays NaN (fminf / fmaxf would drop it).
+__global__ __launch_bounds__(256) void vae_posterior_kernel(const float* __restrict__ mom, float* __restrict__ mean, float* __restrict__ std,
+                                                           float* __restrict__ logvar, long total, int hw, int L) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int px = (int)(idx % hw);
+    const long nl = idx / hw;
+    const int l = (int)(nl % L);
+    const long n = nl / L;
+    const float* mp = mom + (n * hw + px) * 2 * L;
+    const float raw = mp[L + l];
+    const float lv = raw < -30.f ? -30.f : raw > 20.f ? 20.f : raw;
+    mean[idx] = mp[l];
+    std[idx] = expf(0.5f * lv);
+    if (logvar) logvar[idx] = lv;
+}
+
+// Per-channel fp64 sums of m, m * m and s * s, added to acc[l][0..2]: one workgroup per channel walks the batch [N, L, hw] sample by
+// sample.  A sample's sums are formed in a fixed order - thread (element stride 256), wave (xor shuffles), the four waves through LDS -
+// and added to the running sums by thread 0, in sample order: no atomics, and the result is a function of the sequence of samples,
+// not of how it is cut into batches.
+__global__ __launch_bounds__(256) void vae_stats_accumulate_kernel(const float* __restrict__ mean, const float* __restrict__ std, int N, int L,
+                                                                  int hw, double* __restrict__ acc) {
+    __shared__ double red[3][4];
+    const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double run[3] = {0.0, 0.0, 0.0};
+    if (tid == 0)
+        for (int j = 0; j < 3; ++j) run[j] = acc[l * 3 + j];
+    for (int n = 0; n < N; ++n) {
+        const size_t base = ((size_t)n * L + l) * hw;
+        double a = 0.0, b = 0.0, c = 0.0;
+        for (int i = tid; i < hw; i += 256) {
+            const double m = (double)mean[base + i], s = (double)std[base + i];
+            a += m;
+            b += m * m;
+            c += s * s;
+        }
+        a = wave_sum_d(a);
+        b = wave_sum_d(b);
+        c = wave_sum_d(c);
+        if (lane == 0) {
+            red[0][wave] = a;
+            red[1][wave] = b;
+            red[2][wave] = c;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int j = 0; j < 3; ++j) run[j] += ((red[j][0] + red[j][1]) + red[j][2]) + red[j][3];
+        __syncthreads();                                   // red is free for the next sample
+    }
+    if (tid == 0)
+        for (int j = 0; j < 3; ++j) acc[l * 3 + j] = run[j];
+}
+
+// mean_c = sum m / n, std_c = sqrt(sum s^2 / n + sum m^2 / n - mean_c^2) in fp64 (the reference's E[s^2] + E[(m - mean_c)^2]), stored as fp32
+__global__ void vae_stats_finish_kernel(const double* __restrict__ acc, double count, float* __restrict__ ch_mean, float* __restrict__ ch_std, int L) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= L) return;
+    const double m = acc[l * 3] / count;
+    double var = acc[l * 3 + 2] / count + (acc[l * 3 + 1] / count - m * m);
+    var = var < 0.0 ? 0.0 : var;                           // (a NaN stays a NaN)
+    ch_mean[l] = (float)m;
+    ch_std[l] = (float)sqrt(var);
+}
+#endif
+
 MD_NS_CLOSE
 
+#define VAE_TRY(call)                    \
+    do {                                 \
+        const int rc_ = (call);          \
+        if (rc_ != MAPDIT_OK) return rc_; \
+    } while (0)
+
 // ---- entry points -----------------------------------------------------------------------------------------------------------------
-extern "C" int MD_SYM(vae_conv)(const mapdit_vae_conv_t* a, void* stream) {
-    MD_CHECK(a && a->in && a->w && a->bias && a->out, "vae_conv: null argument");
-    MD_CHECK(a->k == 1 || a->k == 3, "vae_conv: k=%d (1 or 3)", a->k);
-    MD_CHECK(a->N > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, "vae_conv: empty shape N=%d H=%d W=%d Cin=%d Cout=%d", a->N, a->H,
+// mapdit_vae_conv (Hin = Win = 0) and mapdit_vae_conv_down (the input size) are one launch path: only the coordinate map differs.
+static int vae_conv_launch(const char* who, const mapdit_vae_conv_t* a, int Hin, int Win, bool down, void* stream) {
+    MD_CHECK(a && a->in && a->w && a->bias && a->out, "%s: null argument", who);
+    if (down) MD_CHECK(a->k == 3, "%s: k=%d (the downsample is a 3 x 3 convolution)", who, a->k);
+    else MD_CHECK(a->k == 1 || a->k == 3, "%s: k=%d (1 or 3)", who, a->k);
+    MD_CHECK(a->N > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, "%s: empty shape N=%d H=%d W=%d Cin=%d Cout=%d", who, a->N, a->H,
              a->W, a->Cin, a->Cout);
-    MD_CHECK(a->in_kind >= MAPDIT_VAE_IN_16 && a->in_kind <= MAPDIT_VAE_IN_F32_NCHW, "vae_conv: bad in_kind %d", a->in_kind);
-    MD_CHECK(a->out_kind >= MAPDIT_VAE_OUT_F32 && a->out_kind <= MAPDIT_VAE_OUT_16, "vae_conv: bad out_kind %d", a->out_kind);
-    MD_CHECK(!a->up2 || (a->H % 2 == 0 && a->W % 2 == 0), "vae_conv: up2 needs even H=%d, W=%d", a->H, a->W);
-    MD_CHECK(!(a->res && a->out_kind == MAPDIT_VAE_OUT_F32_NCHW), "vae_conv: no residual with the NCHW store");
+    MD_CHECK(a->in_kind >= MAPDIT_VAE_IN_16 && a->in_kind <= MAPDIT_VAE_IN_F32_NCHW, "%s: bad in_kind %d", who, a->in_kind);
+    MD_CHECK(a->out_kind >= MAPDIT_VAE_OUT_F32 && a->out_kind <= MAPDIT_VAE_OUT_16, "%s: bad out_kind %d", who, a->out_kind);
+    if (down) {
+        MD_CHECK(!a->up2, "%s: up2=%d (a downsample reads no upsampled input)", who, a->up2);
+        MD_CHECK(Hin >= 2 && Win >= 2, "%s: input of %d x %d (2 x 2 at the least)", who, Hin, Win);
+        MD_CHECK(a->H == Hin / 2 && a->W == Win / 2, "%s: output %d x %d of a %d x %d input (%d x %d expected: half, rounded down)", who, a->H,
+                 a->W, Hin, Win, Hin / 2, Win / 2);
+        MD_CHECK((long)a->N * Hin * Win < (1L << 31), "%s: %ld input pixels are too many", who, (long)a->N * Hin * Win);
+    } else {
+        MD_CHECK(!a->up2 || (a->H % 2 == 0 && a->W % 2 == 0), "%s: up2 needs even H=%d, W=%d", who, a->H, a->W);
+    }
+    MD_CHECK(!(a->res && a->out_kind == MAPDIT_VAE_OUT_F32_NCHW), "%s: no residual with the NCHW store", who);
     const long M = (long)a->N * a->H * a->W;
-    MD_CHECK(M * a->Cout < (1L << 40) && M < (1L << 31), "vae_conv: %ld output pixels are too many", M);
+    MD_CHECK(M * a->Cout < (1L << 40) && M < (1L << 31), "%s: %ld output pixels are too many", who, M);
     hipStream_t st = (hipStream_t)stream;
-    const ConvP p{a->in, (const bf16_t*)a->w, a->bias, a->res, a->out, a->N, a->H, a->W, a->Cin, a->Cout, a->k, a->up2 ? 1 : 0, M};
+    const int up2 = a->up2 ? 1 : 0;
+    const ConvP p{a->in, (const bf16_t*)a->w, a->bias, a->res, a->out, a->N, a->H, a->W, a->Cin, a->Cout, a->k, up2, M,
+                  down ? 2 : 1, down ? 0 : a->k >> 1, down ? Hin : a->H, down ? Win : a->W,
+                  down ? Hin : up2 ? a->H >> 1 : a->H, down ? Win : up2 ? a->W >> 1 : a->W};
     const bool aligned = !(((uintptr_t)a->in | (uintptr_t)a->w) & 15);
     if (a->Cin % CBK == 0 && a->Cout % 64 == 0 && a->in_kind != MAPDIT_VAE_IN_F32_NCHW && a->out_kind != MAPDIT_VAE_OUT_F32_NCHW && aligned) {
         const bool f32 = a->in_kind == MAPDIT_VAE_IN_F32, o16 = a->out_kind == MAPDIT_VAE_OUT_16, wide = a->Cout % 128 == 0;
@@ -443,11 +554,17 @@ extern "C" int MD_SYM(vae_conv)(const mapdit_vae_conv_t* a, void* stream) {
         else VAE_CONV_GO(0, 0);
 #undef VAE_CONV_GO
     } else {
-        MD_CHECK(M * a->Cout < (1L << 38), "vae_conv: %ld x %d outputs are too many for the plain kernel", M, a->Cout);
+        MD_CHECK(M * a->Cout < (1L << 38), "%s: %ld x %d outputs are too many for the plain kernel", who, M, a->Cout);
         vae_conv_plain_kernel<<<cdiv(M * a->Cout, 256), 256, 0, st>>>(p, a->in_kind, a->out_kind);
     }
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(vae_conv)(const mapdit_vae_conv_t* a, void* stream) { return vae_conv_launch("vae_conv", a, 0, 0, false, stream); }
+
+extern "C" int MD_SYM(vae_conv_down)(const mapdit_vae_conv_t* a, int Hin, int Win, void* stream) {
+    return vae_conv_launch("vae_conv_down", a, Hin, Win, true, stream);
 }
 
 extern "C" int MD_SYM(vae_groupnorm)(const float* x, const float* gamma, const float* beta, float eps, int silu, uint16_t* out, float* stats,
@@ -478,10 +595,50 @@ extern "C" int MD_SYM(vae_softmax)(const float* scores, int lds, uint16_t* probs
     return MAPDIT_OK;
 }
 
-// ---- the decoder plan -------------------------------------------------------------------------------------------------------------
+// ---- the pointwise entry points of the encoder (one build) --------------------------------------------------------------------------
+#if MAPDIT_DT == 0
+extern "C" int mapdit_vae_prepare_u8(const uint8_t* img, const uint8_t* flip, float* out, int N, int H, int W, int C, void* stream) {
+    MD_CHECK(img && out, "vae_prepare_u8: null argument");
+    MD_CHECK(N > 0 && H > 0 && W > 0 && C > 0, "vae_prepare_u8: N=%d, H=%d, W=%d, C=%d must be positive", N, H, W, C);
+    const long total = (long)N * H * W * C;
+    MD_CHECK(total < (1L << 38), "vae_prepare_u8: %ld elements are too many for one call", total);
+    vae_prepare_u8_kernel<<<cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(img, flip, out, total, H, W, C);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_vae_posterior(const float* moments, float* mean, float* std, float* logvar, int N, int hw, int L, void* stream) {
+    MD_CHECK(moments && mean && std, "vae_posterior: null argument");
+    MD_CHECK(N > 0 && hw > 0 && L > 0, "vae_posterior: N=%d, hw=%d, L=%d must be positive", N, hw, L);
+    const long total = (long)N * hw * L;
+    MD_CHECK(total < (1L << 38), "vae_posterior: %ld elements are too many for one call", total);
+    vae_posterior_kernel<<<cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(moments, mean, std, logvar, total, hw, L);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_vae_stats_accumulate(const float* mean, const float* std, int N, int L, int hw, double* acc, void* stream) {
+    MD_CHECK(mean && std && acc, "vae_stats_accumulate: null argument");
+    MD_CHECK(N > 0 && L > 0 && hw > 0, "vae_stats_accumulate: N=%d, L=%d, hw=%d must be positive", N, L, hw);
+    MD_CHECK(!((uintptr_t)acc & 7), "vae_stats_accumulate: acc must be 8-byte aligned");
+    vae_stats_accumulate_kernel<<<L, 256, 0, (hipStream_t)stream>>>(mean, std, N, L, hw, acc);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_vae_stats_finish(const double* acc, double count, float* ch_mean, float* ch_std, int L, void* stream) {
+    MD_CHECK(acc && ch_mean && ch_std, "vae_stats_finish: null argument");
+    MD_CHECK(L > 0 && count > 0.0, "vae_stats_finish: L=%d and count=%g must be positive", L, count);
+    vae_stats_finish_kernel<<<cdiv(L, 64), 64, 0, (hipStream_t)stream>>>(acc, count, ch_mean, ch_std, L);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+#endif
+
+// ---- the two plans ------------------------------------------------------------------------------------------------------------------
 namespace {
 struct VaePlan {
-    int C[4];          // widths in the decoder's order (reversed block_out_channels)
+    int C[4];          // widths in execution order: the decoder walks block_out_channels reversed, the encoder as listed
     int nb;
     size_t maxE;       // largest activation, elements
     size_t off_x, off_y, off_h, off_a, off_qkv, off_s, off_p, off_gn, gn_bytes, total;
@@ -489,8 +646,8 @@ struct VaePlan {
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// 0 = ok; otherwise the message is set
-int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
+// the config checks both directions share; fills nb and C.  0 = ok; otherwise the message is set
+int vae_plan_config(const mapdit_vae_config_t* cfg, int N, int h, int w, bool reversed, VaePlan* pl) {
     MD_CHECK(cfg, "vae: null config");
     MD_CHECK(N > 0 && h > 0 && w > 0, "vae: N=%d, h=%d, w=%d must be positive", N, h, w);
     MD_CHECK(cfg->num_blocks >= 1 && cfg->num_blocks <= 4, "vae: num_blocks=%d (1..4 block widths)", cfg->num_blocks);
@@ -500,11 +657,34 @@ int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
     const int ch[4] = {cfg->ch0, cfg->ch1, cfg->ch2, cfg->ch3};
     pl->nb = cfg->num_blocks;
     for (int i = 0; i < pl->nb; ++i) {
-        const int c = ch[pl->nb - 1 - i];
+        const int c = ch[reversed ? pl->nb - 1 - i : i];
         MD_CHECK(c > 0 && c % cfg->norm_num_groups == 0, "vae: channel width %d is not a multiple of the norm groups (%d)", c, cfg->norm_num_groups);
         MD_CHECK(c % 8 == 0, "vae: channel width %d is not a multiple of 8 (16-bit operand rows of 16 bytes)", c);
         pl->C[i] = c;
     }
+    return MAPDIT_OK;
+}
+
+// the workspace of either direction: three fp32 and one 16-bit activation of maxE elements, the attention buffers for T tokens of
+// width Cmid, and the split GroupNorm's partial sums for images of max_hw pixels
+void vae_plan_layout(VaePlan* pl, size_t maxE, int N, size_t T, int Cmid, size_t max_hw, int G) {
+    pl->maxE = maxE;
+    size_t o = 0;
+    pl->off_x = o; o += up256(maxE * 4);
+    pl->off_y = o; o += up256(maxE * 4);
+    pl->off_h = o; o += up256(maxE * 4);
+    pl->off_a = o; o += up256(maxE * 2);
+    pl->off_qkv = o; o += up256((size_t)N * T * 3 * Cmid * 2);
+    pl->off_s = o; o += up256(T * T * 4);
+    pl->off_p = o; o += up256(T * T * 2);
+    // partial sums of the split GroupNorm: per sample, 1,024-pixel chunk of the largest image and group, two fp64
+    pl->gn_bytes = (size_t)N * (size_t)cdiv((long)max_hw, GN_PX) * G * 2 * sizeof(double);
+    pl->off_gn = o; o += up256(pl->gn_bytes);
+    pl->total = o;
+}
+
+int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
+    VAE_TRY(vae_plan_config(cfg, N, h, w, true, pl));
     MD_CHECK((long)h * w % 8 == 0, "vae: h*w = %ld tokens in the mid-block attention must be a multiple of 8 (operand alignment of its GEMMs)", (long)h * w);
     MD_CHECK((long)N * h * w * (1L << (2 * (pl->nb - 1))) < (1L << 31), "vae: N=%d latents of %d x %d are too many output pixels for one call", N, h, w);
     size_t px = (size_t)N * h * w, maxE = px * (size_t)pl->C[0];
@@ -518,97 +698,95 @@ int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
             maxE = px * (size_t)cin > maxE ? px * (size_t)cin : maxE;
         }
     }
-    pl->maxE = maxE;
-    const size_t T = (size_t)h * w;
-    size_t o = 0;
-    pl->off_x = o; o += up256(maxE * 4);
-    pl->off_y = o; o += up256(maxE * 4);
-    pl->off_h = o; o += up256(maxE * 4);
-    pl->off_a = o; o += up256(maxE * 2);
-    pl->off_qkv = o; o += up256((size_t)N * T * 3 * pl->C[0] * 2);
-    pl->off_s = o; o += up256(T * T * 4);
-    pl->off_p = o; o += up256(T * T * 2);
-    // partial sums of the split GroupNorm: per sample, 1,024-pixel chunk of the largest image and group, two fp64
-    pl->gn_bytes = (size_t)N * (size_t)cdiv((long)(px / N), GN_PX) * cfg->norm_num_groups * 2 * sizeof(double);
-    pl->off_gn = o; o += up256(pl->gn_bytes);
-    pl->total = o;
+    vae_plan_layout(pl, maxE, N, (size_t)h * w, pl->C[0], px / N, cfg->norm_num_groups);
     return MAPDIT_OK;
 }
-}  // namespace
 
-#if MAPDIT_DT == 0
-extern "C" size_t mapdit_vae_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int h, int w) {
-    VaePlan pl;
-    return vae_plan(cfg, N, h, w, &pl) == MAPDIT_OK ? pl.total : 0;
-}
-#endif
-
-#define VAE_TRY(call)                    \
-    do {                                 \
-        const int rc_ = (call);          \
-        if (rc_ != MAPDIT_OK) return rc_; \
-    } while (0)
-
-extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* const* wt, const float* z, float* out, int N, int h, int w,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    VaePlan pl;
-    VAE_TRY(vae_plan(cfg, N, h, w, &pl));
-    MD_CHECK(wt && z && out && workspace, "vae_decode: null argument");
-    MD_CHECK(workspace_bytes >= pl.total, "vae_decode: workspace of %zu bytes, %zu needed (mapdit_vae_workspace_bytes)", workspace_bytes, pl.total);
-    MD_CHECK(!((uintptr_t)workspace & 255), "vae_decode: the workspace must be 256-byte aligned");
-    const int nres = 2 + pl.nb * (cfg->layers_per_block + 1);
-    const int nslots = MAPDIT_VAE_NUM_GLOBAL + nres * MAPDIT_VAE_NUM_RESNET + (pl.nb - 1) * MAPDIT_VAE_NUM_UP;
-    for (int i = 0; i < nslots; ++i) {
-        const int rs = i - MAPDIT_VAE_NUM_GLOBAL;
-        const bool optional = rs >= 0 && rs < nres * MAPDIT_VAE_NUM_RESNET &&
-                              (rs % MAPDIT_VAE_NUM_RESNET == MAPDIT_VAE_R_SC_W || rs % MAPDIT_VAE_NUM_RESNET == MAPDIT_VAE_R_SC_B);
-        MD_CHECK(wt[i] || optional, "vae_decode: weight slot %d is null", i);
+// the encoder: N images of H x W
+int vae_encode_plan(const mapdit_vae_config_t* cfg, int N, int H, int W, VaePlan* pl) {
+    VAE_TRY(vae_plan_config(cfg, N, H, W, false, pl));
+    const int s = 1 << (pl->nb - 1);
+    MD_CHECK(H % s == 0 && W % s == 0, "vae encode: an image of %d x %d is not a multiple of %d (2^(num_blocks - 1): every downsample halves an even size)", H, W, s);
+    const long T = (long)(H / s) * (W / s);
+    MD_CHECK(T % 8 == 0, "vae encode: (H / %d) * (W / %d) = %ld tokens in the mid-block attention must be a multiple of 8 (operand alignment of its GEMMs)", s, s, T);
+    MD_CHECK((long)N * H * W < (1L << 31), "vae encode: N=%d images of %d x %d are too many pixels for one call", N, H, W);
+    size_t px = (size_t)N * H * W, maxE = px * (size_t)pl->C[0];
+    int cin = pl->C[0];
+    for (int i = 0; i < pl->nb; ++i) {
+        const size_t e = px * (size_t)(cin > pl->C[i] ? cin : pl->C[i]);
+        maxE = e > maxE ? e : maxE;
+        cin = pl->C[i];
+        if (i < pl->nb - 1) px /= 4;
     }
-    char* ws = (char*)workspace;
-    float* X = (float*)(ws + pl.off_x);
-    float* Y = (float*)(ws + pl.off_y);
-    float* Hb = (float*)(ws + pl.off_h);
-    uint16_t* A16 = (uint16_t*)(ws + pl.off_a);
-    uint16_t* QKV = (uint16_t*)(ws + pl.off_qkv);
-    float* S = (float*)(ws + pl.off_s);
-    uint16_t* P = (uint16_t*)(ws + pl.off_p);
-    const int G = cfg->norm_num_groups;
-    const float eps = cfg->norm_eps;
+    const size_t mom = px * 2 * (size_t)cfg->latent_channels;          // conv_out / quant_conv outputs
+    maxE = mom > maxE ? mom : maxE;
+    vae_plan_layout(pl, maxE, N, (size_t)T, pl->C[pl->nb - 1], (size_t)H * W, cfg->norm_num_groups);
+    return MAPDIT_OK;
+}
 
-    auto conv = [&](const void* in, int in_kind, const void* wgt, const void* bias, const float* res, void* o, int out_kind, int H, int W, int Cin,
-                    int Cout, int k, int up2) {
+// What a plan runs with: the workspace's buffers and the launches both directions are made of.  The resnet and the mid-block
+// attention are the same code in the decoder and the encoder; X holds the residual stream on entry and on return.
+struct VaeRun {
+    const char* who;
+    int N, G;
+    float eps;
+    void* stream;
+    float *X, *Y, *Hb;
+    uint16_t *A16, *QKV;
+    float* S;
+    uint16_t* P;
+    void* gn_scratch;
+    size_t gn_bytes;
+
+    VaeRun(const char* who_, const mapdit_vae_config_t* cfg, const VaePlan& pl, int N_, void* workspace, void* stream_)
+        : who(who_), N(N_), G(cfg->norm_num_groups), eps(cfg->norm_eps), stream(stream_) {
+        char* ws = (char*)workspace;
+        X = (float*)(ws + pl.off_x);
+        Y = (float*)(ws + pl.off_y);
+        Hb = (float*)(ws + pl.off_h);
+        A16 = (uint16_t*)(ws + pl.off_a);
+        QKV = (uint16_t*)(ws + pl.off_qkv);
+        S = (float*)(ws + pl.off_s);
+        P = (uint16_t*)(ws + pl.off_p);
+        gn_scratch = ws + pl.off_gn;
+        gn_bytes = pl.gn_bytes;
+    }
+    void swap_xy() {
+        float* t = X;
+        X = Y;
+        Y = t;
+    }
+    int conv(const void* in, int in_kind, const void* wgt, const void* bias, const float* res, void* o, int out_kind, int H, int W, int Cin, int Cout,
+             int k, int up2) const {
         const mapdit_vae_conv_t a{in, in_kind, (const uint16_t*)wgt, (const float*)bias, res, o, out_kind, N, H, W, Cin, Cout, k, up2};
         return MD_SYM(vae_conv)(&a, stream);
-    };
-    auto gn = [&](const float* x, const void* g, const void* b, int silu, int HW, int C) {
-        return MD_SYM(vae_groupnorm)(x, (const float*)g, (const float*)b, eps, silu, A16, nullptr, N, HW, C, G, ws + pl.off_gn, pl.gn_bytes, stream);
-    };
-    int rix = 0;      // resnets in execution order
-    // X [N, H, W, cin] -> X [N, H, W, cout]
-    auto resnet = [&](int H, int W, int cin, int cout) {
-        const void* const* r = wt + MAPDIT_VAE_NUM_GLOBAL + (rix++) * MAPDIT_VAE_NUM_RESNET;
+    }
+    // [N, Hin, Win, C] -> [N, Hin / 2, Win / 2, C]
+    int conv_down(const void* in, int in_kind, const void* wgt, const void* bias, void* o, int out_kind, int Hin, int Win, int Cin, int Cout) const {
+        const mapdit_vae_conv_t a{in, in_kind, (const uint16_t*)wgt, (const float*)bias, nullptr, o, out_kind, N, Hin / 2, Win / 2, Cin, Cout, 3, 0};
+        return MD_SYM(vae_conv_down)(&a, Hin, Win, stream);
+    }
+    int gn(const float* x, const void* g, const void* b, int silu, int HW, int C) const {
+        return MD_SYM(vae_groupnorm)(x, (const float*)g, (const float*)b, eps, silu, A16, nullptr, N, HW, C, G, gn_scratch, gn_bytes, stream);
+    }
+    // X [N, H, W, cin] -> X [N, H, W, cout]; r: the resnet's MAPDIT_VAE_NUM_RESNET slots, rix its number in execution order
+    int resnet(const void* const* r, int rix, int H, int W, int cin, int cout) const {
         const bool sc = cin != cout;
-        MD_CHECK(!sc || (r[MAPDIT_VAE_R_SC_W] && r[MAPDIT_VAE_R_SC_B]), "vae_decode: resnet %d maps %d -> %d channels and has no conv_shortcut", rix - 1, cin, cout);
+        MD_CHECK(!sc || (r[MAPDIT_VAE_R_SC_W] && r[MAPDIT_VAE_R_SC_B]), "%s: resnet %d maps %d -> %d channels and has no conv_shortcut", who, rix, cin, cout);
         VAE_TRY(gn(X, r[MAPDIT_VAE_R_N1_G], r[MAPDIT_VAE_R_N1_B], 1, H * W, cin));
         VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C1_W], r[MAPDIT_VAE_R_C1_B], nullptr, Hb, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 3, 0));
         VAE_TRY(gn(Hb, r[MAPDIT_VAE_R_N2_G], r[MAPDIT_VAE_R_N2_B], 1, H * W, cout));
         if (sc) VAE_TRY(conv(X, MAPDIT_VAE_IN_F32, r[MAPDIT_VAE_R_SC_W], r[MAPDIT_VAE_R_SC_B], nullptr, Y, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 1, 0));
         // (same widths: the residual is read and the sum written in place, element by element, by the thread that owns it)
         VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C2_W], r[MAPDIT_VAE_R_C2_B], sc ? Y : X, X, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 0));
-        return (int)MAPDIT_OK;
-    };
-
-    int H = h, W = w;
-    const int C0 = pl.C[0], L = cfg->latent_channels;
-    // post_quant_conv (reads z as NCHW) and conv_in
-    VAE_TRY(conv(z, MAPDIT_VAE_IN_F32_NCHW, wt[MAPDIT_VAE_W_PQ_W], wt[MAPDIT_VAE_W_PQ_B], nullptr, Hb, MAPDIT_VAE_OUT_F32, H, W, L, L, 1, 0));
-    VAE_TRY(conv(Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_CONV_IN_W], wt[MAPDIT_VAE_W_CONV_IN_B], nullptr, X, MAPDIT_VAE_OUT_F32, H, W, L, C0, 3, 0));
-    // mid block
-    VAE_TRY(resnet(H, W, C0, C0));
-    {
+        return MAPDIT_OK;
+    }
+    // the mid block's single-head attention over the T = H * W pixels of each sample, X += out(softmax(q k^T / sqrt(C)) v)
+    int attention(const void* gn_g, const void* gn_b, const void* qkv_w, const void* qkv_b, const void* out_w, const void* out_b, int H, int W,
+                  int C0) const {
         const int T = H * W;
-        VAE_TRY(gn(X, wt[MAPDIT_VAE_W_ATTN_GN_G], wt[MAPDIT_VAE_W_ATTN_GN_B], 0, T, C0));
-        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_ATTN_QKV_W], wt[MAPDIT_VAE_W_ATTN_QKV_B], nullptr, QKV, MAPDIT_VAE_OUT_16, H, W, C0, 3 * C0, 1, 0));
+        VAE_TRY(gn(X, gn_g, gn_b, 0, T, C0));
+        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, qkv_w, qkv_b, nullptr, QKV, MAPDIT_VAE_OUT_16, H, W, C0, 3 * C0, 1, 0));
         for (int n = 0; n < N; ++n) {
             const uint16_t* qn = QKV + (size_t)n * T * 3 * C0;
             mapdit_epilogue_t e{};
@@ -625,8 +803,60 @@ extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* co
             e2.alpha = 1.f;
             VAE_TRY(MD_SYM_GEMM(MAPDIT_NN, T, C0, T, P, T, qn + 2 * C0, 3 * C0, &e2, stream));
         }
-        VAE_TRY(conv(Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_ATTN_OUT_W], wt[MAPDIT_VAE_W_ATTN_OUT_B], X, X, MAPDIT_VAE_OUT_F32, H, W, C0, C0, 1, 0));
+        return conv(Hb, MAPDIT_VAE_IN_F32, out_w, out_b, X, X, MAPDIT_VAE_OUT_F32, H, W, C0, C0, 1, 0);
     }
+};
+
+// every slot but a resnet's conv_shortcut pair must be set
+int vae_check_table(const char* who, const void* const* wt, int nglobal, int nres, int ntail) {
+    const int nslots = nglobal + nres * MAPDIT_VAE_NUM_RESNET + ntail;
+    for (int i = 0; i < nslots; ++i) {
+        const int rs = i - nglobal;
+        const bool optional = rs >= 0 && rs < nres * MAPDIT_VAE_NUM_RESNET &&
+                              (rs % MAPDIT_VAE_NUM_RESNET == MAPDIT_VAE_R_SC_W || rs % MAPDIT_VAE_NUM_RESNET == MAPDIT_VAE_R_SC_B);
+        MD_CHECK(wt[i] || optional, "%s: weight slot %d is null", who, i);
+    }
+    return MAPDIT_OK;
+}
+}  // namespace
+
+#if MAPDIT_DT == 0
+extern "C" size_t mapdit_vae_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int h, int w) {
+    VaePlan pl;
+    return vae_plan(cfg, N, h, w, &pl) == MAPDIT_OK ? pl.total : 0;
+}
+
+extern "C" size_t mapdit_vae_encode_workspace_bytes(const mapdit_vae_config_t* cfg, int N, int H, int W) {
+    VaePlan pl;
+    return vae_encode_plan(cfg, N, H, W, &pl) == MAPDIT_OK ? pl.total : 0;
+}
+#endif
+
+extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* const* wt, const float* z, float* out, int N, int h, int w,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    VaePlan pl;
+    VAE_TRY(vae_plan(cfg, N, h, w, &pl));
+    MD_CHECK(wt && z && out && workspace, "vae_decode: null argument");
+    MD_CHECK(workspace_bytes >= pl.total, "vae_decode: workspace of %zu bytes, %zu needed (mapdit_vae_workspace_bytes)", workspace_bytes, pl.total);
+    MD_CHECK(!((uintptr_t)workspace & 255), "vae_decode: the workspace must be 256-byte aligned");
+    const int nres = 2 + pl.nb * (cfg->layers_per_block + 1);
+    VAE_TRY(vae_check_table("vae_decode", wt, MAPDIT_VAE_NUM_GLOBAL, nres, (pl.nb - 1) * MAPDIT_VAE_NUM_UP));
+    VaeRun r("vae_decode", cfg, pl, N, workspace, stream);
+    int rix = 0;      // resnets in execution order
+    auto resnet = [&](int H, int W, int cin, int cout) {
+        const int i = rix++;
+        return r.resnet(wt + MAPDIT_VAE_NUM_GLOBAL + i * MAPDIT_VAE_NUM_RESNET, i, H, W, cin, cout);
+    };
+
+    int H = h, W = w;
+    const int C0 = pl.C[0], L = cfg->latent_channels;
+    // post_quant_conv (reads z as NCHW) and conv_in
+    VAE_TRY(r.conv(z, MAPDIT_VAE_IN_F32_NCHW, wt[MAPDIT_VAE_W_PQ_W], wt[MAPDIT_VAE_W_PQ_B], nullptr, r.Hb, MAPDIT_VAE_OUT_F32, H, W, L, L, 1, 0));
+    VAE_TRY(r.conv(r.Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_CONV_IN_W], wt[MAPDIT_VAE_W_CONV_IN_B], nullptr, r.X, MAPDIT_VAE_OUT_F32, H, W, L, C0, 3, 0));
+    // mid block
+    VAE_TRY(resnet(H, W, C0, C0));
+    VAE_TRY(r.attention(wt[MAPDIT_VAE_W_ATTN_GN_G], wt[MAPDIT_VAE_W_ATTN_GN_B], wt[MAPDIT_VAE_W_ATTN_QKV_W], wt[MAPDIT_VAE_W_ATTN_QKV_B],
+                        wt[MAPDIT_VAE_W_ATTN_OUT_W], wt[MAPDIT_VAE_W_ATTN_OUT_B], H, W, C0));
     VAE_TRY(resnet(H, W, C0, C0));
     // up blocks
     int cin = C0;
@@ -641,14 +871,61 @@ extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* co
             const void* const* u = ups + i * MAPDIT_VAE_NUM_UP;
             H *= 2;
             W *= 2;
-            VAE_TRY(conv(X, MAPDIT_VAE_IN_F32, u[MAPDIT_VAE_U_W], u[MAPDIT_VAE_U_B], nullptr, Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 1));
-            float* t = X;
-            X = Y;
-            Y = t;
+            VAE_TRY(r.conv(r.X, MAPDIT_VAE_IN_F32, u[MAPDIT_VAE_U_W], u[MAPDIT_VAE_U_B], nullptr, r.Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 1));
+            r.swap_xy();
         }
     }
-    VAE_TRY(gn(X, wt[MAPDIT_VAE_W_NORM_OUT_G], wt[MAPDIT_VAE_W_NORM_OUT_B], 1, H * W, cin));
-    VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_CONV_OUT_W], wt[MAPDIT_VAE_W_CONV_OUT_B], nullptr, out, MAPDIT_VAE_OUT_F32_NCHW, H, W, cin,
-                 cfg->out_channels, 3, 0));
+    VAE_TRY(r.gn(r.X, wt[MAPDIT_VAE_W_NORM_OUT_G], wt[MAPDIT_VAE_W_NORM_OUT_B], 1, H * W, cin));
+    VAE_TRY(r.conv(r.A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_CONV_OUT_W], wt[MAPDIT_VAE_W_CONV_OUT_B], nullptr, out, MAPDIT_VAE_OUT_F32_NCHW, H, W, cin,
+                   cfg->out_channels, 3, 0));
     return MAPDIT_OK;
+}
+
+// x [N, H, W, C] (MAPDIT_VAE_IN_F32) or [N, C, H, W] (MAPDIT_VAE_IN_F32_NCHW) -> mean, std fp32 [N, L, H / s, W / s]
+extern "C" int MD_SYM(vae_encode)(const mapdit_vae_config_t* cfg, const void* const* wt, const float* x, int x_kind, float* mean, float* std, int N,
+                                  int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+    VaePlan pl;
+    VAE_TRY(vae_encode_plan(cfg, N, H, W, &pl));
+    MD_CHECK(wt && x && mean && std && workspace, "vae_encode: null argument");
+    MD_CHECK(x_kind == MAPDIT_VAE_IN_F32 || x_kind == MAPDIT_VAE_IN_F32_NCHW, "vae_encode: x_kind=%d (MAPDIT_VAE_IN_F32 or MAPDIT_VAE_IN_F32_NCHW)", x_kind);
+    MD_CHECK(workspace_bytes >= pl.total, "vae_encode: workspace of %zu bytes, %zu needed (mapdit_vae_encode_workspace_bytes)", workspace_bytes, pl.total);
+    MD_CHECK(!((uintptr_t)workspace & 255), "vae_encode: the workspace must be 256-byte aligned");
+    const int nres = pl.nb * cfg->layers_per_block + 2;
+    VAE_TRY(vae_check_table("vae_encode", wt, MAPDIT_VAE_E_NUM_GLOBAL, nres, (pl.nb - 1) * MAPDIT_VAE_NUM_DOWN));
+    VaeRun r("vae_encode", cfg, pl, N, workspace, stream);
+    int rix = 0;
+    auto resnet = [&](int h, int w, int cin, int cout) {
+        const int i = rix++;
+        return r.resnet(wt + MAPDIT_VAE_E_NUM_GLOBAL + i * MAPDIT_VAE_NUM_RESNET, i, h, w, cin, cout);
+    };
+
+    const int L2 = 2 * cfg->latent_channels;
+    VAE_TRY(r.conv(x, x_kind, wt[MAPDIT_VAE_E_CONV_IN_W], wt[MAPDIT_VAE_E_CONV_IN_B], nullptr, r.X, MAPDIT_VAE_OUT_F32, H, W, cfg->out_channels, pl.C[0], 3, 0));
+    // down blocks
+    int cin = pl.C[0];
+    const void* const* downs = wt + MAPDIT_VAE_E_NUM_GLOBAL + nres * MAPDIT_VAE_NUM_RESNET;
+    for (int i = 0; i < pl.nb; ++i) {
+        const int cout = pl.C[i];
+        for (int j = 0; j < cfg->layers_per_block; ++j) {
+            VAE_TRY(resnet(H, W, cin, cout));
+            cin = cout;
+        }
+        if (i < pl.nb - 1) {
+            const void* const* d = downs + i * MAPDIT_VAE_NUM_DOWN;
+            VAE_TRY(r.conv_down(r.X, MAPDIT_VAE_IN_F32, d[MAPDIT_VAE_D_W], d[MAPDIT_VAE_D_B], r.Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout));
+            r.swap_xy();
+            H /= 2;
+            W /= 2;
+        }
+    }
+    // mid block
+    VAE_TRY(resnet(H, W, cin, cin));
+    VAE_TRY(r.attention(wt[MAPDIT_VAE_E_ATTN_GN_G], wt[MAPDIT_VAE_E_ATTN_GN_B], wt[MAPDIT_VAE_E_ATTN_QKV_W], wt[MAPDIT_VAE_E_ATTN_QKV_B],
+                        wt[MAPDIT_VAE_E_ATTN_OUT_W], wt[MAPDIT_VAE_E_ATTN_OUT_B], H, W, cin));
+    VAE_TRY(resnet(H, W, cin, cin));
+    // conv_norm_out + SiLU, conv_out, quant_conv, the posterior head
+    VAE_TRY(r.gn(r.X, wt[MAPDIT_VAE_E_NORM_OUT_G], wt[MAPDIT_VAE_E_NORM_OUT_B], 1, H * W, cin));
+    VAE_TRY(r.conv(r.A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_E_CONV_OUT_W], wt[MAPDIT_VAE_E_CONV_OUT_B], nullptr, r.Hb, MAPDIT_VAE_OUT_F32, H, W, cin, L2, 3, 0));
+    VAE_TRY(r.conv(r.Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_E_QUANT_W], wt[MAPDIT_VAE_E_QUANT_B], nullptr, r.Y, MAPDIT_VAE_OUT_F32, H, W, L2, L2, 1, 0));
+    return mapdit_vae_posterior(r.Y, mean, std, nullptr, N, H * W, cfg->latent_channels, stream);
 }

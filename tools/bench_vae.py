@@ -7,6 +7,12 @@ fp16 on the same GPU (what the diffusers package would execute) in a child proce
 search can be slow; if the child does not finish, that is reported and the native numbers stand alone.
 
     python tools/bench_vae.py [--n 16] [--latents 32,16] [--rounds 3] [--torch] [--torch-timeout 300] [--out FILE]
+
+--encode measures the encoder (mapdit_vae_encode) instead: device time per image for N images of each --images size (128, 256), both
+operand formats, from a fp32 NCHW batch and from uint8 through mapdit_vae_prepare_u8, with the FLOP count of the encoder; --torch then
+runs the encoder as plain torch.nn.functional fp16 calls in the child process.
+
+    python tools/bench_vae.py --encode [--n 16] [--images 128,256] [--rounds 3] [--torch] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -43,6 +49,25 @@ def decoder_flops(cfg, h, w):
             px *= 4
             macs += px * 9 * c * c
     macs += px * 9 * cin * cfg["out_channels"]
+    return 2 * macs
+
+
+def encoder_flops(cfg, H, W):
+    """FLOPs (2 per multiply-add) of one encode of an H x W image: every conv / linear and the two attention products."""
+    ch = list(cfg["block_out_channels"])
+    px, lat2 = H * W, 2 * cfg["latent_channels"]
+    res = lambda p, ci, co: p * 9 * ci * co + p * 9 * co * co + (p * ci * co if ci != co else 0)  # noqa: E731
+    macs = px * 9 * cfg["out_channels"] * ch[0]
+    cin = ch[0]
+    for i, c in enumerate(ch):
+        for _ in range(cfg["layers_per_block"]):
+            macs += res(px, cin, c)
+            cin = c
+        if i < len(ch) - 1:
+            px //= 4
+            macs += px * 9 * c * c
+    macs += 2 * res(px, cin, cin) + 4 * px * cin * cin + 2 * px * px * cin
+    macs += px * 9 * cin * lat2 + px * lat2 * lat2
     return 2 * macs
 
 
@@ -84,6 +109,72 @@ def torch_decode_fp16(sd, z, cfg, groups=32):
         if i < nb - 1:
             x = conv(F.interpolate(x, scale_factor=2.0, mode="nearest"), f"decoder.up_blocks.{i}.upsamplers.0.conv", 1)
     return conv(F.silu(gn(x, "decoder.conv_norm_out")), "decoder.conv_out", 1)
+
+
+def torch_encode_fp16(sd, x, cfg, groups=32):
+    """The encoder as plain torch.nn.functional calls on fp16 tensors (NCHW, like the diffusers modules); returns the moments."""
+    A = "encoder.mid_block.attentions.0."
+    conv = lambda t, n, p: F.conv2d(t, sd[n + ".weight"], sd[n + ".bias"], padding=p)  # noqa: E731
+    gn = lambda t, n: F.group_norm(t, groups, sd[n + ".weight"], sd[n + ".bias"], 1e-6)  # noqa: E731
+
+    def resnet(t, p):
+        h = conv(F.silu(gn(t, p + ".norm1")), p + ".conv1", 1)
+        h = conv(F.silu(gn(h, p + ".norm2")), p + ".conv2", 1)
+        return (conv(t, p + ".conv_shortcut", 0) if p + ".conv_shortcut.weight" in sd else t) + h
+    t = conv(x, "encoder.conv_in", 1)
+    nb = len(cfg["block_out_channels"])
+    for i in range(nb):
+        for j in range(cfg["layers_per_block"]):
+            t = resnet(t, f"encoder.down_blocks.{i}.resnets.{j}")
+        if i < nb - 1:
+            d = f"encoder.down_blocks.{i}.downsamplers.0.conv"
+            t = F.conv2d(F.pad(t, (0, 1, 0, 1)), sd[d + ".weight"], sd[d + ".bias"], stride=2)
+    t = resnet(t, "encoder.mid_block.resnets.0")
+    n, c, hh, ww = t.shape
+    u = gn(t, A + "group_norm").reshape(n, c, hh * ww).transpose(1, 2)
+    q, k, v = (F.linear(u, sd[A + f"{m}.weight"], sd[A + f"{m}.bias"]) for m in ("to_q", "to_k", "to_v"))
+    o = F.scaled_dot_product_attention(q[:, None], k[:, None], v[:, None])[:, 0]
+    t = t + F.linear(o, sd[A + "to_out.0.weight"], sd[A + "to_out.0.bias"]).transpose(1, 2).reshape(n, c, hh, ww)
+    t = resnet(t, "encoder.mid_block.resnets.1")
+    return conv(conv(F.silu(gn(t, "encoder.conv_norm_out")), "encoder.conv_out", 1), "quant_conv", 0)
+
+
+def run_torch_encode(args):
+    import vae_encoder_reference as E
+    dev = torch.device("cuda")
+    sd = {k: v.to(dev, torch.float16) for k, v in E.init_encoder_state_dict(DEFAULT, seed=1).items()}
+    out = []
+    for s in args.images:
+        x = (torch.rand(args.n, 3, s, s, generator=torch.Generator().manual_seed(3)) * 2 - 1).to(dev, torch.float16)
+        with torch.no_grad():
+            ms = [time_events(lambda: torch_encode_fp16(sd, x, DEFAULT), 2, 3) for _ in range(args.rounds)]
+        line = dict(leg="torch_fp16_encode", image=s, n=args.n, ms_per_image=statistics.median(ms) / args.n,
+                    ms_per_image_range=[min(ms) / args.n, max(ms) / args.n], tflops=encoder_flops(DEFAULT, s, s) * args.n / (statistics.median(ms) * 1e-3) / 1e12)
+        print(json.dumps(line), flush=True)
+        out.append(line)
+    return out
+
+
+def run_native_encode(args):
+    import vae_encoder_reference as E
+    from mapdit_amd.vae import VAEEncoder
+    dev = torch.device("cuda")
+    sd = E.init_encoder_state_dict(DEFAULT, seed=1)
+    out = []
+    for prec in ("f16", "bf16"):
+        enc = VAEEncoder.from_state_dict(sd, dev, precision=prec, max_batch=args.n)
+        for s in args.images:
+            u8 = torch.randint(0, 256, (args.n, s, s, 3), generator=torch.Generator().manual_seed(3), dtype=torch.uint8).to(dev)
+            x = ((u8.float() / 255 - 0.5) / 0.5).permute(0, 3, 1, 2).contiguous()
+            for src, t in (("f32_nchw", x), ("uint8", u8)):
+                ms = [time_events(lambda: enc.encode(t), 2, 3) for _ in range(args.rounds)]
+                line = dict(leg="native_encode", precision=prec, input=src, image=s, n=args.n, ms_per_image=statistics.median(ms) / args.n,
+                            ms_per_image_range=[min(ms) / args.n, max(ms) / args.n], gflop_per_image=encoder_flops(DEFAULT, s, s) / 1e9,
+                            tflops=encoder_flops(DEFAULT, s, s) * args.n / (statistics.median(ms) * 1e-3) / 1e12,
+                            workspace_mib=enc.workspace_bytes(args.n, s, s) / 2 ** 20)
+                print(json.dumps(line), flush=True)
+                out.append(line)
+    return out
 
 
 def run_torch(args):
@@ -145,6 +236,8 @@ def main():
     p.add_argument("--n", type=int, default=16)
     p.add_argument("--latents", type=lambda s: [int(v) for v in s.split(",")], default=[32, 16])
     p.add_argument("--rounds", type=int, default=3)
+    p.add_argument("--encode", action="store_true", help="measure the encoder (images to posterior latents) instead of the decoder")
+    p.add_argument("--images", type=lambda s: [int(v) for v in s.split(",")], default=[128, 256], help="--encode: image sizes")
     p.add_argument("--torch", action="store_true", help="also time the plain-torch fp16 network (child process, own time limit)")
     p.add_argument("--torch-only", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--torch-timeout", type=float, default=300.0)
@@ -152,11 +245,13 @@ def main():
     args = p.parse_args()
     assert torch.cuda.is_available(), "bench_vae.py measures on the GPU; there is no CPU path"
     if args.torch_only:
-        run_torch(args)
+        (run_torch_encode if args.encode else run_torch)(args)
         return
-    lines = run_native(args)
+    lines = (run_native_encode if args.encode else run_native)(args)
     if args.torch:
         cmd = [sys.executable, os.path.abspath(__file__), "--torch-only", "--n", str(args.n), "--latents", ",".join(map(str, args.latents)), "--rounds", str(args.rounds)]
+        if args.encode:
+            cmd += ["--encode", "--images", ",".join(map(str, args.images))]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.torch_timeout)
             got = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
