@@ -943,6 +943,73 @@ int mapdit_vae_stats_accumulate(const float* mean, const float* std, int N, int 
 int mapdit_vae_stats_finish(const double* acc, double count, float* ch_mean, float* ch_std, int L, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Inception / FID (additive within abi 5): the 2048 pool_3 features of the 2015 Inception-v3 as the FID literature uses it (the
+ * layout of the pt_inception-2015-12-05 port: BatchNorm eps 1e-3 folded into the convolutions by the caller, the 3 x 3 average
+ * pools with count_include_pad = False, a 3 x 3 MAX pool in Mixed_7c), and the fp64 sums a Gaussian fit needs.  Activations are
+ * 16-bit NHWC between the layers (bf16; _f16 twins below), accumulation fp32; the resized image and the last block's output are fp32.
+ * PARITY WITH THE HUB WEIGHTS UNPINNED: the network is restated from its public description (tests/inception_reference.py).
+ * ------------------------------------------------------------------------------------------------------------ */
+/* Convolution + bias (+ ReLU when relu != 0) as an implicit GEMM over M = N * Hout * Wout output pixels,
+ *   Hout = (Hin + 2 pad_h - kh) / stride + 1, Wout likewise (pad 0: the "valid" form, the output smaller than the input):
+ *   out[n, y, x, c_off + co] = act(bias[co] + sum_{ky, kx, c} in[n, y * stride + ky - pad_h, x * stride + kx - pad_w, c] * w[co][ky][kx][c])
+ * in: [N, Hin, Win, Cin], 16-bit or fp32 (rounded to the operand format, fp16 saturated at +-65504, while it is read).  w 16-bit, packed
+ * [Cout][kh][kw][Cin]; bias fp32 [Cout].  out: fp32 or 16-bit rows of ld_out channels, of which [c_off, c_off + Cout) are written and
+ * the others never touched: a block's concat costs no copy.  kh, kw in 1..7 (1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1 occur), stride 1 or 2.
+ * 16-bit input with Cin % 16 == 0 and Cout % 16 == 0 runs on the MFMA: K = (ky, kx, c) flattened and staged in 16-channel granules,
+ * so a 64-wide K tile may span taps and its tail past kh * kw * Cin is zero-filled; 128 x 64 output tiles with row and column guards.
+ * Every other case (the first layer: Cin = 3) takes a plain kernel.  The K order of an output element does not depend on its place
+ * in a tile or on N: an image alone and in a batch gives the same bits.  Out-of-image taps are zeros that are never loaded. */
+enum { MAPDIT_INC_IN_16 = 0, MAPDIT_INC_IN_F32 = 1 };
+enum { MAPDIT_INC_OUT_F32 = 0, MAPDIT_INC_OUT_16 = 1 };
+typedef struct {
+    const void* in;
+    int in_kind;
+    const uint16_t* w;
+    const float* bias;
+    void* out;
+    int out_kind;
+    int N, Hin, Win, Cin, Cout, kh, kw, stride, pad_h, pad_w, relu, ld_out, c_off;
+} mapdit_inc_conv_t;
+int mapdit_inc_conv(const mapdit_inc_conv_t* args, void* stream);
+/* The three 3 x 3 pools over [N, H, W, C] (in_kind / out_kind as above), written into channels [c_off, c_off + C) of rows of ld_out:
+ * MAX_S2: stride 2, no padding, output (H - 3) / 2 + 1;  AVG: stride 1, pad 1, the sum of the IN-IMAGE taps divided by their count
+ * (count_include_pad = False: a constant image stays that constant, corners included);  MAX_S1: stride 1, pad 1. */
+enum { MAPDIT_INC_POOL_MAX_S2 = 0, MAPDIT_INC_POOL_AVG = 1, MAPDIT_INC_POOL_MAX_S1 = 2 };
+int mapdit_inc_pool(const void* in, int in_kind, void* out, int out_kind, int N, int H, int W, int C, int mode, int ld_out, int c_off,
+                    void* stream);
+/* [N, HW, C] (in_kind) -> fp32 [N, C]: the mean over the HW pixels, a serial fp32 sum in pixel order. */
+int mapdit_inc_global_avg(const void* in, int in_kind, float* out, int N, int HW, int C, void* stream);
+/* Bilinear resize to size x size, align_corners = False, no antialiasing (F.interpolate's map; the source coordinates are formed
+ * in exact integer arithmetic, the weights are one fp32 division each) -> out fp32 NHWC [N, size, size, C].  _u8: img uint8
+ * [N, H, W, C], every tap mapped v / 255 * 2 - 1 before the blend.  _f32: img fp32 [N, C, H, W], values kept. */
+int mapdit_inc_resize_u8(const uint8_t* img, float* out, int N, int H, int W, int C, int size, void* stream);
+int mapdit_inc_resize_f32(const float* img, float* out, int N, int H, int W, int C, int size, void* stream);
+
+/* The network.  Weight table: MAPDIT_INC_NUM_CONV pairs (w 16-bit in mapdit_inc_conv's packing with the BatchNorm scale folded in,
+ * bias fp32 = the folded shift) in execution order: the stem (Conv2d_1a_3x3, 2a, 2b, 3b_1x1, 4a), then per block its branches as
+ * listed - Mixed_5b/5c/5d: branch1x1, branch5x5_1, _2, branch3x3dbl_1, _2, _3, branch_pool;  Mixed_6a: branch3x3, branch3x3dbl_1, _2,
+ * _3;  Mixed_6b..6e: branch1x1, branch7x7_1, _2, _3, branch7x7dbl_1 .. _5, branch_pool;  Mixed_7a: branch3x3_1, _2, branch7x7x3_1 .. _4;
+ * Mixed_7b/7c: branch1x1, branch3x3_1, _2a, _2b, branch3x3dbl_1, _2, _3a, _3b, branch_pool.  mapdit_inc_layer_shape gives slot
+ * index's Cin, Cout, kh, kw and stride (host only), so a caller can check its table against the plan's. */
+#define MAPDIT_INC_NUM_CONV 94
+typedef struct {
+    int image_size;           /* the square every image is resized to before the first convolution: 299 for FID (75 at the least) */
+} mapdit_inc_config_t;
+enum { MAPDIT_INC_IMG_U8_NHWC = 0, MAPDIT_INC_IMG_F32_NCHW = 1 };
+int mapdit_inc_layer_shape(int index, int* cin, int* cout, int* kh, int* kw, int* stride);
+/* Bytes mapdit_inc_features needs for N images: the fp32 image at image_size, four 16-bit activations of the largest layer
+ * (N * 147 * 147 * 64 elements at 299) and the last block's fp32 output.  0 with a message in mapdit_last_error() when refused. */
+size_t mapdit_inc_workspace_bytes(const mapdit_inc_config_t* cfg, int N);
+/* images: uint8 [N, H, W, 3] (MAPDIT_INC_IMG_U8_NHWC) or fp32 [N, 3, H, W] in [-1, 1] (MAPDIT_INC_IMG_F32_NCHW), H, W >= 8 ->
+ * feat fp32 [N, 2048].  Every launch goes to `stream`; no allocation, no synchronisation, no host read-back. */
+int mapdit_inc_features(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                        int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
+/* sum[d] += sum_n feat[n][d] and outer[i][j] += sum_n feat[n][i] * feat[n][j] in fp64 (feat fp32 [N, D]; sum [D], outer [D, D], zeroed
+ * by the caller before the first batch).  Each output element adds its samples in index order to the value it read: no atomics, no
+ * partial sums, so the sums do not depend on how the samples were cut into batches. */
+int mapdit_inc_stats_accumulate(const float* feat, int N, int D, double* sum, double* outer, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
  * holds fp16 bits instead of bf16 bits.  (mapdit_weightnorm_fwd*_f16: w_bf16 receives fp16; the w_split3 image stays a bf16
  * split - the fp32-accurate conditioning GEMMs run on bf16 terms in every engine.)
@@ -1016,6 +1083,12 @@ int mapdit_vae_decode_f16(const mapdit_vae_config_t* cfg, const void* const* wei
 int mapdit_vae_conv_down_f16(const mapdit_vae_conv_t* args, int Hin, int Win, void* stream);
 int mapdit_vae_encode_f16(const mapdit_vae_config_t* cfg, const void* const* weights_host, const float* x, int x_kind, float* mean, float* std,
                           int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+int mapdit_inc_conv_f16(const mapdit_inc_conv_t* args, void* stream);
+int mapdit_inc_pool_f16(const void* in, int in_kind, void* out, int out_kind, int N, int H, int W, int C, int mode, int ld_out, int c_off,
+                        void* stream);
+int mapdit_inc_global_avg_f16(const void* in, int in_kind, float* out, int N, int HW, int C, void* stream);
+int mapdit_inc_features_f16(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                            int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

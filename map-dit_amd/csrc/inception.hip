@@ -1,0 +1,669 @@
+// FID's feature network (the 2015 Inception-v3 in the layout of the pt_inception-2015-12-05 port, BatchNorm folded into the
+// convolutions) and the fp64 feature statistics (mapdit.h, "Inception / FID").  Built once per 16-bit operand format (csrc/Makefile).
+// Activations are 16-bit NHWC between the layers (a convolution rounds its input to the operand format anyway; max pooling commutes
+// with that rounding, the average pool rounds once more); the image at 299 x 299 and the last block's output are fp32.
+//
+// Convolution.  out[m][co] = sum_K A[m][K] * w[co][K] with m = (n, y, x) of the OUTPUT flattened and K = (ky, kx, c) flattened to
+// Ktot = kh * kw * Cin: the weight is a plain row-major [Cout][Ktot] B operand, the A operand is gathered.  Cin is a multiple of 16 and
+// of nothing larger (48, 80, 288 ...), so K is staged in GRANULES of 16 channels: a granule lies inside one tap (one bounds decision,
+// two 16-byte loads), a 64-wide K tile is four granules that may belong to different taps, and the granules of the last tile past
+// Ktot are zeros on both operands.  A workgroup (4 waves) owns 128 output pixels x 64 output channels, each wave 32 x 64 (2 x 4 tiles of
+// v_mfma_f32_16x16x32); rows past M and weight rows past Cout (a multiple of 16, not of 64) stage zeros without forming an address,
+// and the epilogue skips them.  A tile of 128 consecutive m straddles image rows and samples: each staged row derives (n, y, x) from
+// its own m.  The K order of an output element is the tile order and the MFMA's own: it does not depend on where the pixel falls in a
+// tile or on N, so an image alone and in a batch gives the same bits.
+#include "common.h"
+
+MD_NS_OPEN
+
+// fp32 -> operand format; fp16 saturates at its largest finite value instead of becoming inf (NaN stays NaN)
+__device__ __forceinline__ float inc_sat(float v) {
+#if MAPDIT_DT == 1
+    v = v > 65504.f ? 65504.f : v;
+    v = v < -65504.f ? -65504.f : v;
+#endif
+    return v;
+}
+__device__ __forceinline__ bf16_t inc_cvt(float v) { return cvt16(inc_sat(v)); }
+
+struct IncConvP {
+    const void* in;
+    const bf16_t* w;
+    const float* bias;
+    void* out;
+    int Hin, Win, Cin, Cout, kh, kw, st, ph, pw, Ho, Wo, ld, coff, relu, Ktot;
+    long M;
+};
+
+constexpr int IBM = 128, IBN = 64, IBK = 64, ILD = IBK + 8;      // LDS rows of 144 B: 16-byte aligned, consecutive rows 4 banks apart
+
+template <int OUT16> __global__ __launch_bounds__(256) void inc_conv_mfma_kernel(const IncConvP p) {
+    __shared__ __attribute__((aligned(16))) bf16_t As[2][IBM * ILD];
+    __shared__ __attribute__((aligned(16))) bf16_t Bs[2][IBN * ILD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, q = lane >> 4;
+    const long m0 = (long)blockIdx.x * IBM;
+    const int co0 = blockIdx.y * IBN, wr0 = wave * 32;
+    const int Hin = p.Hin, Win = p.Win, Cin = p.Cin, kw = p.kw, Ktot = p.Ktot;
+    const int nk = (Ktot + IBK - 1) / IBK;
+
+    // staging role: rows srow and srow + 64 of the A tile, row srow of the B tile, the granule at kq of every K tile
+    const int srow = tid >> 2, kq = (tid & 3) * 16;
+    int pn[2], py[2], px[2];
+    bool pv[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const long m = m0 + srow + 64 * t;
+        pv[t] = m < p.M;
+        const long mm = pv[t] ? m : 0;
+        const int hw = p.Ho * p.Wo;
+        pn[t] = (int)(mm / hw);
+        const int rem = (int)(mm % hw);
+        py[t] = (rem / p.Wo) * p.st - p.ph;               // the input row / column of tap (0, 0)
+        px[t] = (rem % p.Wo) * p.st - p.pw;
+    }
+    const bool bv = co0 + srow < p.Cout;
+    const bf16_t* wrow = p.w + (size_t)(bv ? co0 + srow : 0) * Ktot;
+
+    uint4 ra[2][2], rb[2];
+    auto fetch = [&](int kt) {
+        const int k0 = kt * IBK + kq;
+        const bool kv = k0 < Ktot;                         // (Ktot % 16 == 0: a granule is inside K or past it, never across)
+        const int tap = kv ? k0 / Cin : 0, c0 = kv ? k0 - tap * Cin : 0;
+        const int ky = tap / kw, kx = tap - ky * kw;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int yy = py[t] + ky, xx = px[t] + kx;
+            ra[t][0] = uint4{0u, 0u, 0u, 0u};
+            ra[t][1] = uint4{0u, 0u, 0u, 0u};
+            if (kv && pv[t] && yy >= 0 && yy < Hin && xx >= 0 && xx < Win) {
+                const uint4* s = (const uint4*)((const bf16_t*)p.in + (((size_t)pn[t] * Hin + yy) * Win + xx) * Cin + c0);
+                ra[t][0] = s[0];
+                ra[t][1] = s[1];
+            }
+        }
+        rb[0] = uint4{0u, 0u, 0u, 0u};
+        rb[1] = uint4{0u, 0u, 0u, 0u};
+        if (kv && bv) {
+            const uint4* s = (const uint4*)(wrow + k0);
+            rb[0] = s[0];
+            rb[1] = s[1];
+        }
+    };
+    auto stash = [&](int buf) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            uint4* d = (uint4*)(&As[buf][(srow + 64 * t) * ILD + kq]);
+            d[0] = ra[t][0];
+            d[1] = ra[t][1];
+        }
+        uint4* d = (uint4*)(&Bs[buf][srow * ILD + kq]);
+        d[0] = rb[0];
+        d[1] = rb[1];
+    };
+
+    f32x4_t acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    fetch(0);
+    stash(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) fetch(kt + 1);
+#pragma unroll
+        for (int ks = 0; ks < IBK / 32; ++ks) {
+            bf16x8_t a[2], b[4];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a[i] = *(const bf16x8_t*)(&As[buf][(wr0 + i * 16 + r) * ILD + ks * 32 + q * 8]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = *(const bf16x8_t*)(&Bs[buf][(j * 16 + r) * ILD + ks * 32 + q * 8]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(a[i], b[j], acc[i][j]);
+        }
+        // the other buffer was last read by the compute of K tile kt - 1, which every wave left before the previous barrier
+        if (kt + 1 < nk) stash(buf ^ 1);
+        __syncthreads();
+    }
+
+    // accumulator element e of a lane: pixel row 4 q + e of the 16 x 16 tile, output channel r
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int co = co0 + j * 16 + r;
+        if (co >= p.Cout) continue;
+        const float bvv = p.bias[co];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long m = m0 + wr0 + i * 16 + q * 4 + e;
+                if (m >= p.M) continue;
+                const size_t o = (size_t)m * p.ld + p.coff + co;
+                float v = acc[i][j][e] + bvv;
+                if (p.relu) v = v > 0.f ? v : 0.f;
+                if constexpr (OUT16) ((bf16_t*)p.out)[o] = inc_cvt(v);
+                else ((float*)p.out)[o] = v;
+            }
+    }
+}
+
+// Every other shape (the first layer: Cin = 3, K = 27, fp32 input) and every misaligned operand: one thread per output element, the
+// same operand rounding, a serial fp32 sum in (ky, kx, c) order.
+__global__ __launch_bounds__(256) void inc_conv_plain_kernel(const IncConvP p, int in_f32, int out16) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.M * p.Cout) return;
+    const int co = (int)(idx % p.Cout);
+    const long m = idx / p.Cout;
+    const int hw = p.Ho * p.Wo;
+    const int n = (int)(m / hw), rem = (int)(m % hw), y = rem / p.Wo, x = rem % p.Wo;
+    const bf16_t* wr = p.w + (size_t)co * p.Ktot;
+    float acc = 0.f;
+    for (int ky = 0; ky < p.kh; ++ky) {
+        const int yy = y * p.st + ky - p.ph;
+        if (yy < 0 || yy >= p.Hin) continue;
+        for (int kx = 0; kx < p.kw; ++kx) {
+            const int xx = x * p.st + kx - p.pw;
+            if (xx < 0 || xx >= p.Win) continue;
+            const bf16_t* wt = wr + (size_t)(ky * p.kw + kx) * p.Cin;
+            const size_t e0 = (((size_t)n * p.Hin + yy) * p.Win + xx) * p.Cin;
+            if (in_f32) {
+                const float* ip = (const float*)p.in + e0;
+                for (int c = 0; c < p.Cin; ++c) acc = fmaf(up16(inc_cvt(ip[c])), up16(wt[c]), acc);
+            } else {
+                const bf16_t* ip = (const bf16_t*)p.in + e0;
+                for (int c = 0; c < p.Cin; ++c) acc = fmaf(up16(ip[c]), up16(wt[c]), acc);
+            }
+        }
+    }
+    float v = acc + p.bias[co];
+    if (p.relu) v = v > 0.f ? v : 0.f;
+    const size_t o = (size_t)m * p.ld + p.coff + co;
+    if (out16) ((bf16_t*)p.out)[o] = inc_cvt(v);
+    else ((float*)p.out)[o] = v;
+}
+
+// ---- pooling ----------------------------------------------------------------------------------------------------------------------
+// The three 3 x 3 forms, one thread per output element, taps in (ky, kx) order over the in-image taps only: the stride-2 maximum
+// without padding (every tap is inside), the stride-1 pad-1 average that divides by the COUNT OF IN-IMAGE TAPS (count_include_pad =
+// False: 4 at a corner, 6 on an edge, 9 inside; IEEE division), and the stride-1 pad-1 maximum (padding never wins).  A NaN propagates.
+__device__ __forceinline__ float inc_load(const void* in, int in_f32, size_t e) { return in_f32 ? ((const float*)in)[e] : up16(((const bf16_t*)in)[e]); }
+
+__global__ __launch_bounds__(256) void inc_pool_kernel(const void* __restrict__ in, int in_f32, void* __restrict__ out, int out16, long total,
+                                                       int H, int W, int C, int Ho, int Wo, int mode, int ld, int coff) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx % C);
+    const long m = idx / C;
+    const int hw = Ho * Wo;
+    const int n = (int)(m / hw), rem = (int)(m % hw), y = rem / Wo, x = rem % Wo;
+    const int st = mode == MAPDIT_INC_POOL_MAX_S2 ? 2 : 1, pad = mode == MAPDIT_INC_POOL_MAX_S2 ? 0 : 1;
+    const bool avg = mode == MAPDIT_INC_POOL_AVG;
+    float a = avg ? 0.f : -INFINITY;
+    int cnt = 0;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int yy = y * st + ky - pad;
+        if (yy < 0 || yy >= H) continue;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int xx = x * st + kx - pad;
+            if (xx < 0 || xx >= W) continue;
+            const float v = inc_load(in, in_f32, (((size_t)n * H + yy) * W + xx) * C + c);
+            if (avg) a += v;
+            else a = (v > a || v != v) ? v : a;
+            ++cnt;
+        }
+    }
+    if (avg) a = a / (float)cnt;
+    const size_t o = (size_t)m * ld + coff + c;
+    if (out16) ((bf16_t*)out)[o] = inc_cvt(a);
+    else ((float*)out)[o] = a;
+}
+
+// [N, HW, C] -> fp32 [N, C]: one thread per (n, c), a serial fp32 sum in pixel order, IEEE division by HW
+__global__ __launch_bounds__(256) void inc_global_avg_kernel(const void* __restrict__ in, int in_f32, float* __restrict__ out, long total, int HW, int C) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx % C);
+    const long n = idx / C;
+    float a = 0.f;
+    for (int i = 0; i < HW; ++i) a += inc_load(in, in_f32, ((size_t)n * HW + i) * C + c);
+    out[idx] = a / (float)HW;
+}
+
+#if MAPDIT_DT == 0
+// ---- fp32 / byte / fp64 kernels: built once (no _f16 twin) -------------------------------------------------------------------------
+// Bilinear resize to S x S with align_corners = False and no antialiasing, F.interpolate's map: source coordinate
+// (dst + 0.5) * in / out - 0.5 clamped at 0; i0 = floor, i1 = i0 + 1 clamped to the last pixel, weights (1 - l, l); the row blend of
+// the two column blends.  u8 != 0: img is uint8 [N, H, W, C] and each tap is taken to [-1, 1] first, v / 255 * 2 - 1 (the blend's
+// weights sum to 1, so this is the blend of the bytes mapped afterwards, with the fp32 rounding on values <= 1 instead of <= 255);
+// else img is fp32 [N, C, H, W] already in [-1, 1].  out fp32 NHWC [N, S, S, C].
+__global__ __launch_bounds__(256) void inc_resize_kernel(const void* __restrict__ img, int u8, float* __restrict__ out, long total, int H, int W,
+                                                         int C, int S) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx % C);
+    const long pix = idx / C;
+    const int x = (int)(pix % S);
+    const long row = pix / S;
+    const int y = (int)(row % S);
+    const long n = row / S;
+    // source coordinate (2 d + 1) in / (2 S) - 1/2 = ((2 d + 1) in - S) / (2 S): the numerator is an exact integer, so the floor and the
+    // remainder are exact and the weight is one fp32 division of two small integers
+    long ny = (long)(2 * y + 1) * H - S, nx = (long)(2 * x + 1) * W - S;
+    ny = ny < 0 ? 0 : ny;
+    nx = nx < 0 ? 0 : nx;
+    int y0 = (int)(ny / (2 * S)), x0 = (int)(nx / (2 * S));
+    float ly = (float)(ny - (long)y0 * 2 * S) / (float)(2 * S), lx = (float)(nx - (long)x0 * 2 * S) / (float)(2 * S);
+    if (y0 >= H - 1) {
+        y0 = H - 1;
+        ly = 0.f;
+    }
+    if (x0 >= W - 1) {
+        x0 = W - 1;
+        lx = 0.f;
+    }
+    const int y1 = y0 < H - 1 ? y0 + 1 : y0, x1 = x0 < W - 1 ? x0 + 1 : x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    float v00, v01, v10, v11;
+    if (u8) {
+        const uint8_t* b = (const uint8_t*)img + (size_t)n * H * W * C + c;
+        v00 = (float)b[((size_t)y0 * W + x0) * C] / 255.f * 2.f - 1.f;
+        v01 = (float)b[((size_t)y0 * W + x1) * C] / 255.f * 2.f - 1.f;
+        v10 = (float)b[((size_t)y1 * W + x0) * C] / 255.f * 2.f - 1.f;
+        v11 = (float)b[((size_t)y1 * W + x1) * C] / 255.f * 2.f - 1.f;
+    } else {
+        const float* b = (const float*)img + ((size_t)n * C + c) * H * W;
+        v00 = b[(size_t)y0 * W + x0];
+        v01 = b[(size_t)y0 * W + x1];
+        v10 = b[(size_t)y1 * W + x0];
+        v11 = b[(size_t)y1 * W + x1];
+    }
+    out[idx] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
+// Feature statistics in fp64: sum[d] += sum_n x[n][d], outer[i][j] += sum_n x[n][i] * x[n][j].  One thread per output element walks
+// the samples in index order and adds to the value it read: no atomics, no partial sums - the result is a function of the sequence
+// of samples, not of the batches it arrives in.  (The product of two fp32 values is exact in fp64.)
+__global__ __launch_bounds__(256) void inc_stats_outer_kernel(const float* __restrict__ x, int N, int D, double* __restrict__ outer) {
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63), i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (i >= D || j >= D) return;
+    double a = outer[(size_t)i * D + j];
+    for (int n = 0; n < N; ++n) a += (double)x[(size_t)n * D + i] * (double)x[(size_t)n * D + j];
+    outer[(size_t)i * D + j] = a;
+}
+
+__global__ __launch_bounds__(256) void inc_stats_sum_kernel(const float* __restrict__ x, int N, int D, double* __restrict__ sum) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= D) return;
+    double a = sum[d];
+    for (int n = 0; n < N; ++n) a += (double)x[(size_t)n * D + d];
+    sum[d] = a;
+}
+#endif
+
+MD_NS_CLOSE
+
+#define INC_TRY(call)                     \
+    do {                                  \
+        const int rc_ = (call);           \
+        if (rc_ != MAPDIT_OK) return rc_; \
+    } while (0)
+
+// ---- entry points -----------------------------------------------------------------------------------------------------------------
+extern "C" int MD_SYM(inc_conv)(const mapdit_inc_conv_t* a, void* stream) {
+    MD_CHECK(a && a->in && a->w && a->bias && a->out, "inc_conv: null argument");
+    MD_CHECK(a->N > 0 && a->Hin > 0 && a->Win > 0 && a->Cin > 0 && a->Cout > 0, "inc_conv: empty shape N=%d Hin=%d Win=%d Cin=%d Cout=%d", a->N,
+             a->Hin, a->Win, a->Cin, a->Cout);
+    MD_CHECK(a->kh >= 1 && a->kh <= 7 && a->kw >= 1 && a->kw <= 7, "inc_conv: kernel of %d x %d (1..7 each way)", a->kh, a->kw);
+    MD_CHECK(a->stride == 1 || a->stride == 2, "inc_conv: stride=%d (1 or 2)", a->stride);
+    MD_CHECK(a->pad_h >= 0 && a->pad_h < a->kh && a->pad_w >= 0 && a->pad_w < a->kw, "inc_conv: pad (%d, %d) for a %d x %d kernel", a->pad_h, a->pad_w,
+             a->kh, a->kw);
+    MD_CHECK(a->in_kind == MAPDIT_INC_IN_16 || a->in_kind == MAPDIT_INC_IN_F32, "inc_conv: bad in_kind %d", a->in_kind);
+    MD_CHECK(a->out_kind == MAPDIT_INC_OUT_F32 || a->out_kind == MAPDIT_INC_OUT_16, "inc_conv: bad out_kind %d", a->out_kind);
+    MD_CHECK(a->Hin + 2 * a->pad_h >= a->kh && a->Win + 2 * a->pad_w >= a->kw, "inc_conv: a %d x %d kernel does not fit a %d x %d input", a->kh, a->kw,
+             a->Hin, a->Win);
+    MD_CHECK(a->c_off >= 0 && a->ld_out >= a->c_off + a->Cout, "inc_conv: channels [%d, %d) do not fit rows of ld_out=%d", a->c_off, a->c_off + a->Cout,
+             a->ld_out);
+    const int Ho = (a->Hin + 2 * a->pad_h - a->kh) / a->stride + 1, Wo = (a->Win + 2 * a->pad_w - a->kw) / a->stride + 1;
+    const long M = (long)a->N * Ho * Wo;
+    MD_CHECK(M < (1L << 31) && (long)a->N * a->Hin * a->Win < (1L << 31) && M * a->ld_out < (1L << 40), "inc_conv: %ld output pixels are too many", M);
+    const long Ktot = (long)a->kh * a->kw * a->Cin;
+    MD_CHECK(Ktot < (1L << 24), "inc_conv: K = %ld is too long", Ktot);
+    hipStream_t st = (hipStream_t)stream;
+    const IncConvP p{a->in, (const bf16_t*)a->w, a->bias, a->out, a->Hin, a->Win, a->Cin, a->Cout, a->kh, a->kw, a->stride, a->pad_h, a->pad_w,
+                     Ho, Wo, a->ld_out, a->c_off, a->relu ? 1 : 0, (int)Ktot, M};
+    const bool aligned = !(((uintptr_t)a->in | (uintptr_t)a->w) & 15);
+    if (a->in_kind == MAPDIT_INC_IN_16 && a->Cin % 16 == 0 && a->Cout % 16 == 0 && aligned) {
+        const dim3 grid((unsigned)cdiv(M, IBM), (unsigned)cdiv(a->Cout, IBN));
+        if (a->out_kind == MAPDIT_INC_OUT_16) inc_conv_mfma_kernel<1><<<grid, 256, 0, st>>>(p);
+        else inc_conv_mfma_kernel<0><<<grid, 256, 0, st>>>(p);
+    } else {
+        MD_CHECK(M * a->Cout < (1L << 38), "inc_conv: %ld x %d outputs are too many for the plain kernel", M, a->Cout);
+        inc_conv_plain_kernel<<<cdiv(M * a->Cout, 256), 256, 0, st>>>(p, a->in_kind == MAPDIT_INC_IN_F32, a->out_kind == MAPDIT_INC_OUT_16);
+    }
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(inc_pool)(const void* in, int in_kind, void* out, int out_kind, int N, int H, int W, int C, int mode, int ld_out, int c_off,
+                                void* stream) {
+    MD_CHECK(in && out, "inc_pool: null argument");
+    MD_CHECK(N > 0 && H > 0 && W > 0 && C > 0, "inc_pool: N=%d, H=%d, W=%d, C=%d must be positive", N, H, W, C);
+    MD_CHECK(mode == MAPDIT_INC_POOL_MAX_S2 || mode == MAPDIT_INC_POOL_AVG || mode == MAPDIT_INC_POOL_MAX_S1, "inc_pool: bad mode %d", mode);
+    MD_CHECK(in_kind == MAPDIT_INC_IN_16 || in_kind == MAPDIT_INC_IN_F32, "inc_pool: bad in_kind %d", in_kind);
+    MD_CHECK(out_kind == MAPDIT_INC_OUT_F32 || out_kind == MAPDIT_INC_OUT_16, "inc_pool: bad out_kind %d", out_kind);
+    MD_CHECK(mode != MAPDIT_INC_POOL_MAX_S2 || (H >= 3 && W >= 3), "inc_pool: a %d x %d image is smaller than the 3 x 3 window", H, W);
+    MD_CHECK(c_off >= 0 && ld_out >= c_off + C, "inc_pool: channels [%d, %d) do not fit rows of ld_out=%d", c_off, c_off + C, ld_out);
+    const int Ho = mode == MAPDIT_INC_POOL_MAX_S2 ? (H - 3) / 2 + 1 : H, Wo = mode == MAPDIT_INC_POOL_MAX_S2 ? (W - 3) / 2 + 1 : W;
+    const long total = (long)N * Ho * Wo * C;
+    MD_CHECK((long)N * H * W < (1L << 31) && total < (1L << 38) && (long)N * Ho * Wo * ld_out < (1L << 40), "inc_pool: %ld elements are too many", total);
+    inc_pool_kernel<<<cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(in, in_kind == MAPDIT_INC_IN_F32, out, out_kind == MAPDIT_INC_OUT_16, total, H, W,
+                                                                      C, Ho, Wo, mode, ld_out, c_off);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(inc_global_avg)(const void* in, int in_kind, float* out, int N, int HW, int C, void* stream) {
+    MD_CHECK(in && out, "inc_global_avg: null argument");
+    MD_CHECK(N > 0 && HW > 0 && C > 0, "inc_global_avg: N=%d, HW=%d, C=%d must be positive", N, HW, C);
+    MD_CHECK(in_kind == MAPDIT_INC_IN_16 || in_kind == MAPDIT_INC_IN_F32, "inc_global_avg: bad in_kind %d", in_kind);
+    const long total = (long)N * C;
+    MD_CHECK(total < (1L << 31) && total * HW < (1L << 40), "inc_global_avg: %ld x %d elements are too many", total, HW);
+    inc_global_avg_kernel<<<cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(in, in_kind == MAPDIT_INC_IN_F32, out, total, HW, C);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+#if MAPDIT_DT == 0
+static int inc_resize_launch(const char* who, const void* img, int u8, float* out, int N, int H, int W, int C, int S, void* stream) {
+    MD_CHECK(img && out, "%s: null argument", who);
+    MD_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && S > 0, "%s: N=%d, H=%d, W=%d, C=%d, size=%d must be positive", who, N, H, W, C, S);
+    MD_CHECK(H < (1 << 24) && W < (1 << 24) && S < (1 << 22), "%s: H=%d, W=%d (below 2^24) or size=%d (below 2^22) is too large", who, H, W, S);
+    const long total = (long)N * S * S * C;
+    MD_CHECK(total < (1L << 38) && (long)N * H * W * C < (1L << 40), "%s: %ld elements are too many for one call", who, total);
+    inc_resize_kernel<<<cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(img, u8, out, total, H, W, C, S);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+extern "C" int mapdit_inc_resize_u8(const uint8_t* img, float* out, int N, int H, int W, int C, int size, void* stream) {
+    return inc_resize_launch("inc_resize_u8", img, 1, out, N, H, W, C, size, stream);
+}
+
+extern "C" int mapdit_inc_resize_f32(const float* img, float* out, int N, int H, int W, int C, int size, void* stream) {
+    return inc_resize_launch("inc_resize_f32", img, 0, out, N, H, W, C, size, stream);
+}
+
+extern "C" int mapdit_inc_stats_accumulate(const float* feat, int N, int D, double* sum, double* outer, void* stream) {
+    MD_CHECK(feat && sum && outer, "inc_stats_accumulate: null argument");
+    MD_CHECK(N > 0 && D > 0 && D <= 65536, "inc_stats_accumulate: N=%d and D=%d must be positive (D <= 65536)", N, D);
+    MD_CHECK(!(((uintptr_t)sum | (uintptr_t)outer) & 7), "inc_stats_accumulate: sum and outer must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    inc_stats_sum_kernel<<<cdiv(D, 256), 256, 0, st>>>(feat, N, D, sum);
+    const dim3 grid((unsigned)cdiv(D, 64), (unsigned)cdiv(D, 4));
+    inc_stats_outer_kernel<<<grid, 256, 0, st>>>(feat, N, D, outer);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+#endif
+
+// ---- the network -------------------------------------------------------------------------------------------------------------------
+// One walk serves the three uses: `shape` (no launches; records every convolution's shape and the largest activation), the
+// workspace query and the run.  Buffers: X the block's input, Y its concatenated output (each branch's last convolution, and the
+// max-pool branches of Mixed_6a / 7a, write their channel slice of it), T1 / T2 the branches' temporaries; all 16-bit NHWC of maxE
+// elements.  IMG: the fp32 image at size x size; FIN: the last block's fp32 output.
+namespace {
+inline size_t inc_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct IncLayer {
+    int cin, cout, kh, kw, st;
+};
+
+struct IncWalk {
+    bool dry;
+    int N;
+    void* stream;
+    const void* const* wt;
+    uint16_t *X, *Y, *T1, *T2;
+    float *IMG, *FIN;
+    int li;                      // the next convolution's number in execution order
+    size_t maxE, finE;
+    IncLayer layers[MAPDIT_INC_NUM_CONV];
+
+    void note(int H, int W, int C) {
+        const size_t e = (size_t)N * H * W * C;
+        maxE = e > maxE ? e : maxE;
+    }
+    int conv(const void* in, int in_kind, int H, int W, int cin, int cout, int kh, int kw, int st, int ph, int pw, void* out, int out_kind, int ld,
+             int coff, int* Ho, int* Wo) {
+        MD_CHECK(li < MAPDIT_INC_NUM_CONV, "inception: more than %d convolutions", MAPDIT_INC_NUM_CONV);
+        MD_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "inception: the image size is too small: convolution %d (%d x %d) meets a %d x %d input", li, kh,
+                 kw, H, W);
+        const int ho = (H + 2 * ph - kh) / st + 1, wo = (W + 2 * pw - kw) / st + 1;
+        layers[li] = IncLayer{cin, cout, kh, kw, st};
+        const int i = li++;
+        if (Ho) *Ho = ho;
+        if (Wo) *Wo = wo;
+        if (out_kind == MAPDIT_INC_OUT_16) note(ho, wo, ld);
+        else finE = (size_t)N * ho * wo * ld;
+        if (dry) return MAPDIT_OK;
+        const mapdit_inc_conv_t a{in, in_kind, (const uint16_t*)wt[2 * i], (const float*)wt[2 * i + 1], out, out_kind, N, H, W, cin, cout, kh, kw, st, ph,
+                                  pw, 1, ld, coff};
+        return MD_SYM(inc_conv)(&a, stream);
+    }
+    // 16-bit [N, H, W, cin] -> 16-bit, the common case
+    int c16(const uint16_t* in, int H, int W, int cin, int cout, int kh, int kw, int st, int ph, int pw, uint16_t* out, int ld, int coff) {
+        return conv(in, MAPDIT_INC_IN_16, H, W, cin, cout, kh, kw, st, ph, pw, out, MAPDIT_INC_OUT_16, ld, coff, nullptr, nullptr);
+    }
+    int pool(const uint16_t* in, int H, int W, int C, int mode, uint16_t* out, int ld, int coff) {
+        MD_CHECK(mode != MAPDIT_INC_POOL_MAX_S2 || (H >= 3 && W >= 3), "inception: the image size is too small: a stride-2 pool meets a %d x %d input", H, W);
+        const int ho = mode == MAPDIT_INC_POOL_MAX_S2 ? (H - 3) / 2 + 1 : H, wo = mode == MAPDIT_INC_POOL_MAX_S2 ? (W - 3) / 2 + 1 : W;
+        note(ho, wo, ld);
+        if (dry) return MAPDIT_OK;
+        return MD_SYM(inc_pool)(in, MAPDIT_INC_IN_16, out, MAPDIT_INC_OUT_16, N, H, W, C, mode, ld, coff, stream);
+    }
+    void swap_xy() {
+        uint16_t* t = X;
+        X = Y;
+        Y = t;
+    }
+
+    // Mixed_5b / 5c / 5d
+    int block_a(int H, int W, int cin, int pw_) {
+        const int ld = 224 + pw_;
+        INC_TRY(c16(X, H, W, cin, 64, 1, 1, 1, 0, 0, Y, ld, 0));
+        INC_TRY(c16(X, H, W, cin, 48, 1, 1, 1, 0, 0, T1, 48, 0));
+        INC_TRY(c16(T1, H, W, 48, 64, 5, 5, 1, 2, 2, Y, ld, 64));
+        INC_TRY(c16(X, H, W, cin, 64, 1, 1, 1, 0, 0, T1, 64, 0));
+        INC_TRY(c16(T1, H, W, 64, 96, 3, 3, 1, 1, 1, T2, 96, 0));
+        INC_TRY(c16(T2, H, W, 96, 96, 3, 3, 1, 1, 1, Y, ld, 128));
+        INC_TRY(pool(X, H, W, cin, MAPDIT_INC_POOL_AVG, T1, cin, 0));
+        INC_TRY(c16(T1, H, W, cin, pw_, 1, 1, 1, 0, 0, Y, ld, 224));
+        swap_xy();
+        return MAPDIT_OK;
+    }
+    // Mixed_6a: 288 -> 768, the size halves
+    int block_b(int* H, int* W) {
+        const int h = *H, w = *W, cin = 288, ld = 768;
+        MD_CHECK(h >= 3 && w >= 3, "inception: the image size is too small: Mixed_6a meets a %d x %d input", h, w);
+        INC_TRY(c16(X, h, w, cin, 384, 3, 3, 2, 0, 0, Y, ld, 0));
+        INC_TRY(c16(X, h, w, cin, 64, 1, 1, 1, 0, 0, T1, 64, 0));
+        INC_TRY(c16(T1, h, w, 64, 96, 3, 3, 1, 1, 1, T2, 96, 0));
+        INC_TRY(c16(T2, h, w, 96, 96, 3, 3, 2, 0, 0, Y, ld, 384));
+        INC_TRY(pool(X, h, w, cin, MAPDIT_INC_POOL_MAX_S2, Y, ld, 480));
+        *H = (h - 3) / 2 + 1;
+        *W = (w - 3) / 2 + 1;
+        swap_xy();
+        return MAPDIT_OK;
+    }
+    // Mixed_6b .. 6e
+    int block_c(int H, int W, int c7) {
+        const int cin = 768, ld = 768;
+        INC_TRY(c16(X, H, W, cin, 192, 1, 1, 1, 0, 0, Y, ld, 0));
+        INC_TRY(c16(X, H, W, cin, c7, 1, 1, 1, 0, 0, T1, c7, 0));
+        INC_TRY(c16(T1, H, W, c7, c7, 1, 7, 1, 0, 3, T2, c7, 0));
+        INC_TRY(c16(T2, H, W, c7, 192, 7, 1, 1, 3, 0, Y, ld, 192));
+        INC_TRY(c16(X, H, W, cin, c7, 1, 1, 1, 0, 0, T1, c7, 0));
+        INC_TRY(c16(T1, H, W, c7, c7, 7, 1, 1, 3, 0, T2, c7, 0));
+        INC_TRY(c16(T2, H, W, c7, c7, 1, 7, 1, 0, 3, T1, c7, 0));
+        INC_TRY(c16(T1, H, W, c7, c7, 7, 1, 1, 3, 0, T2, c7, 0));
+        INC_TRY(c16(T2, H, W, c7, 192, 1, 7, 1, 0, 3, Y, ld, 384));
+        INC_TRY(pool(X, H, W, cin, MAPDIT_INC_POOL_AVG, T1, cin, 0));
+        INC_TRY(c16(T1, H, W, cin, 192, 1, 1, 1, 0, 0, Y, ld, 576));
+        swap_xy();
+        return MAPDIT_OK;
+    }
+    // Mixed_7a: 768 -> 1280, the size halves
+    int block_d(int* H, int* W) {
+        const int h = *H, w = *W, cin = 768, ld = 1280;
+        MD_CHECK(h >= 3 && w >= 3, "inception: the image size is too small: Mixed_7a meets a %d x %d input", h, w);
+        INC_TRY(c16(X, h, w, cin, 192, 1, 1, 1, 0, 0, T1, 192, 0));
+        INC_TRY(c16(T1, h, w, 192, 320, 3, 3, 2, 0, 0, Y, ld, 0));
+        INC_TRY(c16(X, h, w, cin, 192, 1, 1, 1, 0, 0, T1, 192, 0));
+        INC_TRY(c16(T1, h, w, 192, 192, 1, 7, 1, 0, 3, T2, 192, 0));
+        INC_TRY(c16(T2, h, w, 192, 192, 7, 1, 1, 3, 0, T1, 192, 0));
+        INC_TRY(c16(T1, h, w, 192, 192, 3, 3, 2, 0, 0, Y, ld, 320));
+        INC_TRY(pool(X, h, w, cin, MAPDIT_INC_POOL_MAX_S2, Y, ld, 512));
+        *H = (h - 3) / 2 + 1;
+        *W = (w - 3) / 2 + 1;
+        swap_xy();
+        return MAPDIT_OK;
+    }
+    // Mixed_7b (average pool, 16-bit output into Y) / Mixed_7c (the port's 3 x 3 max pool, fp32 output into FIN)
+    int block_e(int H, int W, int cin, int pool_mode, bool last) {
+        const int ld = 2048, ok = last ? MAPDIT_INC_OUT_F32 : MAPDIT_INC_OUT_16;
+        void* O = last ? (void*)FIN : (void*)Y;
+        const int k16 = MAPDIT_INC_IN_16;
+        INC_TRY(conv(X, k16, H, W, cin, 320, 1, 1, 1, 0, 0, O, ok, ld, 0, nullptr, nullptr));
+        INC_TRY(c16(X, H, W, cin, 384, 1, 1, 1, 0, 0, T1, 384, 0));
+        INC_TRY(conv(T1, k16, H, W, 384, 384, 1, 3, 1, 0, 1, O, ok, ld, 320, nullptr, nullptr));
+        INC_TRY(conv(T1, k16, H, W, 384, 384, 3, 1, 1, 1, 0, O, ok, ld, 704, nullptr, nullptr));
+        INC_TRY(c16(X, H, W, cin, 448, 1, 1, 1, 0, 0, T1, 448, 0));
+        INC_TRY(c16(T1, H, W, 448, 384, 3, 3, 1, 1, 1, T2, 384, 0));
+        INC_TRY(conv(T2, k16, H, W, 384, 384, 1, 3, 1, 0, 1, O, ok, ld, 1088, nullptr, nullptr));
+        INC_TRY(conv(T2, k16, H, W, 384, 384, 3, 1, 1, 1, 0, O, ok, ld, 1472, nullptr, nullptr));
+        INC_TRY(pool(X, H, W, cin, pool_mode, T1, cin, 0));
+        INC_TRY(conv(T1, k16, H, W, cin, 192, 1, 1, 1, 0, 0, O, ok, ld, 1856, nullptr, nullptr));
+        if (!last) swap_xy();
+        return MAPDIT_OK;
+    }
+
+    // IMG [N, S, S, 3] -> FIN [N, Hf, Wf, 2048]
+    int run(int S, int* Hf, int* Wf) {
+        int H = S, W = S;
+        li = 0;
+        maxE = finE = 0;
+        INC_TRY(conv(IMG, MAPDIT_INC_IN_F32, H, W, 3, 32, 3, 3, 2, 0, 0, X, MAPDIT_INC_OUT_16, 32, 0, &H, &W));        // Conv2d_1a_3x3
+        INC_TRY(conv(X, MAPDIT_INC_IN_16, H, W, 32, 32, 3, 3, 1, 0, 0, Y, MAPDIT_INC_OUT_16, 32, 0, &H, &W));          // Conv2d_2a_3x3
+        INC_TRY(c16(Y, H, W, 32, 64, 3, 3, 1, 1, 1, X, 64, 0));                                                        // Conv2d_2b_3x3
+        INC_TRY(pool(X, H, W, 64, MAPDIT_INC_POOL_MAX_S2, Y, 64, 0));
+        H = (H - 3) / 2 + 1;
+        W = (W - 3) / 2 + 1;
+        INC_TRY(c16(Y, H, W, 64, 80, 1, 1, 1, 0, 0, X, 80, 0));                                                        // Conv2d_3b_1x1
+        INC_TRY(conv(X, MAPDIT_INC_IN_16, H, W, 80, 192, 3, 3, 1, 0, 0, Y, MAPDIT_INC_OUT_16, 192, 0, &H, &W));        // Conv2d_4a_3x3
+        INC_TRY(pool(Y, H, W, 192, MAPDIT_INC_POOL_MAX_S2, X, 192, 0));
+        H = (H - 3) / 2 + 1;
+        W = (W - 3) / 2 + 1;
+        INC_TRY(block_a(H, W, 192, 32));
+        INC_TRY(block_a(H, W, 256, 64));
+        INC_TRY(block_a(H, W, 288, 64));
+        INC_TRY(block_b(&H, &W));
+        INC_TRY(block_c(H, W, 128));
+        INC_TRY(block_c(H, W, 160));
+        INC_TRY(block_c(H, W, 160));
+        INC_TRY(block_c(H, W, 192));
+        INC_TRY(block_d(&H, &W));
+        INC_TRY(block_e(H, W, 1280, MAPDIT_INC_POOL_AVG, false));
+        INC_TRY(block_e(H, W, 2048, MAPDIT_INC_POOL_MAX_S1, true));
+        MD_CHECK(li == MAPDIT_INC_NUM_CONV, "inception: %d convolutions walked, %d declared", li, MAPDIT_INC_NUM_CONV);
+        *Hf = H;
+        *Wf = W;
+        return MAPDIT_OK;
+    }
+};
+
+struct IncPlan {
+    size_t off_img, off_fin, off_x, off_y, off_t1, off_t2, total;
+    int Hf, Wf;
+};
+
+int inc_plan(const mapdit_inc_config_t* cfg, int N, IncWalk* wk, IncPlan* pl) {
+    MD_CHECK(cfg, "inception: null config");
+    MD_CHECK(N > 0, "inception: N=%d must be positive", N);
+    MD_CHECK(cfg->image_size >= 75 && cfg->image_size <= 4096, "inception: image_size=%d (75 .. 4096; FID uses 299)", cfg->image_size);
+    MD_CHECK((long)N * cfg->image_size * cfg->image_size < (1L << 31), "inception: N=%d images of %d x %d are too many pixels for one call", N,
+             cfg->image_size, cfg->image_size);
+    *wk = IncWalk{};
+    wk->dry = true;
+    wk->N = N;
+    INC_TRY(wk->run(cfg->image_size, &pl->Hf, &pl->Wf));
+    size_t o = 0;
+    pl->off_img = o; o += inc_up256((size_t)N * cfg->image_size * cfg->image_size * 3 * 4);
+    pl->off_fin = o; o += inc_up256(wk->finE * 4);
+    pl->off_x = o; o += inc_up256(wk->maxE * 2);
+    pl->off_y = o; o += inc_up256(wk->maxE * 2);
+    pl->off_t1 = o; o += inc_up256(wk->maxE * 2);
+    pl->off_t2 = o; o += inc_up256(wk->maxE * 2);
+    pl->total = o;
+    return MAPDIT_OK;
+}
+}  // namespace
+
+#if MAPDIT_DT == 0
+extern "C" size_t mapdit_inc_workspace_bytes(const mapdit_inc_config_t* cfg, int N) {
+    IncWalk wk;
+    IncPlan pl;
+    return inc_plan(cfg, N, &wk, &pl) == MAPDIT_OK ? pl.total : 0;
+}
+
+extern "C" int mapdit_inc_layer_shape(int index, int* cin, int* cout, int* kh, int* kw, int* stride) {
+    MD_CHECK(index >= 0 && index < MAPDIT_INC_NUM_CONV, "inc_layer_shape: index %d outside [0, %d)", index, MAPDIT_INC_NUM_CONV);
+    MD_CHECK(cin && cout && kh && kw && stride, "inc_layer_shape: null argument");
+    const mapdit_inc_config_t cfg{299};
+    IncWalk wk;
+    IncPlan pl;
+    INC_TRY(inc_plan(&cfg, 1, &wk, &pl));
+    const IncLayer& l = wk.layers[index];
+    *cin = l.cin;
+    *cout = l.cout;
+    *kh = l.kh;
+    *kw = l.kw;
+    *stride = l.st;
+    return MAPDIT_OK;
+}
+#endif
+
+extern "C" int MD_SYM(inc_features)(const mapdit_inc_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
+                                    float* feat, void* workspace, size_t ws_bytes, void* stream) {
+    IncWalk wk;
+    IncPlan pl;
+    INC_TRY(inc_plan(cfg, N, &wk, &pl));
+    MD_CHECK(wt && images && feat && workspace, "inc_features: null argument");
+    MD_CHECK(img_kind == MAPDIT_INC_IMG_U8_NHWC || img_kind == MAPDIT_INC_IMG_F32_NCHW, "inc_features: bad img_kind %d", img_kind);
+    MD_CHECK(H >= 8 && W >= 8, "inc_features: images of %d x %d (8 x 8 at the least)", H, W);
+    MD_CHECK(ws_bytes >= pl.total, "inc_features: workspace of %zu bytes, %zu needed (mapdit_inc_workspace_bytes)", ws_bytes, pl.total);
+    MD_CHECK(!((uintptr_t)workspace & 255), "inc_features: the workspace must be 256-byte aligned");
+    for (int i = 0; i < 2 * MAPDIT_INC_NUM_CONV; ++i) MD_CHECK(wt[i], "inc_features: weight slot %d is null", i);
+    char* ws = (char*)workspace;
+    wk = IncWalk{};
+    wk.dry = false;
+    wk.N = N;
+    wk.stream = stream;
+    wk.wt = wt;
+    wk.IMG = (float*)(ws + pl.off_img);
+    wk.FIN = (float*)(ws + pl.off_fin);
+    wk.X = (uint16_t*)(ws + pl.off_x);
+    wk.Y = (uint16_t*)(ws + pl.off_y);
+    wk.T1 = (uint16_t*)(ws + pl.off_t1);
+    wk.T2 = (uint16_t*)(ws + pl.off_t2);
+    const int S = cfg->image_size;
+    if (img_kind == MAPDIT_INC_IMG_U8_NHWC) INC_TRY(mapdit_inc_resize_u8((const uint8_t*)images, wk.IMG, N, H, W, 3, S, stream));
+    else INC_TRY(mapdit_inc_resize_f32((const float*)images, wk.IMG, N, H, W, 3, S, stream));
+    int Hf = 0, Wf = 0;
+    INC_TRY(wk.run(S, &Hf, &Wf));
+    return MD_SYM(inc_global_avg)(wk.FIN, MAPDIT_INC_IN_F32, feat, N, Hf * Wf, 2048, stream);
+}

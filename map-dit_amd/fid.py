@@ -1,0 +1,355 @@
+"""Native FID on ``libmapdit_hip.so``: the 2048 ``pool_3`` features of the 2015 Inception-v3 in the layout of ``pytorch-fid``'s
+``pt_inception-2015-12-05`` weights (``mapdit_inc_features``, include/mapdit.h), their fp64 sums on the device
+(``mapdit_inc_stats_accumulate``) and the Fréchet distance of the two Gaussian fits on the host.
+
+    python -m mapdit_amd.fid stats --images A.npz --inception-weights FILE --output ref.npz
+    python -m mapdit_amd.fid compare a.npz b.npz [--inception-weights FILE]
+
+Parity with the hub weights is unpinned: the network is restated from its public description and checked against an independent
+fp64 restatement on random weights (tests/inception_reference.py), not against ``pytorch-fid``.  The first FID quoted from this
+code needs one cross-check against ``pytorch-fid`` on a machine that has the weight file.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .vae import PRECISIONS, load_state_dict_file
+
+BN_EPS = 1e-3
+FEATURE_DIM = 2048
+IMAGE_SIZE = 299
+
+
+# ---- the key set: every BasicConv2d in execution order (the order of mapdit_inc_features' weight table) ----------------------------
+def conv_units() -> list:
+    """(name, cin, cout, (kh, kw), stride, (pad_h, pad_w)) of the 94 ``BasicConv2d`` units, in execution order."""
+    u = [("Conv2d_1a_3x3", 3, 32, (3, 3), 2, (0, 0)), ("Conv2d_2a_3x3", 32, 32, (3, 3), 1, (0, 0)), ("Conv2d_2b_3x3", 32, 64, (3, 3), 1, (1, 1)),
+         ("Conv2d_3b_1x1", 64, 80, (1, 1), 1, (0, 0)), ("Conv2d_4a_3x3", 80, 192, (3, 3), 1, (0, 0))]
+
+    def one(name, cin, cout, k=(1, 1), stride=1, pad=(0, 0)):
+        u.append((name, cin, cout, k, stride, pad))
+
+    for blk, cin, pool in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):
+        one(f"{blk}.branch1x1", cin, 64)
+        one(f"{blk}.branch5x5_1", cin, 48)
+        one(f"{blk}.branch5x5_2", 48, 64, (5, 5), 1, (2, 2))
+        one(f"{blk}.branch3x3dbl_1", cin, 64)
+        one(f"{blk}.branch3x3dbl_2", 64, 96, (3, 3), 1, (1, 1))
+        one(f"{blk}.branch3x3dbl_3", 96, 96, (3, 3), 1, (1, 1))
+        one(f"{blk}.branch_pool", cin, pool)
+    one("Mixed_6a.branch3x3", 288, 384, (3, 3), 2)
+    one("Mixed_6a.branch3x3dbl_1", 288, 64)
+    one("Mixed_6a.branch3x3dbl_2", 64, 96, (3, 3), 1, (1, 1))
+    one("Mixed_6a.branch3x3dbl_3", 96, 96, (3, 3), 2)
+    for blk, c7 in (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192)):
+        one(f"{blk}.branch1x1", 768, 192)
+        one(f"{blk}.branch7x7_1", 768, c7)
+        one(f"{blk}.branch7x7_2", c7, c7, (1, 7), 1, (0, 3))
+        one(f"{blk}.branch7x7_3", c7, 192, (7, 1), 1, (3, 0))
+        one(f"{blk}.branch7x7dbl_1", 768, c7)
+        one(f"{blk}.branch7x7dbl_2", c7, c7, (7, 1), 1, (3, 0))
+        one(f"{blk}.branch7x7dbl_3", c7, c7, (1, 7), 1, (0, 3))
+        one(f"{blk}.branch7x7dbl_4", c7, c7, (7, 1), 1, (3, 0))
+        one(f"{blk}.branch7x7dbl_5", c7, 192, (1, 7), 1, (0, 3))
+        one(f"{blk}.branch_pool", 768, 192)
+    one("Mixed_7a.branch3x3_1", 768, 192)
+    one("Mixed_7a.branch3x3_2", 192, 320, (3, 3), 2)
+    one("Mixed_7a.branch7x7x3_1", 768, 192)
+    one("Mixed_7a.branch7x7x3_2", 192, 192, (1, 7), 1, (0, 3))
+    one("Mixed_7a.branch7x7x3_3", 192, 192, (7, 1), 1, (3, 0))
+    one("Mixed_7a.branch7x7x3_4", 192, 192, (3, 3), 2)
+    for blk, cin in (("Mixed_7b", 1280), ("Mixed_7c", 2048)):
+        one(f"{blk}.branch1x1", cin, 320)
+        one(f"{blk}.branch3x3_1", cin, 384)
+        one(f"{blk}.branch3x3_2a", 384, 384, (1, 3), 1, (0, 1))
+        one(f"{blk}.branch3x3_2b", 384, 384, (3, 1), 1, (1, 0))
+        one(f"{blk}.branch3x3dbl_1", cin, 448)
+        one(f"{blk}.branch3x3dbl_2", 448, 384, (3, 3), 1, (1, 1))
+        one(f"{blk}.branch3x3dbl_3a", 384, 384, (1, 3), 1, (0, 1))
+        one(f"{blk}.branch3x3dbl_3b", 384, 384, (3, 1), 1, (1, 0))
+        one(f"{blk}.branch_pool", cin, 192)
+    return u
+
+
+_BN_LEAVES = ("bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")
+_IGNORED = ("fc.", "AuxLogits.")
+
+
+def inception_shapes() -> dict:
+    """Key -> shape of the feature network's state dict (``fc.*``, ``AuxLogits.*`` and ``num_batches_tracked`` are not part of it)."""
+    s = {}
+    for name, cin, cout, (kh, kw), _, _ in conv_units():
+        s[f"{name}.conv.weight"] = (cout, cin, kh, kw)
+        for leaf in _BN_LEAVES:
+            s[f"{name}.{leaf}"] = (cout,)
+    return s
+
+
+def fold_bn(w, gamma, beta, mean, var, eps=BN_EPS):
+    """conv (no bias) + eval BatchNorm -> conv + bias: w' = w * g / sqrt(var + eps), b' = beta - mean * g / sqrt(var + eps).  fp64."""
+    s = gamma.double() / torch.sqrt(var.double() + eps)
+    return w.double() * s[:, None, None, None], beta.double() - mean.double() * s
+
+
+def fold_state_dict(sd) -> dict:
+    """Checked and folded: {unit name: (w' fp64 [Cout, Cin, kh, kw], b' fp64 [Cout])} in execution order.  A missing or unexpected key
+    is a KeyError naming it, a wrong shape a ValueError; a missing ``bn.weight`` counts as ones."""
+    shapes = inception_shapes()
+    sd = {k: v for k, v in sd.items() if not k.startswith(_IGNORED) and not k.endswith("num_batches_tracked")}
+    optional = {k for k in shapes if k.endswith(".bn.weight")}
+    missing, extra = sorted(set(shapes) - set(sd) - optional), sorted(set(sd) - set(shapes))
+    if missing:
+        raise KeyError(f"Inception state dict: missing key {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+    if extra:
+        raise KeyError(f"Inception state dict: unexpected key {extra[0]!r}" + (f" (and {len(extra) - 1} more)" if len(extra) > 1 else ""))
+    for k, v in sd.items():
+        if tuple(v.shape) != tuple(shapes[k]):
+            raise ValueError(f"Inception state dict: {k!r} has shape {tuple(v.shape)}, expected {tuple(shapes[k])}")
+    out = {}
+    for name, _, cout, _, _, _ in conv_units():
+        gamma = sd.get(f"{name}.bn.weight")
+        gamma = torch.ones(cout, dtype=torch.float64) if gamma is None else gamma
+        out[name] = fold_bn(sd[f"{name}.conv.weight"], gamma, sd[f"{name}.bn.bias"], sd[f"{name}.bn.running_mean"], sd[f"{name}.bn.running_var"])
+    return out
+
+
+def pack_conv_weight(w, dtype):
+    """[Cout, Cin, kh, kw] -> 16-bit [Cout][kh][kw][Cin], the B operand of mapdit_inc_conv."""
+    return w.permute(0, 2, 3, 1).contiguous().to(torch.float32).to(dtype)
+
+
+class InceptionFeatures:
+    """``InceptionFeatures.from_file(path, device).features(x)``: x uint8 [N, H, W, 3] as ``sample_fid.py`` stores images, or fp32
+    [N, 3, H, W] in [-1, 1], on the device, any H, W >= 8 -> fp32 [N, 2048] on the device.  Every image is resized to 299 x 299
+    (bilinear, align_corners=False) first.  ``precision``: the 16-bit format of the weights and of the activations between the
+    layers ("f16" default: 10 mantissa bits; "bf16"); accumulation is fp32.  Batches above ``max_batch`` are chunked; an image alone
+    gives the same bits as in a batch."""
+
+    def __init__(self, folded, device, precision="f16", max_batch=32, image_size=IMAGE_SIZE):
+        if precision not in PRECISIONS:
+            raise ValueError(f"Inception precision {precision!r}: one of {sorted(PRECISIONS)}")
+        if max_batch < 1:
+            raise ValueError(f"max_batch={max_batch} must be at least 1")
+        self.device, self.precision, self.max_batch = torch.device(device), precision, int(max_batch)
+        units = conv_units()
+        if list(folded) != [u[0] for u in units]:
+            raise KeyError("Inception weights: the folded units are not the network's 94 in execution order")
+        self._check_plan(units)
+        dt = PRECISIONS[precision]
+        self.packed = []
+        for name in folded:
+            w, b = folded[name]
+            self.packed += [pack_conv_weight(w, dt).to(self.device), b.to(torch.float32).contiguous().to(self.device)]
+        self._cfg = L.IncConfig(image_size=int(image_size))
+        self._table = None
+        self._ws = None
+
+    @staticmethod
+    def _check_plan(units):
+        """This module's table against the library's plan (host only): slot by slot the same shapes, or nothing runs."""
+        if len(units) != L.INC_NUM_CONV:
+            raise L.MapditError(f"fid.py lists {len(units)} convolutions, mapdit.h {L.INC_NUM_CONV}")
+        lib = L.lib()
+        v = [C.c_int() for _ in range(5)]
+        for i, (name, cin, cout, (kh, kw), stride, _) in enumerate(units):
+            lib.inc_layer_shape(i, *[C.byref(x) for x in v])
+            if [x.value for x in v] != [cin, cout, kh, kw, stride]:
+                raise L.MapditError(f"weight slot {i} ({name}): fid.py has {[cin, cout, kh, kw, stride]}, the library's plan {[x.value for x in v]}")
+
+    @classmethod
+    def from_state_dict(cls, sd, device, precision="f16", max_batch=32):
+        return cls(fold_state_dict(sd), device, precision, max_batch)
+
+    @classmethod
+    def from_file(cls, path, device, precision="f16", max_batch=32):
+        return cls.from_state_dict(load_state_dict_file(path), device, precision, max_batch)
+
+    def workspace_bytes(self, n) -> int:
+        lib = L.lib()
+        need = lib.inc_workspace_bytes(C.byref(self._cfg), int(n))
+        if need == 0:
+            raise ValueError(f"Inception features refused: {lib.last_error().decode()}")
+        return need
+
+    @torch.no_grad()
+    def features(self, x):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or self.device.type != "cuda":
+            raise NotImplementedError("InceptionFeatures.features runs on the GPU only (HIP kernels, no CPU path): pass a CUDA tensor to a network on the device")
+        u8 = x.dtype == torch.uint8
+        if x.dim() != 4 or x.shape[3 if u8 else 1] != 3:
+            raise ValueError(f"Inception features: x has shape {tuple(x.shape)} ({x.dtype}), expected uint8 [N, H, W, 3] or float [N, 3, H, W]")
+        x = x.detach().to(self.device).contiguous() if u8 else x.detach().to(self.device, torch.float32).contiguous()
+        N, H, W = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+        if H < 8 or W < 8:
+            raise ValueError(f"Inception features: images of {H} x {W} (8 x 8 at the least)")
+        feat = torch.empty(N, FEATURE_DIM, dtype=torch.float32, device=self.device)
+        if N == 0:
+            return feat
+        chunk = min(N, self.max_batch)
+        need = self.workspace_bytes(chunk)
+        lib = L.lib()
+        if self._table is None:
+            self._table = (C.c_void_p * len(self.packed))(*[t.data_ptr() for t in self.packed])
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        fn = lib.inc_features_f16 if self.precision == "f16" else lib.inc_features
+        kind = L.INC_IMG_U8_NHWC if u8 else L.INC_IMG_F32_NCHW
+        with torch.cuda.device(self.device):
+            stream = L.cur_stream()
+            for i in range(0, N, chunk):
+                n = min(chunk, N - i)
+                fn(C.byref(self._cfg), self._table, x[i:i + n].data_ptr(), kind, n, H, W, feat[i:i + n].data_ptr(), self._ws.data_ptr(),
+                   self._ws.numel(), stream)
+        return feat
+
+
+class FeatureStats:
+    """Running fp64 sums of x and x x^T on the device; ``mean_cov`` -> the mean and the unbiased covariance (``np.cov``'s N - 1) as
+    fp64 numpy arrays.  Every element adds its samples in the order they arrive, so the result does not depend on the batching."""
+
+    def __init__(self, D=FEATURE_DIM, device="cuda"):
+        self.D, self.device, self.n = int(D), torch.device(device), 0
+        if self.device.type != "cuda":
+            raise NotImplementedError("FeatureStats accumulates on the GPU only (HIP kernels, no CPU path)")
+        self.sum = torch.zeros(self.D, dtype=torch.float64, device=self.device)
+        self.outer = torch.zeros(self.D, self.D, dtype=torch.float64, device=self.device)
+
+    def update(self, feat):
+        if not isinstance(feat, torch.Tensor) or not feat.is_cuda:
+            raise NotImplementedError("FeatureStats.update runs on the GPU only (HIP kernels, no CPU path): pass a CUDA tensor")
+        if feat.dim() != 2 or feat.shape[1] != self.D:
+            raise ValueError(f"FeatureStats.update: features of shape {tuple(feat.shape)}, expected [N, {self.D}]")
+        feat = feat.detach().to(self.device, torch.float32).contiguous()
+        if feat.shape[0] == 0:
+            return self
+        with torch.cuda.device(self.device):
+            L.lib().inc_stats_accumulate(feat.data_ptr(), feat.shape[0], self.D, self.sum.data_ptr(), self.outer.data_ptr(), L.cur_stream())
+        self.n += int(feat.shape[0])
+        return self
+
+    def mean_cov(self):
+        if self.n < 2:
+            raise ValueError(f"FeatureStats: {self.n} samples; a covariance needs two at the least")
+        s, o = self.sum.cpu().numpy(), self.outer.cpu().numpy()
+        mu = s / self.n
+        sigma = (o - np.outer(s, mu)) / (self.n - 1)
+        return mu, (sigma + sigma.T) / 2                      # (the sums are symmetric already; the subtraction's rounding need not be)
+
+    def save(self, path):
+        mu, sigma = self.mean_cov()
+        save_stats(path, mu, sigma)
+
+
+def save_stats(path, mu, sigma):
+    with open(path, "wb") as f:                                # (an open file: np.savez appends no second ".npz" to the name)
+        np.savez(f, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64))
+
+
+def load_stats(path):
+    """``mu`` [D] and ``sigma`` [D, D] of any ``.npz`` that holds them (``pytorch-fid`` statistics, ADM's ``VIRTUAL_*`` reference
+    batches); other keys are ignored."""
+    with np.load(path) as z:
+        for k in ("mu", "sigma"):
+            if k not in z.files:
+                raise KeyError(f"{path}: no {k!r} in the file (it holds {sorted(z.files)}); statistics need 'mu' and 'sigma'")
+        mu, sigma = np.asarray(z["mu"], np.float64), np.asarray(z["sigma"], np.float64)
+    if mu.ndim != 1 or sigma.shape != (mu.shape[0], mu.shape[0]):
+        raise ValueError(f"{path}: mu of shape {mu.shape} and sigma of shape {sigma.shape} are no [D] and [D, D]")
+    return mu, sigma
+
+
+FeatureStats.load = staticmethod(load_stats)
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
+    """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) in fp64 on the host.  tr (S1 S2)^(1/2) is the sum of the square roots of the
+    eigenvalues of S1^(1/2) S2 S1^(1/2), a symmetric positive semi-definite matrix with the spectrum of S1 S2: two symmetric eigh
+    solves, no complex arithmetic, no scipy.  Eigenvalues that rounding made negative count as 0."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, np.float64)), np.atleast_1d(np.asarray(mu2, np.float64))
+    s1, s2 = np.atleast_2d(np.asarray(sigma1, np.float64)), np.atleast_2d(np.asarray(sigma2, np.float64))
+    if mu1.shape != mu2.shape or s1.shape != s2.shape or s1.shape != (mu1.shape[0], mu1.shape[0]):
+        raise ValueError(f"frechet_distance: shapes {mu1.shape}, {s1.shape}, {mu2.shape}, {s2.shape}")
+    lam, q = np.linalg.eigh((s1 + s1.T) / 2)
+    root = (q * np.sqrt(np.clip(lam, 0.0, None))) @ q.T                    # S1^(1/2)
+    m = root @ ((s2 + s2.T) / 2) @ root
+    ev = np.linalg.eigvalsh((m + m.T) / 2)
+    d = mu1 - mu2
+    return float(d @ d + np.trace(s1) + np.trace(s2) - 2.0 * np.sqrt(np.clip(ev, 0.0, None)).sum())
+
+
+# ---- the command line ---------------------------------------------------------------------------------------------------------------
+def load_images(path):
+    """A uint8 [N, H, W, 3] array: an ``.npy``, or the first array of an ``.npz`` (``arr_0``, as ``sample_fid.py`` writes it)."""
+    a = np.load(path)
+    if not isinstance(a, np.ndarray):
+        with a:
+            if not a.files:
+                raise ValueError(f"{path}: an empty .npz")
+            a = a["arr_0" if "arr_0" in a.files else a.files[0]]
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+        raise ValueError(f"{path}: an array of shape {a.shape} and dtype {a.dtype}; images are uint8 [N, H, W, 3]")
+    return a
+
+
+def stats_of_images(images, net, batch_size=64, device="cuda") -> FeatureStats:
+    st = FeatureStats(FEATURE_DIM, device)
+    for i in range(0, len(images), batch_size):
+        st.update(net.features(torch.from_numpy(np.ascontiguousarray(images[i:i + batch_size])).to(device)))
+    return st
+
+
+def _is_stats(path) -> bool:
+    if not str(path).endswith(".npz"):
+        return False
+    with np.load(path) as z:
+        return "mu" in z.files and "sigma" in z.files
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m mapdit_amd.fid")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    s = sub.add_parser("stats", help="feature statistics (mu, sigma) of an image array")
+    s.add_argument("--images", required=True, help=".npz / .npy of uint8 [N, H, W, 3]")
+    s.add_argument("--output", required=True)
+    c = sub.add_parser("compare", help="FID of two statistics files or image arrays")
+    c.add_argument("a")
+    c.add_argument("b")
+    for q in (s, c):
+        q.add_argument("--inception-weights", default=None, help="pt_inception-2015-12-05 weights (.safetensors, or a torch state dict)")
+        q.add_argument("--batch-size", type=int, default=64)
+        q.add_argument("--precision", choices=sorted(PRECISIONS), default="f16")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    net = None
+
+    def network():
+        nonlocal net
+        if args.inception_weights is None:
+            raise ValueError("an image array needs --inception-weights (only statistics files compare without the network)")
+        if net is None:
+            net = InceptionFeatures.from_file(args.inception_weights, "cuda", args.precision, args.batch_size)
+        return net
+
+    if args.cmd == "stats":
+        images = load_images(args.images)                      # (a bad array ends the run before the weights are read)
+        st = stats_of_images(images, network(), args.batch_size)
+        st.save(args.output)
+        print(f"{args.output}: mu, sigma of {st.n} images")
+        return args.output
+    pairs = [load_stats(f) if _is_stats(f) else stats_of_images(load_images(f), network(), args.batch_size).mean_cov() for f in (args.a, args.b)]
+    fid = frechet_distance(*pairs[0], *pairs[1])
+    print(f"fid: {fid:.6f}")
+    return fid
+
+
+if __name__ == "__main__":
+    main()

@@ -3,7 +3,9 @@ random labels (classifier-free guidance when ``--cfg-scale`` > 1), stored as one
 ``<result-dir>/fid_samples/<output-file>`` (reference sample_fid.py:48-97; flags :100-114).  One hipGraph is captured for
 the batch shape and replayed for every batch (``--sampler dpm++``: DPM-Solver++ with ``--num-sampling-steps`` model evaluations).  Without a VAE (``--use-vae false``) the array holds the de-normalised
 latents clamped to [-1, 1] and quantised the same way; with ``--vae-weights FILE`` the native VAE decoder (map-dit_amd/vae.py) turns
-them into pixels first (``arr_0``: [n, 8S, 8S, 3])."""
+them into pixels first (``arr_0``: [n, 8S, 8S, 3]).  ``--fid-ref REF.npz --inception-weights FILE`` (together, and with pixels): the
+FID of the samples against the reference statistics, accumulated batch by batch on the device (map-dit_amd/fid.py), printed, returned
+and written to ``fid_samples/<output-file>.fid.json``; the array is written as before."""
 from __future__ import annotations
 
 import argparse
@@ -37,13 +39,32 @@ def build_parser():
     p.add_argument("--precision", choices=["bf16", "f16", "bf16x3"], default="f16")
     S.add_sampler_flags(p)
     S.add_vae_flags(p)
+    p.add_argument("--fid-ref", type=str, default=None, help="reference statistics (.npz with mu and sigma): compute the FID of the samples")
+    p.add_argument("--inception-weights", type=str, default=None,
+                   help="pt_inception-2015-12-05 weights (.safetensors, or a torch state dict) for --fid-ref")
+    p.add_argument("--inception-precision", choices=["f16", "bf16"], default="f16", help="16-bit operand format of the feature network")
     return p
+
+
+def check_fid_flags(args) -> bool:
+    """Before anything is built: --fid-ref and --inception-weights go together, name files, and need pixels."""
+    if args.fid_ref is None and args.inception_weights is None:
+        return False
+    if args.fid_ref is None or args.inception_weights is None:
+        raise ValueError("--fid-ref and --inception-weights go together: the FID needs the reference statistics and the feature network")
+    for flag, path in (("--fid-ref", args.fid_ref), ("--inception-weights", args.inception_weights)):
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{flag} {path}: no such file")
+    if not args.use_vae:
+        raise ValueError("--fid-ref needs pixels: the feature network reads 3-channel images, --use-vae false writes latents")
+    return True
 
 
 @torch.no_grad()          # the reference switches autograd off globally (torch.set_grad_enabled(False)); scoped here
 def main(argv=None):
     args = build_parser().parse_args(argv)
     S.check_vae_flags(args)                                               # a missing --vae-weights file ends the run before any model is built
+    want_fid = check_fid_flags(args)                                      # (so does half of the FID flag pair)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     device = torch.device("cuda")
@@ -59,6 +80,13 @@ def main(argv=None):
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
     diffusion, solver = S.make_diffusion(args, train_args)
+    if want_fid:
+        from . import fid as FID
+        ref_mu, ref_sigma = FID.load_stats(args.fid_ref)
+        if ref_mu.shape != (FID.FEATURE_DIM,):
+            raise ValueError(f"--fid-ref {args.fid_ref}: statistics of {ref_mu.shape[0]} dimensions, the pool features have {FID.FEATURE_DIM}")
+        fid_net = FID.InceptionFeatures.from_file(args.inception_weights, device, args.inception_precision)
+        fid_stats = FID.FeatureStats(FID.FEATURE_DIM, device)
 
     n = args.batch_size
     use_cfg = args.cfg_scale > 1.0
@@ -84,10 +112,21 @@ def main(argv=None):
         if vae is not None:
             samples = vae.decode(samples).sample
         gathered.append(S.to_uint8_nhwc(samples))
+        if want_fid:                                                      # the stored bytes, cut where the array is cut
+            keep = min(len(gathered[-1]), args.num_samples - fid_stats.n)
+            if keep > 0:
+                fid_stats.update(fid_net.features(torch.from_numpy(gathered[-1][:keep]).to(device)))
     out = np.concatenate(gathered, axis=0)[: args.num_samples]
     os.makedirs(os.path.join(args.result_dir, "fid_samples"), exist_ok=True)
     path = os.path.join(args.result_dir, "fid_samples", args.output_file)
     np.savez(path, arr_0=out)
+    if want_fid:
+        import json
+        value = FID.frechet_distance(*fid_stats.mean_cov(), ref_mu, ref_sigma)
+        with open(path + ".fid.json", "w") as f:
+            json.dump({"fid": value, "n": fid_stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}, f)
+        print(f"fid: {value:.6f}")
+        return value
     return path
 
 
