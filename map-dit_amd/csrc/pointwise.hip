@@ -25,11 +25,14 @@ __global__ __launch_bounds__(256) void modulate_fwd_kernel(const float* __restri
         const float4* sc = (const float4*)(scale + (size_t)n * ldmod + d);
         const float4* sh = (const float4*)(shift + (size_t)n * ldmod + d);
         float4 x0 = xp[0], x1 = xp[1], c0 = sc[0], c1 = sc[1], h0 = sh[0], h1 = sh[1];
+        float w[8] = {ka * x0.x * c0.x + kb * h0.x, ka * x0.y * c0.y + kb * h0.y, ka * x0.z * c0.z + kb * h0.z, ka * x0.w * c0.w + kb * h0.w,
+                      ka * x1.x * c1.x + kb * h1.x, ka * x1.y * c1.y + kb * h1.y, ka * x1.z * c1.z + kb * h1.z, ka * x1.w * c1.w + kb * h1.w};
+        // (the fp32 values are pinned before their 16-bit conversion, as in rot_modulate_fwd_kernel below and in the GEMM epilogue that
+        // computes the modulate of every later branch: at gain 0 the rotation engine must give the bits of this one, tests/test_rotation.py)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(w[i]));
         uint4 u;
-        u.x = pack16(ka * x0.x * c0.x + kb * h0.x, ka * x0.y * c0.y + kb * h0.y);
-        u.y = pack16(ka * x0.z * c0.z + kb * h0.z, ka * x0.w * c0.w + kb * h0.w);
-        u.z = pack16(ka * x1.x * c1.x + kb * h1.x, ka * x1.y * c1.y + kb * h1.y);
-        u.w = pack16(ka * x1.z * c1.z + kb * h1.z, ka * x1.w * c1.w + kb * h1.w);
+        u.x = pack16(w[0], w[1]); u.y = pack16(w[2], w[3]); u.z = pack16(w[4], w[5]); u.w = pack16(w[6], w[7]);
         *(uint4*)(out + m * D + d) = u;
     }
 }
@@ -360,11 +363,16 @@ __global__ __launch_bounds__(256) void rot_modulate_fwd_kernel(const float* __re
         const float4* ap = (const float4*)(A + (size_t)n * ldc + d);
         const float4* bp = (const float4*)(B + (size_t)n * ldc + d);
         const float4 x0 = xp[0], x1 = xp[1], a0 = ap[0], a1 = ap[1], b0 = bp[0], b1 = bp[1];
+        float w[8] = {__builtin_fmaf(x0.x, a0.x, x0.y * b0.x), __builtin_fmaf(x0.y, a0.y, x0.x * b0.y),
+                      __builtin_fmaf(x0.z, a0.z, x0.w * b0.z), __builtin_fmaf(x0.w, a0.w, x0.z * b0.w),
+                      __builtin_fmaf(x1.x, a1.x, x1.y * b1.x), __builtin_fmaf(x1.y, a1.y, x1.x * b1.y),
+                      __builtin_fmaf(x1.z, a1.z, x1.w * b1.z), __builtin_fmaf(x1.w, a1.w, x1.z * b1.w)};
+        // (the fp32 values are pinned before their 16-bit conversion, as in the GEMM epilogue that computes the same modulate for
+        // every later branch (gemm.hip EpiResid): the fp16 build otherwise folds the conversion into the fma - one rounding here, two there)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(w[i]));
         uint4 u;
-        u.x = pack16(__builtin_fmaf(x0.x, a0.x, x0.y * b0.x), __builtin_fmaf(x0.y, a0.y, x0.x * b0.y));
-        u.y = pack16(__builtin_fmaf(x0.z, a0.z, x0.w * b0.z), __builtin_fmaf(x0.w, a0.w, x0.z * b0.w));
-        u.z = pack16(__builtin_fmaf(x1.x, a1.x, x1.y * b1.x), __builtin_fmaf(x1.y, a1.y, x1.x * b1.y));
-        u.w = pack16(__builtin_fmaf(x1.z, a1.z, x1.w * b1.z), __builtin_fmaf(x1.w, a1.w, x1.z * b1.w));
+        u.x = pack16(w[0], w[1]); u.y = pack16(w[2], w[3]); u.z = pack16(w[4], w[5]); u.w = pack16(w[6], w[7]);
         *(uint4*)(out + m * D + d) = u;
     }
 }
@@ -486,7 +494,12 @@ __global__ void scale_copy_kernel(float* __restrict__ out, const float* __restri
 // out[i] += alpha * x[i]: the product is rounded to fp32 first (what scale_copy_kernel stores), then added - not one fused multiply-add
 __global__ void scale_accumulate_kernel(float* __restrict__ out, const float* __restrict__ x, long n, float alpha) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = out[i] + __fmul_rn(alpha, x[i]);
+    if (i < n) {
+        // (pinned: __fmul_rn is a plain product to hipcc, which -ffp-contract=fast folded into one v_fmac_f32 with the addition)
+        float prod = alpha * x[i];
+        asm volatile("" : "+v"(prod));
+        out[i] = out[i] + prod;
+    }
 }
 // out[i] = sum_s slabs[s*stride + i], four elements per thread   (fixed order; n a multiple of 4, 16-byte aligned)
 __global__ void reduce_slabs_kernel(float* __restrict__ out, const float* __restrict__ slabs, int nslabs, long stride, long n4) {
@@ -684,7 +697,7 @@ extern "C" int MD_SYM(resid_mod_bwd)(const mapdit_resid_mod_bwd_t* a, void* stre
         hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->dgain_part, npart, a->dgain_out, 0);
         MD_LAUNCH_CHECK();
     }
-    if (a->gain_partials_out) *a->gain_partials_out = own_gain ? 0 : npart;
+    if (a->gain_partials_out) *a->gain_partials_out = own_gain || !a->dxm ? 0 : npart;      // (no modulate half: no partial is written)
     return MAPDIT_OK;
 }
 
