@@ -666,6 +666,38 @@ int mapdit_data_batch(const float* means, const float* stds, const int64_t* labe
                       int64_t* y, int64_t* idx_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Counter-based step draws (step_rng.py, train.py --step-rng counter), additive within abi 5: everything random in a training step
+ * - diffusion / flow noise, timesteps, label drops, the --synthetic batch - as ONE launch and as a pure function of
+ * (seed, step, slot).  `slot` is a sample's 0-based position in the GLOBAL batch of 0-based optimiser step `step`: a rank passes
+ * first_slot = lo of its share (parallel.shard_batch), micro-batch k of that rank lo + k * micro, so neither the world size nor the
+ * number of micro-batches enters a counter.  No state, no host read, no allocation: capturable.  THE LAYOUT BELOW IS A CONTRACT:
+ * resuming a run bit for bit depends on it.
+ *   Generator, key and the fp32 normal recipe: those of the data set above (Philox4x32-10, key = (seed & 0xffffffff, seed >> 32),
+ *     normals within 8 ulp of the real value).  The tags below sit in counter word c3, where the data set has TAG_PERM / TAG_NOISE: no
+ *     counter of one family is a counter of another.
+ *   eps[j][i]   = normal i & 3 of philox(counter = (i >> 2, first_slot + j, step, MAPDIT_TAG_EPS))
+ *   x_syn[j][i] = the same with MAPDIT_TAG_SYNX
+ *   Scalars of a slot: a = philox(counter = (0, slot, step, MAPDIT_TAG_STEP)), b = philox(counter = (1, slot, step, MAPDIT_TAG_STEP))
+ *     t     = (uint64(a0) * T) >> 32                  in [0, T); P(t = k) differs from 1 / T by less than 2^-32, a relative bias below
+ *                                                     T / 2^32 (2.3e-7 at T = 1000)
+ *     drop  = (a1 >> 8) < thr,  thr = ceil((double)(float)drop_prob * 2^24) computed on the host: an integer compare with the truth
+ *                                                     table of torch.rand(fp32) < p for the 24-bit uniform (a1 >> 8) 2^-24
+ *     u     = ((uint64(a2) << 21) | (a3 >> 11)) * 2^-53   in [0, 1), 53 bits, exact
+ *     y_syn = (uint64(b0) * num_classes) >> 32        in [0, num_classes)
+ *     z     = normal 0 of the fp32 recipe on the words (b2, b3): r cos(2 pi u'), widened to double (b1 is not used)
+ *   mapdit_step_draw: every output is nullable and a null one costs nothing; count >= 1, per >= 1, first_slot >= 0,
+ *     first_slot + count <= 2^32, count * per <= 2^34; 1 <= T <= 2^31 where t is asked for, num_classes >= 1 where y_syn is,
+ *     0 <= drop_prob <= 1 where drop is.  eps / x_syn fp32 [count][per]; t / drop / y_syn int64 [count]; u / z fp64 [count].  One lane
+ *     makes one Philox call for four consecutive normals; where per % 4 == 0 and the plane is 16-byte aligned it stores them as 16 bytes,
+ *     otherwise element by element (the ragged tail, an unaligned plane).  The tags are fixed: changing one changes every run.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define MAPDIT_TAG_EPS 0x53455053
+#define MAPDIT_TAG_SYNX 0x53594E58
+#define MAPDIT_TAG_STEP 0x53544550
+int mapdit_step_draw(uint64_t seed, uint32_t step, long first_slot, int count, long per, int T, int num_classes, float drop_prob,
+                     float* eps, float* x_syn, int64_t* t, double* u, double* z, int64_t* drop, int64_t* y_syn, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Engine: the whole DiT forward / backward sequenced from C++ on one stream (src/dit.py:70-105 and its autograd).
  * ------------------------------------------------------------------------------------------------------------ */
 enum { MAPDIT_OFF_MP_SILU = 1, MAPDIT_OFF_MP_RESIDUAL = 2, MAPDIT_OFF_MP_POS_ENC = 4, MAPDIT_OFF_MP_EMBEDDING = 8,

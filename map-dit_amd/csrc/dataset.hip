@@ -1,15 +1,10 @@
 // Device-resident latent data set (train.py --data-loader device, data.py): the epoch shuffle, the gather of a batch and the draw from
 // each sample's posterior, in one launch and as a pure function of (seed, epoch, position) - mapdit.h, "Device-resident latent data set",
-// is the contract.  The library's first counter-based generator lives here: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random
-// numbers: as easy as 1, 2, 3", SC'11), written from its published definition.
-//
-// Normals are Box-Muller pairs of u = ((w >> 8) + 0.5) 2^-24, w a Philox word: u lies in [2^-25, 1 - 2^-25], so |z| <= sqrt(50 ln 2) =
-// 5.89 and the tail beyond it is CUT OFF (4e-9 of the mass per draw).  u has 25 significant bits above 1/2 and is never formed there:
-// the upper half is reflected, ln u = log1p(-(1 - u)) and sincospi(2u) = sincospi(2u - 2), and 1 - u has 24 bits again - every argument
-// the library functions see is exact, so the result carries their error and nothing else.
+// is the contract.  The generator (Philox4x32-10) and the fp32 normal recipe live in philox.h, which steprng.hip shares: they exist once.
 #include <math.h>
 
 #include "common.h"
+#include "philox.h"
 
 // mean + eps * std is two roundings and (f - m) / s a correctly rounded subtraction and division in the reference's torch ops
 // (train.py:170-176): no fused multiply-add here.  -ffp-contract=fast disregards the pragma (the backend fuses whatever it meets,
@@ -22,43 +17,6 @@ namespace {
 #define DS_TAG_NOISE 0x4E4F4953u   // "NOIS"
 #define DS_LANES 256
 #define DS_MAX_CHUNKS 64           // workgroups per sample at most; the groups of four elements beyond them are strided over
-
-struct u32x4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;                                              // (the bump after the last round is dead code)
-        k1 += 0xBB67AE85u;
-    }
-    return {c0, c1, c2, c3};
-}
-
-// One Box-Muller pair from two words: (r cos 2 pi u_b, r sin 2 pi u_b), r = sqrt(-2 ln u_a).  kr = the 24-bit draw reflected into the
-// lower half where it lies in the upper one; (kr + 0.5) 2^-24 then has at most 24 significant bits.
-__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float* zc, float* zs) {
-    const uint32_t ka = wa >> 8, kb = wb >> 8;
-    const bool ha = ka >> 23, hb = kb >> 23;
-    const float va = ((float)(ha ? 0xFFFFFFu - ka : ka) + 0.5f) * 0x1p-24f;      // u_a, or 1 - u_a
-    const float vb = ((float)(hb ? 0xFFFFFFu - kb : kb) + 0.5f) * 0x1p-23f;      // 2 u_b, or 2 - 2 u_b
-    const float r = sqrtf(-2.0f * (ha ? log1pf(-va) : logf(va)));
-    float s, c;
-    sincospif(vb, &s, &c);
-    *zc = r * c;
-    *zs = r * (hb ? -s : s);
-}
-
-__device__ __forceinline__ void philox_normal4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, float z[4]) {
-    const u32x4 w = philox4x32_10(c0, c1, c2, c3, k0, k1);
-    box_muller(w.x, w.y, &z[0], &z[1]);
-    box_muller(w.z, w.w, &z[2], &z[3]);
-}
 
 // The epoch permutation of [0, N): a balanced Feistel network of four rounds over [0, 2^(2 half)), walked until the value is below N.
 // 2^(2 half) <= 4 N, so a walk takes fewer than four turns on average; it ends because the network is a bijection (the walk from a
@@ -169,8 +127,6 @@ int feistel_half(long N) {
     for (unsigned long v = (unsigned long)(N - 1); v; v >>= 1) ++bits;
     return bits < 2 ? 1 : (bits + 1) / 2;
 }
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

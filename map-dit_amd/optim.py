@@ -356,6 +356,38 @@ class FusedAdamEMA:
             self.exp_avg[o:o + n].view(shape).copy_(st["exp_avg"])
             self.exp_avg_sq[o:o + n].view(shape).copy_(st["exp_avg_sq"])
 
+    # ---- resuming a run bit for bit (train.py --resume) ------------------------------------------------------------------
+    GUARD_FIELDS = ("step_count", "_launches", "_launches_polled", "_overflows_seen", "_scale_ceiling", "_clean_since", "_stuck",
+                    "_poll_every_step")
+
+    def resume_state_dict(self):
+        """What state_dict() - the reference's Adam layout - does not carry and a bit-exact continuation needs: the flat fp32 EMA copies
+        ({"ema": {std: fp32 [flat]}}; the snapshots are fp16) and everything step() and poll_overflow() read of the non-finite guard
+        ({"guard": the host counters, the model's fp16 loss scale and the two device status words}).  Synchronises (checkpoint cadence).
+        Under a sharded optimiser the copies are complete after reducer.gather_state() only, like state_dict()."""
+        guard = {k: getattr(self, k) for k in self.GUARD_FIELDS}
+        guard["loss_scale"] = float(getattr(self.model, "loss_scale", 0.0))
+        guard["status"] = self._status.cpu()
+        return {"ema": {std: flat.detach().cpu() for std, flat in zip(self.ema_stds, self.ema)}, "guard": guard}
+
+    def load_resume_state_dict(self, state):
+        """The counterpart of resume_state_dict(); call it AFTER load_state_dict(), which resets the guard for a foreign checkpoint."""
+        ema, guard = state["ema"], state["guard"]
+        if sorted(ema) != sorted(self.ema_stds):
+            raise ValueError(f"the checkpoint holds EMA copies for std {sorted(ema)}, this optimiser carries {sorted(self.ema_stds)}")
+        for std, flat in zip(self.ema_stds, self.ema):
+            if ema[std].shape != flat.shape or ema[std].dtype != flat.dtype:
+                raise ValueError(f"EMA copy {std}: {tuple(ema[std].shape)} {ema[std].dtype} does not fit the model's flat buffer "
+                                 f"{tuple(flat.shape)} {flat.dtype}")
+            flat.copy_(ema[std])
+        missing = [k for k in self.GUARD_FIELDS + ("loss_scale", "status") if k not in guard]
+        if missing:
+            raise ValueError(f"the checkpoint's guard state lacks {missing}")
+        for k in self.GUARD_FIELDS:
+            setattr(self, k, guard[k])
+        self.model.loss_scale = guard["loss_scale"]
+        self._status.copy_(guard["status"])
+
     def load_ema_state_dict(self, std: float, sd):
         """Restore one EMA copy from a snapshot's ``state_dict`` (resuming a run)."""
         flat = self.ema[self.ema_stds.index(std)]

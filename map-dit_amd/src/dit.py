@@ -591,12 +591,21 @@ class DiT(nn.Module):
     # there is nothing for a tracing compiler to fuse: dynamo is told not to trace into forward, so torch.compile(model) is a
     # thin wrapper around the eager call (and its "_orig_mod."-prefixed state dicts load, see _strip_compile_prefix).
     @torch.compiler.disable
-    def forward(self, x, t, y):
-        """x [N,C,H,W], t [N], y [N] -> [N,2C,H,W]   (reference src/dit.py:70-105)."""
+    def forward(self, x, t, y, force_drop_ids=None):
+        """x [N,C,H,W], t [N], y [N] -> [N,2C,H,W]   (reference src/dit.py:70-105).  force_drop_ids (int64 or bool [N], 1 = drop the
+        label): the caller's label drops in place of token_drop's torch.rand draw - used in training mode only, like the reference's
+        LabelEmbedder.forward(labels, train, force_drop_ids); the default generator is then not consumed."""
         x_in = x
         x, t, y = self._check_inputs(x, t, y)
+        if force_drop_ids is not None:
+            if self.class_dropout_prob <= 0:
+                raise ValueError("force_drop_ids needs the null-class row of the label table (class_dropout_prob > 0)")
+            if not isinstance(force_drop_ids, torch.Tensor) or force_drop_ids.shape != y.shape \
+                    or force_drop_ids.dtype not in (torch.int64, torch.bool):
+                raise ValueError(f"force_drop_ids must be an int64 or bool tensor of shape {tuple(y.shape)}")
+            force_drop_ids = force_drop_ids.to(y.device)
         if self.training and self.class_dropout_prob > 0:
-            y = self.y_embedder.token_drop(y)                                   # label_embedder.py:19-34
+            y = self.y_embedder.token_drop(y) if force_drop_ids is None else self.y_embedder.token_drop(y, force_drop_ids)   # label_embedder.py:19-34
         # (x.requires_grad passes _check_inputs with model.input_gradients only: the saved forward then serves dL/dx)
         params_need_grad = any(p.requires_grad for p in self.parameters())
         need_grad = torch.is_grad_enabled() and (params_need_grad or x_in.requires_grad)
@@ -636,7 +645,8 @@ class DiT(nn.Module):
 
     @torch.compiler.disable
     def forward_with_cfg(self, x, t, y, cfg_scale):
-        """Classifier-free guidance batch (reference src/dit.py:107-118)."""
+        """Classifier-free guidance batch (reference src/dit.py:107-118).  It takes no force_drop_ids: the caller writes the null class
+        into y itself, and a keyword it does not know is a TypeError."""
         half = x[: len(x) // 2]
         combined = torch.cat([half, half], dim=0)
         model_out = self.forward(combined, t, y)

@@ -16,7 +16,12 @@ loss-second-moment: improved-DDPM's loss-aware timestep resampling with importan
 (diffusion/timestep_sampler.py; the checkpoint then gains a "schedule_sampler" key), and --objective flow: the rectified-flow velocity
 objective (flow/__init__.py) in the diffusion objective's place, with --flow-shift and --flow-timestep-density; config.yaml records it
 and the sampler CLIs read it, and --data-loader device: the data set lives in HBM and a step's batch is one launch, a function of
-(--seed, step) alone (data.py); the default, host, is the reference's DataLoader.
+(--seed, step) alone (data.py); the default, host, is the reference's DataLoader, and --step-rng counter: a step's timesteps, noise,
+label drops and --synthetic batch come from one launch of a counter-based generator (step_rng.py) instead of torch generators, the same
+bits for any world size and --grad-accum-steps, and --resume PATH: continue a --step-rng counter run from one of its checkpoints, which
+hold the keys "ema" (the fp32 EMA copies) and "train_state" (step, log accumulators, fp16 guard) besides the reference's; with the
+device loader or --synthetic the continued run ends with the bits of the run that was never stopped.  A default (--step-rng torch) run
+writes the reference's checkpoint, key for key, and cannot be continued: its generators' states are in no checkpoint.
 """
 import argparse
 import contextlib
@@ -33,8 +38,10 @@ from .data import DeviceLatentDataset
 from .diffusion import create_diffusion
 from .diffusion.timestep_sampler import create_named_schedule_sampler
 from .flow import create_flow
+from ._lib import MapditError
 from .optim import FusedAdamEMA, create_lr_lambda
 from .src.models import DIT_MODELS
+from .step_rng import StepRNG, first_slot
 
 MP_FLAGS = ["cosine-attention", "weight-normalization", "forced-weight-normalization", "mp-residual", "mp-silu",
             "no-layernorm", "mp-pos-enc", "mp-embedding"]          # reference README.md:59-66
@@ -95,7 +102,7 @@ def build_parser():
     p.add_argument("--synthetic", action="store_true", help="N(0,1) 4x32x32 latents and uniform labels instead of a dataset")
     p.add_argument("--synthetic-input-size", type=int, default=32,
                    help="side of the --synthetic latents (64: 512x512 images, 1,024 tokens per sample at patch 2)")
-    p.add_argument("--results-dir", type=str, required=True)
+    p.add_argument("--results-dir", type=str, default=None, help="required, except with --resume (the run continues in its own directory)")
     p.add_argument("--model", type=str, choices=list(DIT_MODELS.keys()), default="DiT-XS/2")
     p.add_argument("--num-classes", type=int, default=1000)
     p.add_argument("--num-steps", type=int, default=400_000)
@@ -155,7 +162,86 @@ def build_parser():
     p.add_argument("--use-rotation-modulation", action=argparse.BooleanOptionalAction, default=False,
                    help="block conditioning by rotation modulation (reference README.md:1-3; not in its code snapshot: this build's "
                         "own restatement, parity unpinned): ~5.4 %% fewer parameters; bf16 and f16 precisions")
+    p.add_argument("--step-rng", choices=["torch", "counter"], default="torch",
+                   help="where a step's randomness comes from: torch (default: torch.randint / randn_like / rand on per-rank generators, "
+                        "as the reference draws) or counter (step_rng.py: timesteps, noise, label drops and the --synthetic batch in one "
+                        "launch, a function of (--seed, optimiser step, slot in the global batch): the same draws for any world size and "
+                        "--grad-accum-steps, nothing to carry over a --resume.  With --data-loader device or --synthetic the whole step "
+                        "is then a function of (--seed, step); with --data-loader host the loader's order is not.  Checkpoints of a "
+                        "counter run gain the keys --resume needs; a torch run writes the reference's two)")
+    p.add_argument("--resume", type=str, default=None, metavar="PATH",
+                   help="continue a --step-rng counter run: PATH is one of its checkpoints/NNNNNNN.pt or its experiment directory (the "
+                        "latest checkpoint).  "
+                        "The run goes on in that directory (log.txt is appended to, config.yaml is left alone); its arguments are read "
+                        "from config.yaml and one given here with another value is refused, except --num-steps (may be raised), "
+                        "--log-every, --ckpt-every, --ema-snapshot-every, --verbose, --num-workers and --grad-comm (allreduce / zero1).  "
+                        "Bit-identical to the unstopped run with --data-loader device or --synthetic; a host loader starts a fresh epoch "
+                        "order.  A --step-rng torch run cannot be continued (its checkpoints are the reference's, without the generators)")
     return p
+
+
+# ---- --resume: host logic (no device work) ------------------------------------------------------------------------------------------
+RESUME_FREE = ("num_steps", "log_every", "ckpt_every", "ema_snapshot_every", "verbose", "num_workers", "grad_comm", "resume", "results_dir")
+RESUME_KEYS = ("model", "opt", "ema", "train_state")          # what a checkpoint must hold to be continued
+
+
+def resolve_checkpoint(path):
+    """--resume PATH -> the checkpoint file: PATH itself, or the latest checkpoints/NNNNNNN.pt of the experiment directory PATH."""
+    if os.path.isdir(path):
+        found = sorted(glob(os.path.join(path, "checkpoints", "[0-9]*.pt")), key=lambda f: int(os.path.splitext(os.path.basename(f))[0]))
+        if not found:
+            raise ValueError(f"--resume {path}: no checkpoints/NNNNNNN.pt in that directory")
+        return found[-1]
+    if not os.path.isfile(path):
+        raise ValueError(f"--resume {path}: neither a checkpoint file nor an experiment directory")
+    return path
+
+
+def explicit_args(argv):
+    """The arguments given on the command line (dest -> value), without the defaults of those that were not."""
+    p = build_parser()
+    for a in p._actions:
+        a.default, a.required = argparse.SUPPRESS, False
+    return vars(p.parse_args(argv))
+
+
+def merge_resume_args(args, given, cfg):
+    """The arguments a continued run trains with: the run's own (config.yaml) with the command line's for the RESUME_FREE ones.  A
+    run-defining argument given with another value is a ValueError naming it.  Schedules that were derived from --num-steps (None in
+    the yaml) are derived from the ORIGINAL --num-steps again, so that raising it does not move the learning-rate curve."""
+    merged = argparse.Namespace(**vars(args))
+    for key, value in vars(args).items():
+        if key in RESUME_FREE:
+            if key not in given and key in cfg and key not in ("resume", "results_dir"):
+                setattr(merged, key, cfg[key])
+        elif key in given and key in cfg and given[key] != cfg[key]:
+            raise ValueError(f"--resume: --{key.replace('_', '-')} {given[key]!r} differs from the run's {cfg[key]!r} (config.yaml); a "
+                             f"continued run keeps its arguments - only {', '.join('--' + k.replace('_', '-') for k in RESUME_FREE[:7])} may change")
+        elif key in cfg:
+            setattr(merged, key, cfg[key])
+    if merged.step_rng != "counter":
+        raise ValueError("--resume continues runs trained with --step-rng counter: a --step-rng torch run keeps its randomness in torch "
+                         "generators that no checkpoint holds, and its checkpoints are the reference's (\"model\", \"opt\")")
+    original = int(cfg["num_steps"])
+    if merged.num_lin_warmup is None:
+        merged.num_lin_warmup = original // 150
+    if merged.start_decay is None:
+        merged.start_decay = original // 10
+    if merged.ema_snapshot_every is None:
+        merged.ema_snapshot_every = original // 250
+    return merged
+
+
+def check_resumable(ckpt, args, path):
+    """Refuse a checkpoint that cannot be continued (a reference checkpoint holds only "model" and "opt") or lies behind --num-steps."""
+    for key in RESUME_KEYS:
+        if key not in ckpt:
+            raise ValueError(f"--resume {path}: the checkpoint has no {key!r} key (it holds {sorted(ckpt)}): it was not written by this "
+                             f"train.py and cannot be continued bit for bit")
+    done = int(ckpt["train_state"]["train_steps"])
+    if args.num_steps < done:
+        raise ValueError(f"--resume {path}: --num-steps {args.num_steps} lies below the checkpoint's step {done}")
+    return done
 
 
 def micro_batch(batch_size: int, world: int, accum_steps: int) -> int:
@@ -172,6 +258,19 @@ def micro_batch(batch_size: int, world: int, accum_steps: int) -> int:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    resume, resume_path = None, None
+    if args.resume is not None:
+        resume_path = resolve_checkpoint(args.resume)
+        resume_exp = os.path.dirname(os.path.dirname(os.path.abspath(resume_path)))
+        with open(os.path.join(resume_exp, "config.yaml")) as f:
+            args = merge_resume_args(args, explicit_args(argv), yaml.safe_load(f))
+        if args.grad_comm in ("zero1w", "zero1w-bf16"):
+            raise MapditError("--resume is not built for --grad-comm zero1w / zero1w-bf16 (a rank holds rows of every weight, the checkpoint "
+                              "the whole state); continue with allreduce or zero1")
+        resume = torch.load(resume_path, map_location="cpu", weights_only=True)
+        check_resumable(resume, args, resume_path)
+    elif args.results_dir is None:
+        raise ValueError("--results-dir is required (except with --resume)")
     K = int(args.grad_accum_steps)
     micro = micro_batch(args.batch_size, int(os.environ.get("WORLD_SIZE", "1")), K)      # (fails here, before any device work)
     if K > 1 and args.grad_comm in ("zero1w", "zero1w-bf16"):
@@ -223,9 +322,12 @@ def main(argv=None):
 
     exp = None
     if rank == 0:
-        exp = setup_experiment(args.model, args.results_dir)
-        with open(os.path.join(exp, "config.yaml"), "w") as f:
-            yaml.dump(vars(args), f)
+        if resume is not None:
+            exp = resume_exp                     # the run's own directory: config.yaml stays, log.txt is appended to
+        else:
+            exp = setup_experiment(args.model, args.results_dir)
+            with open(os.path.join(exp, "config.yaml"), "w") as f:
+                yaml.dump(vars(args), f)
         os.makedirs(os.path.join(exp, "ema"), exist_ok=True)
         logf = open(os.path.join(exp, "log.txt"), "a")
 
@@ -261,6 +363,24 @@ def main(argv=None):
     reducer.attach(opt)
     # the default draws with torch.randint below, exactly as before; the sampler object exists only with the flag
     t_sampler = create_named_schedule_sampler(args.schedule_sampler, diffusion) if args.schedule_sampler != "uniform" else None
+    # --step-rng counter: one launch per micro-batch draws everything random in it; no torch generator is consumed in a step
+    step_rng = StepRNG(args.seed, dev) if args.step_rng == "counter" else None
+    start_step = 0
+    if resume is not None:
+        state = resume["train_state"]
+        model.load_state_dict(resume["model"])
+        opt.load_state_dict(resume["opt"])
+        opt.load_resume_state_dict({"ema": resume["ema"], "guard": state["guard"]})      # (ZeRO-1: a rank goes on updating its shard of it)
+        if t_sampler is not None:
+            if "schedule_sampler" not in resume:
+                raise ValueError(f"--resume {resume_path}: the checkpoint has no 'schedule_sampler' key, the run samples with {args.schedule_sampler}")
+            t_sampler.load_state_dict(resume["schedule_sampler"])
+        start_step = int(state["train_steps"])
+        log(f"resuming from {resume_path} at step {start_step} (saved by {state['world_size']} rank(s))")
+        if loader is not None:
+            log("--data-loader host: the loader's position is not in a checkpoint - the continuation starts a fresh epoch order and is not "
+                "bit-identical to the run that was never stopped (--data-loader device is)")
+        del resume
 
     def draw_t(n):
         if flow_mode:
@@ -279,11 +399,14 @@ def main(argv=None):
             while True:                          # train_steps: optimiser steps taken so far = the 0-based step this batch belongs to
                 yield ds.batch(train_steps, args.batch_size, rank, world)
         if loader is None:
+            if step_rng is not None:             # the synthetic batch is drawn with the step's other draws (counter_loss)
+                while True:
+                    yield None, None
             g = torch.Generator(device=dev).manual_seed(args.seed + 1 + rank)
             while True:
                 yield (torch.randn(per_rank, 4, args.input_size, args.input_size, device=dev, generator=g),
                        torch.randint(0, args.num_classes, (per_rank,), device=dev, generator=g))
-        epoch = 0
+        epoch = start_step // max(len(loader), 1)      # (a continued run starts a fresh epoch order: the loader's position is not kept)
         while True:
             if world > 1:
                 loader.sampler.set_epoch(epoch)
@@ -291,10 +414,45 @@ def main(argv=None):
                 yield x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
             epoch += 1
 
-    train_steps, log_steps, running, start = 0, 0, torch.zeros((), device=dev), time()
+    def counter_loss(xk, yk, k):
+        """Micro-batch k of this rank under --step-rng counter: its slots of the global batch are lo + k * micro onwards."""
+        want = ["eps"] + (["x_syn", "y_syn"] if xk is None else []) + (["drop"] if model.class_dropout_prob > 0 else [])
+        logit_normal = flow_mode and args.flow_timestep_density == "logit-normal"
+        want.append("u" if t_sampler is not None else "z" if logit_normal else "t")
+        shape = (micro, args.in_channels, args.input_size, args.input_size)
+        d = step_rng.draw(train_steps, first_slot(lo, k, micro), micro, per=shape[1] * shape[2] * shape[3], T=diffusion.num_timesteps,
+                          num_classes=args.num_classes, drop_prob=model.class_dropout_prob, want=want)
+        if xk is None:
+            xk, yk = d.x_syn.view(shape), d.y_syn
+        kw = dict(y=yk, force_drop_ids=d.drop) if "drop" in want else dict(y=yk)
+        if t_sampler is not None:
+            t, w = t_sampler.sample_from_uniforms(d.u)
+            losses = diffusion.training_losses(model, xk, t, kw, noise=d.eps.view(shape))
+            t_sampler.update_with_local_losses(t, losses["loss"].detach())
+            return (losses["loss"] * w).mean()
+        t = diffusion.timesteps_from_normals(d.z) if logit_normal else d.t
+        return diffusion.training_losses(model, xk, t, kw, noise=d.eps.view(shape))["loss"].mean()
+
+    train_steps, log_steps, running, start = start_step, 0, torch.zeros((), device=dev), time()
+    if resume_path is not None:                  # the log accumulators: a checkpoint may fall between two log lines
+        log_steps = int(state["log_steps"])
+        running.fill_(float(state["running"]))
+    if train_steps >= args.num_steps:
+        log(f"nothing to do: the checkpoint is at step {train_steps}, --num-steps is {args.num_steps}")
+        return exp
     log(f"training for {args.num_steps} steps...")
     for x, y in batches():
-        if K == 1:
+        if step_rng is not None:
+            opt.zero_grad()
+            loss = torch.zeros((), device=dev)
+            for k in range(K):
+                sl = slice(k * micro, (k + 1) * micro)
+                part = counter_loss(None if x is None else x[sl], None if y is None else y[sl], k)
+                with (reducer.no_sync() if k < K - 1 else contextlib.nullcontext()):
+                    part.backward()
+                loss = loss + part.detach()
+            loss = loss / K
+        elif K == 1:
             if t_sampler is None:
                 t = draw_t(x.shape[0])
                 loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
@@ -346,6 +504,13 @@ def main(argv=None):
             ckpt = {"model": model.state_dict(), "opt": opt.state_dict()}                      # reference train.py:125-132
             if t_sampler is not None:
                 ckpt["schedule_sampler"] = t_sampler.state_dict()
+            if step_rng is not None:
+                # what --resume needs beyond the reference's keys: the fp32 EMA copies (the snapshots are fp16) and the loop's own state.
+                # (The default run's checkpoint stays the reference's, key for key.)
+                rs = opt.resume_state_dict()
+                ckpt["ema"] = rs["ema"]
+                ckpt["train_state"] = {"train_steps": train_steps, "running": running.item(), "log_steps": log_steps, "guard": rs["guard"],
+                                       "step_rng": args.step_rng, "seed": args.seed, "world_size": world}
             torch.save(ckpt, os.path.join(exp, "checkpoints", f"{train_steps:07d}.pt"))
         if rank == 0 and args.ema_snapshot_every and train_steps % args.ema_snapshot_every == 0:
             for std in opt.ema_stds:                                   # reference src/ema.py:143-155
