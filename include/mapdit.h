@@ -879,7 +879,8 @@ int mapdit_allgather_bucket(mapdit_comm_t* comm, float* buf, long count, void* s
  * up2 != 0: `in` is [N, H/2, W/2, Cin] and is read through a nearest-neighbour 2x upsample (H, W even): the gather reads
  * (y >> 1, x >> 1), the upsampled tensor is never written.  out_kind: fp32 NHWC, fp32 NCHW (no res), or 16-bit NHWC.
  * Cin % 64 == 0 and Cout % 64 == 0 with NHWC on both sides run on the MFMA (128 x 128 output tiles when Cout % 128 == 0, else
- * 128 x 64 - the same bits either way; 64-wide K tiles that never straddle a tap); every other shape takes a plain kernel.  Out-of-image taps are zeros that are never loaded. */
+ * 128 x 64 - the same bits either way; 64-wide K tiles that never straddle a tap); every other shape takes a plain kernel.  Out-of-image taps are zeros that are never loaded.
+ * The kernels are the library's one convolution (csrc/conv.hip), which mapdit_inc_conv runs too. */
 enum { MAPDIT_VAE_IN_16 = 0, MAPDIT_VAE_IN_F32 = 1, MAPDIT_VAE_IN_F32_NCHW = 2 };
 enum { MAPDIT_VAE_OUT_F32 = 0, MAPDIT_VAE_OUT_F32_NCHW = 1, MAPDIT_VAE_OUT_16 = 2 };
 typedef struct {
@@ -898,7 +899,7 @@ int mapdit_vae_conv(const mapdit_vae_conv_t* args, void* stream);
  *   out[n, y, x, co] = bias[co] + sum_{ky, kx, c} in[n, 2 y + ky, 2 x + kx, c] * w[co][ky][kx][c]
  * `in` is [N, Hin, Win, Cin] (Hin, Win >= 2); args->H, args->W are the OUTPUT size and must equal Hin / 2, Win / 2 (rounded down);
  * k == 3, up2 == 0.  A tap with 2 y + ky >= Hin or 2 x + kx >= Win is a zero that is never loaded (for an odd size the pad row is
- * never touched).  The kernels, tile forms, K order and path selection are mapdit_vae_conv's; only the gather's coordinates differ. */
+ * never touched).  The kernels (csrc/conv.hip), tile forms, K order and path selection are mapdit_vae_conv's; only the gather's coordinates differ. */
 int mapdit_vae_conv_down(const mapdit_vae_conv_t* args, int Hin, int Win, void* stream);
 /* GroupNorm over NHWC (+ SiLU when silu != 0): x fp32 [N, HW, C], G groups of C / G adjacent channels, biased variance;
  * out 16-bit [N, HW, C] = act((x - mean) * rstd * gamma + beta); stats (may be NULL) fp32 [N][G][2] = (mean, rstd).
@@ -990,7 +991,8 @@ int mapdit_vae_stats_finish(const double* acc, double count, float* ch_mean, flo
  * 16-bit input with Cin % 16 == 0 and Cout % 16 == 0 runs on the MFMA: K = (ky, kx, c) flattened and staged in 16-channel granules,
  * so a 64-wide K tile may span taps and its tail past kh * kw * Cin is zero-filled; 128 x 64 output tiles with row and column guards.
  * Every other case (the first layer: Cin = 3) takes a plain kernel.  The K order of an output element does not depend on its place
- * in a tile or on N: an image alone and in a batch gives the same bits.  Out-of-image taps are zeros that are never loaded. */
+ * in a tile or on N: an image alone and in a batch gives the same bits.  Out-of-image taps are zeros that are never loaded.
+ * The kernels are mapdit_vae_conv's (csrc/conv.hip): on operands both accept, the two entry points give the same bits. */
 enum { MAPDIT_INC_IN_16 = 0, MAPDIT_INC_IN_F32 = 1 };
 enum { MAPDIT_INC_OUT_F32 = 0, MAPDIT_INC_OUT_16 = 1 };
 typedef struct {

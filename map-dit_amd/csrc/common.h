@@ -76,6 +76,12 @@ __device__ __forceinline__ float lo16(uint32_t w) { return (float)__builtin_bit_
 __device__ __forceinline__ float hi16(uint32_t w) { return (float)__builtin_bit_cast(f16x2_t, w).y; }       // v_cvt_f32_f16 sdwa WORD_1
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0)
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0)
+// fp32 -> operand format for values that may pass the format's range: fp16 saturates at its largest finite value instead of becoming
+// inf (NaN stays NaN); bf16 has fp32's range
+__device__ __forceinline__ float sat16f(float v) {
+    v = v > 65504.f ? 65504.f : v;
+    return v < -65504.f ? -65504.f : v;
+}
 #else
 __device__ __forceinline__ bf16_t cvt16(float x) { return f2bf(x); }
 __device__ __forceinline__ float up16(bf16_t v) { return bf2f(v); }
@@ -84,7 +90,10 @@ __device__ __forceinline__ float lo16(uint32_t w) { return __uint_as_float(w << 
 __device__ __forceinline__ float hi16(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
+__device__ __forceinline__ float sat16f(float v) { return v; }
 #endif
+__device__ __forceinline__ bf16_t cvt16s(float v) { return cvt16(sat16f(v)); }
+__device__ __forceinline__ uint32_t pack16s(float lo, float hi) { return pack16(sat16f(lo), sat16f(hi)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -169,6 +178,26 @@ int MD_SYM(qkv_split72)(const uint16_t* qkv, int B, int T, int H, uint16_t* qn, 
 int MD_SYM(qkv_merge_bwd72)(const uint16_t* qkv, int B, int T, int H, const uint16_t* dqn, const uint16_t* dkn, const uint16_t* dv,
                            uint16_t* dqkv, void* stream);
 
+// conv.hip -> vae.hip, inception.hip (behind mapdit_vae_conv / mapdit_vae_conv_down / mapdit_inc_conv).  The block is the general
+// form both callers are instances of: output pixel (y, x), tap (ky, kx) reads logical input (y * st + ky - ph, x * st + kx - pw), tested
+// against the logical extent Hb x Wb and stored at (yy >> up2, xx >> up2) of the Hs x Ws source; epilogue acc + bias, + res (the output's
+// layout; may alias out), ReLU, then the store at m * ld + coff + co.  The kinds are mapdit.h's MAPDIT_VAE_IN_* / MAPDIT_VAE_OUT_*.
+typedef struct {
+    const void* in;
+    const bf16_t* w;          // [Cout][kh][kw][Cin]
+    const float* bias;
+    const float* res;         // may be NULL
+    void* out;
+    int in_kind, out_kind;
+    int Hs, Ws, Hb, Wb, up2;
+    int kh, kw, st, ph, pw;
+    int Ho, Wo, Cin, Cout, Ktot;
+    long M;                   // N * Ho * Wo
+    int ld, coff, relu;
+} md_conv_t;
+enum { MD_CONV_PLAIN = 0, MD_CONV_64 = 64, MD_CONV_128 = 128 };      // the tile: one thread per output element, or 128 pixels x 64 / 128 channels on the MFMA
+int MD_SYM(conv_launch)(const char* who, const md_conv_t* p, int tile, void* stream);
+
 // Error plumbing shared by the C-ABI entry points (thread-local last-error string; defined in switches.hip).
 void mapdit_set_error(const char* fmt, ...);
 #define MD_CHECK(cond, ...)                                   \
@@ -187,4 +216,12 @@ void mapdit_set_error(const char* fmt, ...);
         }                                                                     \
     } while (0)
 
+// pass a callee's refusal on
+#define MD_TRY(call)                      \
+    do {                                  \
+        const int rc_ = (call);           \
+        if (rc_ != MAPDIT_OK) return rc_; \
+    } while (0)
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline size_t md_up256(size_t v) { return (v + 255) & ~(size_t)255; }

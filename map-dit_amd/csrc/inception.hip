@@ -3,189 +3,12 @@
 // Activations are 16-bit NHWC between the layers (a convolution rounds its input to the operand format anyway; max pooling commutes
 // with that rounding, the average pool rounds once more); the image at 299 x 299 and the last block's output are fp32.
 //
-// Convolution.  out[m][co] = sum_K A[m][K] * w[co][K] with m = (n, y, x) of the OUTPUT flattened and K = (ky, kx, c) flattened to
-// Ktot = kh * kw * Cin: the weight is a plain row-major [Cout][Ktot] B operand, the A operand is gathered.  Cin is a multiple of 16 and
-// of nothing larger (48, 80, 288 ...), so K is staged in GRANULES of 16 channels: a granule lies inside one tap (one bounds decision,
-// two 16-byte loads), a 64-wide K tile is four granules that may belong to different taps, and the granules of the last tile past
-// Ktot are zeros on both operands.  A workgroup (4 waves) owns 128 output pixels x 64 output channels, each wave 32 x 64 (2 x 4 tiles of
-// v_mfma_f32_16x16x32); rows past M and weight rows past Cout (a multiple of 16, not of 64) stage zeros without forming an address,
-// and the epilogue skips them.  A tile of 128 consecutive m straddles image rows and samples: each staged row derives (n, y, x) from
-// its own m.  The K order of an output element is the tile order and the MFMA's own: it does not depend on where the pixel falls in a
-// tile or on N, so an image alone and in a batch gives the same bits.
+// Convolution: conv.hip's kernels (common.h, md_conv_t) with kh x kw taps, stride, pad_h / pad_w, ReLU and a store into a channel
+// slice.  Cin is a multiple of 16 and of nothing larger (48, 80, 288 ...) and Cout a multiple of 16, not of 64: the 16-channel K
+// granules and the row / column guards of the 64-wide tile are what these layers need.
 #include "common.h"
 
 MD_NS_OPEN
-
-// fp32 -> operand format; fp16 saturates at its largest finite value instead of becoming inf (NaN stays NaN)
-__device__ __forceinline__ float inc_sat(float v) {
-#if MAPDIT_DT == 1
-    v = v > 65504.f ? 65504.f : v;
-    v = v < -65504.f ? -65504.f : v;
-#endif
-    return v;
-}
-__device__ __forceinline__ bf16_t inc_cvt(float v) { return cvt16(inc_sat(v)); }
-
-struct IncConvP {
-    const void* in;
-    const bf16_t* w;
-    const float* bias;
-    void* out;
-    int Hin, Win, Cin, Cout, kh, kw, st, ph, pw, Ho, Wo, ld, coff, relu, Ktot;
-    long M;
-};
-
-constexpr int IBM = 128, IBN = 64, IBK = 64, ILD = IBK + 8;      // LDS rows of 144 B: 16-byte aligned, consecutive rows 4 banks apart
-
-template <int OUT16> __global__ __launch_bounds__(256) void inc_conv_mfma_kernel(const IncConvP p) {
-    __shared__ __attribute__((aligned(16))) bf16_t As[2][IBM * ILD];
-    __shared__ __attribute__((aligned(16))) bf16_t Bs[2][IBN * ILD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const long m0 = (long)blockIdx.x * IBM;
-    const int co0 = blockIdx.y * IBN, wr0 = wave * 32;
-    const int Hin = p.Hin, Win = p.Win, Cin = p.Cin, kw = p.kw, Ktot = p.Ktot;
-    const int nk = (Ktot + IBK - 1) / IBK;
-
-    // staging role: rows srow and srow + 64 of the A tile, row srow of the B tile, the granule at kq of every K tile
-    const int srow = tid >> 2, kq = (tid & 3) * 16;
-    int pn[2], py[2], px[2];
-    bool pv[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const long m = m0 + srow + 64 * t;
-        pv[t] = m < p.M;
-        const long mm = pv[t] ? m : 0;
-        const int hw = p.Ho * p.Wo;
-        pn[t] = (int)(mm / hw);
-        const int rem = (int)(mm % hw);
-        py[t] = (rem / p.Wo) * p.st - p.ph;               // the input row / column of tap (0, 0)
-        px[t] = (rem % p.Wo) * p.st - p.pw;
-    }
-    const bool bv = co0 + srow < p.Cout;
-    const bf16_t* wrow = p.w + (size_t)(bv ? co0 + srow : 0) * Ktot;
-
-    uint4 ra[2][2], rb[2];
-    auto fetch = [&](int kt) {
-        const int k0 = kt * IBK + kq;
-        const bool kv = k0 < Ktot;                         // (Ktot % 16 == 0: a granule is inside K or past it, never across)
-        const int tap = kv ? k0 / Cin : 0, c0 = kv ? k0 - tap * Cin : 0;
-        const int ky = tap / kw, kx = tap - ky * kw;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int yy = py[t] + ky, xx = px[t] + kx;
-            ra[t][0] = uint4{0u, 0u, 0u, 0u};
-            ra[t][1] = uint4{0u, 0u, 0u, 0u};
-            if (kv && pv[t] && yy >= 0 && yy < Hin && xx >= 0 && xx < Win) {
-                const uint4* s = (const uint4*)((const bf16_t*)p.in + (((size_t)pn[t] * Hin + yy) * Win + xx) * Cin + c0);
-                ra[t][0] = s[0];
-                ra[t][1] = s[1];
-            }
-        }
-        rb[0] = uint4{0u, 0u, 0u, 0u};
-        rb[1] = uint4{0u, 0u, 0u, 0u};
-        if (kv && bv) {
-            const uint4* s = (const uint4*)(wrow + k0);
-            rb[0] = s[0];
-            rb[1] = s[1];
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            uint4* d = (uint4*)(&As[buf][(srow + 64 * t) * ILD + kq]);
-            d[0] = ra[t][0];
-            d[1] = ra[t][1];
-        }
-        uint4* d = (uint4*)(&Bs[buf][srow * ILD + kq]);
-        d[0] = rb[0];
-        d[1] = rb[1];
-    };
-
-    f32x4_t acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) fetch(kt + 1);
-#pragma unroll
-        for (int ks = 0; ks < IBK / 32; ++ks) {
-            bf16x8_t a[2], b[4];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = *(const bf16x8_t*)(&As[buf][(wr0 + i * 16 + r) * ILD + ks * 32 + q * 8]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *(const bf16x8_t*)(&Bs[buf][(j * 16 + r) * ILD + ks * 32 + q * 8]);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(a[i], b[j], acc[i][j]);
-        }
-        // the other buffer was last read by the compute of K tile kt - 1, which every wave left before the previous barrier
-        if (kt + 1 < nk) stash(buf ^ 1);
-        __syncthreads();
-    }
-
-    // accumulator element e of a lane: pixel row 4 q + e of the 16 x 16 tile, output channel r
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int co = co0 + j * 16 + r;
-        if (co >= p.Cout) continue;
-        const float bvv = p.bias[co];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const long m = m0 + wr0 + i * 16 + q * 4 + e;
-                if (m >= p.M) continue;
-                const size_t o = (size_t)m * p.ld + p.coff + co;
-                float v = acc[i][j][e] + bvv;
-                if (p.relu) v = v > 0.f ? v : 0.f;
-                if constexpr (OUT16) ((bf16_t*)p.out)[o] = inc_cvt(v);
-                else ((float*)p.out)[o] = v;
-            }
-    }
-}
-
-// Every other shape (the first layer: Cin = 3, K = 27, fp32 input) and every misaligned operand: one thread per output element, the
-// same operand rounding, a serial fp32 sum in (ky, kx, c) order.
-__global__ __launch_bounds__(256) void inc_conv_plain_kernel(const IncConvP p, int in_f32, int out16) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.M * p.Cout) return;
-    const int co = (int)(idx % p.Cout);
-    const long m = idx / p.Cout;
-    const int hw = p.Ho * p.Wo;
-    const int n = (int)(m / hw), rem = (int)(m % hw), y = rem / p.Wo, x = rem % p.Wo;
-    const bf16_t* wr = p.w + (size_t)co * p.Ktot;
-    float acc = 0.f;
-    for (int ky = 0; ky < p.kh; ++ky) {
-        const int yy = y * p.st + ky - p.ph;
-        if (yy < 0 || yy >= p.Hin) continue;
-        for (int kx = 0; kx < p.kw; ++kx) {
-            const int xx = x * p.st + kx - p.pw;
-            if (xx < 0 || xx >= p.Win) continue;
-            const bf16_t* wt = wr + (size_t)(ky * p.kw + kx) * p.Cin;
-            const size_t e0 = (((size_t)n * p.Hin + yy) * p.Win + xx) * p.Cin;
-            if (in_f32) {
-                const float* ip = (const float*)p.in + e0;
-                for (int c = 0; c < p.Cin; ++c) acc = fmaf(up16(inc_cvt(ip[c])), up16(wt[c]), acc);
-            } else {
-                const bf16_t* ip = (const bf16_t*)p.in + e0;
-                for (int c = 0; c < p.Cin; ++c) acc = fmaf(up16(ip[c]), up16(wt[c]), acc);
-            }
-        }
-    }
-    float v = acc + p.bias[co];
-    if (p.relu) v = v > 0.f ? v : 0.f;
-    const size_t o = (size_t)m * p.ld + p.coff + co;
-    if (out16) ((bf16_t*)p.out)[o] = inc_cvt(v);
-    else ((float*)p.out)[o] = v;
-}
 
 // ---- pooling ----------------------------------------------------------------------------------------------------------------------
 // The three 3 x 3 forms, one thread per output element, taps in (ky, kx) order over the in-image taps only: the stride-2 maximum
@@ -219,7 +42,7 @@ __global__ __launch_bounds__(256) void inc_pool_kernel(const void* __restrict__ 
     }
     if (avg) a = a / (float)cnt;
     const size_t o = (size_t)m * ld + coff + c;
-    if (out16) ((bf16_t*)out)[o] = inc_cvt(a);
+    if (out16) ((bf16_t*)out)[o] = cvt16s(a);
     else ((float*)out)[o] = a;
 }
 
@@ -307,12 +130,6 @@ __global__ __launch_bounds__(256) void inc_stats_sum_kernel(const float* __restr
 
 MD_NS_CLOSE
 
-#define INC_TRY(call)                     \
-    do {                                  \
-        const int rc_ = (call);           \
-        if (rc_ != MAPDIT_OK) return rc_; \
-    } while (0)
-
 // ---- entry points -----------------------------------------------------------------------------------------------------------------
 extern "C" int MD_SYM(inc_conv)(const mapdit_inc_conv_t* a, void* stream) {
     MD_CHECK(a && a->in && a->w && a->bias && a->out, "inc_conv: null argument");
@@ -333,20 +150,13 @@ extern "C" int MD_SYM(inc_conv)(const mapdit_inc_conv_t* a, void* stream) {
     MD_CHECK(M < (1L << 31) && (long)a->N * a->Hin * a->Win < (1L << 31) && M * a->ld_out < (1L << 40), "inc_conv: %ld output pixels are too many", M);
     const long Ktot = (long)a->kh * a->kw * a->Cin;
     MD_CHECK(Ktot < (1L << 24), "inc_conv: K = %ld is too long", Ktot);
-    hipStream_t st = (hipStream_t)stream;
-    const IncConvP p{a->in, (const bf16_t*)a->w, a->bias, a->out, a->Hin, a->Win, a->Cin, a->Cout, a->kh, a->kw, a->stride, a->pad_h, a->pad_w,
-                     Ho, Wo, a->ld_out, a->c_off, a->relu ? 1 : 0, (int)Ktot, M};
+    // stride and padding as given, the extent and the source are the input; the kinds share the VAE's values but for the 16-bit store
+    const md_conv_t p{a->in, (const bf16_t*)a->w, a->bias, nullptr, a->out, a->in_kind, a->out_kind == MAPDIT_INC_OUT_16 ? MAPDIT_VAE_OUT_16 : MAPDIT_VAE_OUT_F32,
+                      a->Hin, a->Win, a->Hin, a->Win, 0, a->kh, a->kw, a->stride, a->pad_h, a->pad_w, Ho, Wo, a->Cin, a->Cout, (int)Ktot, M,
+                      a->ld_out, a->c_off, a->relu ? 1 : 0};
     const bool aligned = !(((uintptr_t)a->in | (uintptr_t)a->w) & 15);
-    if (a->in_kind == MAPDIT_INC_IN_16 && a->Cin % 16 == 0 && a->Cout % 16 == 0 && aligned) {
-        const dim3 grid((unsigned)cdiv(M, IBM), (unsigned)cdiv(a->Cout, IBN));
-        if (a->out_kind == MAPDIT_INC_OUT_16) inc_conv_mfma_kernel<1><<<grid, 256, 0, st>>>(p);
-        else inc_conv_mfma_kernel<0><<<grid, 256, 0, st>>>(p);
-    } else {
-        MD_CHECK(M * a->Cout < (1L << 38), "inc_conv: %ld x %d outputs are too many for the plain kernel", M, a->Cout);
-        inc_conv_plain_kernel<<<cdiv(M * a->Cout, 256), 256, 0, st>>>(p, a->in_kind == MAPDIT_INC_IN_F32, a->out_kind == MAPDIT_INC_OUT_16);
-    }
-    MD_LAUNCH_CHECK();
-    return MAPDIT_OK;
+    const bool mfma = a->in_kind == MAPDIT_INC_IN_16 && a->Cin % 16 == 0 && a->Cout % 16 == 0 && aligned;
+    return MD_SYM(conv_launch)("inc_conv", &p, mfma ? MD_CONV_64 : MD_CONV_PLAIN, stream);
 }
 
 extern "C" int MD_SYM(inc_pool)(const void* in, int in_kind, void* out, int out_kind, int N, int H, int W, int C, int mode, int ld_out, int c_off,
@@ -417,8 +227,6 @@ extern "C" int mapdit_inc_stats_accumulate(const float* feat, int N, int D, doub
 // max-pool branches of Mixed_6a / 7a, write their channel slice of it), T1 / T2 the branches' temporaries; all 16-bit NHWC of maxE
 // elements.  IMG: the fp32 image at size x size; FIN: the last block's fp32 output.
 namespace {
-inline size_t inc_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct IncLayer {
     int cin, cout, kh, kw, st;
 };
@@ -475,14 +283,14 @@ struct IncWalk {
     // Mixed_5b / 5c / 5d
     int block_a(int H, int W, int cin, int pw_) {
         const int ld = 224 + pw_;
-        INC_TRY(c16(X, H, W, cin, 64, 1, 1, 1, 0, 0, Y, ld, 0));
-        INC_TRY(c16(X, H, W, cin, 48, 1, 1, 1, 0, 0, T1, 48, 0));
-        INC_TRY(c16(T1, H, W, 48, 64, 5, 5, 1, 2, 2, Y, ld, 64));
-        INC_TRY(c16(X, H, W, cin, 64, 1, 1, 1, 0, 0, T1, 64, 0));
-        INC_TRY(c16(T1, H, W, 64, 96, 3, 3, 1, 1, 1, T2, 96, 0));
-        INC_TRY(c16(T2, H, W, 96, 96, 3, 3, 1, 1, 1, Y, ld, 128));
-        INC_TRY(pool(X, H, W, cin, MAPDIT_INC_POOL_AVG, T1, cin, 0));
-        INC_TRY(c16(T1, H, W, cin, pw_, 1, 1, 1, 0, 0, Y, ld, 224));
+        MD_TRY(c16(X, H, W, cin, 64, 1, 1, 1, 0, 0, Y, ld, 0));
+        MD_TRY(c16(X, H, W, cin, 48, 1, 1, 1, 0, 0, T1, 48, 0));
+        MD_TRY(c16(T1, H, W, 48, 64, 5, 5, 1, 2, 2, Y, ld, 64));
+        MD_TRY(c16(X, H, W, cin, 64, 1, 1, 1, 0, 0, T1, 64, 0));
+        MD_TRY(c16(T1, H, W, 64, 96, 3, 3, 1, 1, 1, T2, 96, 0));
+        MD_TRY(c16(T2, H, W, 96, 96, 3, 3, 1, 1, 1, Y, ld, 128));
+        MD_TRY(pool(X, H, W, cin, MAPDIT_INC_POOL_AVG, T1, cin, 0));
+        MD_TRY(c16(T1, H, W, cin, pw_, 1, 1, 1, 0, 0, Y, ld, 224));
         swap_xy();
         return MAPDIT_OK;
     }
@@ -490,11 +298,11 @@ struct IncWalk {
     int block_b(int* H, int* W) {
         const int h = *H, w = *W, cin = 288, ld = 768;
         MD_CHECK(h >= 3 && w >= 3, "inception: the image size is too small: Mixed_6a meets a %d x %d input", h, w);
-        INC_TRY(c16(X, h, w, cin, 384, 3, 3, 2, 0, 0, Y, ld, 0));
-        INC_TRY(c16(X, h, w, cin, 64, 1, 1, 1, 0, 0, T1, 64, 0));
-        INC_TRY(c16(T1, h, w, 64, 96, 3, 3, 1, 1, 1, T2, 96, 0));
-        INC_TRY(c16(T2, h, w, 96, 96, 3, 3, 2, 0, 0, Y, ld, 384));
-        INC_TRY(pool(X, h, w, cin, MAPDIT_INC_POOL_MAX_S2, Y, ld, 480));
+        MD_TRY(c16(X, h, w, cin, 384, 3, 3, 2, 0, 0, Y, ld, 0));
+        MD_TRY(c16(X, h, w, cin, 64, 1, 1, 1, 0, 0, T1, 64, 0));
+        MD_TRY(c16(T1, h, w, 64, 96, 3, 3, 1, 1, 1, T2, 96, 0));
+        MD_TRY(c16(T2, h, w, 96, 96, 3, 3, 2, 0, 0, Y, ld, 384));
+        MD_TRY(pool(X, h, w, cin, MAPDIT_INC_POOL_MAX_S2, Y, ld, 480));
         *H = (h - 3) / 2 + 1;
         *W = (w - 3) / 2 + 1;
         swap_xy();
@@ -503,17 +311,17 @@ struct IncWalk {
     // Mixed_6b .. 6e
     int block_c(int H, int W, int c7) {
         const int cin = 768, ld = 768;
-        INC_TRY(c16(X, H, W, cin, 192, 1, 1, 1, 0, 0, Y, ld, 0));
-        INC_TRY(c16(X, H, W, cin, c7, 1, 1, 1, 0, 0, T1, c7, 0));
-        INC_TRY(c16(T1, H, W, c7, c7, 1, 7, 1, 0, 3, T2, c7, 0));
-        INC_TRY(c16(T2, H, W, c7, 192, 7, 1, 1, 3, 0, Y, ld, 192));
-        INC_TRY(c16(X, H, W, cin, c7, 1, 1, 1, 0, 0, T1, c7, 0));
-        INC_TRY(c16(T1, H, W, c7, c7, 7, 1, 1, 3, 0, T2, c7, 0));
-        INC_TRY(c16(T2, H, W, c7, c7, 1, 7, 1, 0, 3, T1, c7, 0));
-        INC_TRY(c16(T1, H, W, c7, c7, 7, 1, 1, 3, 0, T2, c7, 0));
-        INC_TRY(c16(T2, H, W, c7, 192, 1, 7, 1, 0, 3, Y, ld, 384));
-        INC_TRY(pool(X, H, W, cin, MAPDIT_INC_POOL_AVG, T1, cin, 0));
-        INC_TRY(c16(T1, H, W, cin, 192, 1, 1, 1, 0, 0, Y, ld, 576));
+        MD_TRY(c16(X, H, W, cin, 192, 1, 1, 1, 0, 0, Y, ld, 0));
+        MD_TRY(c16(X, H, W, cin, c7, 1, 1, 1, 0, 0, T1, c7, 0));
+        MD_TRY(c16(T1, H, W, c7, c7, 1, 7, 1, 0, 3, T2, c7, 0));
+        MD_TRY(c16(T2, H, W, c7, 192, 7, 1, 1, 3, 0, Y, ld, 192));
+        MD_TRY(c16(X, H, W, cin, c7, 1, 1, 1, 0, 0, T1, c7, 0));
+        MD_TRY(c16(T1, H, W, c7, c7, 7, 1, 1, 3, 0, T2, c7, 0));
+        MD_TRY(c16(T2, H, W, c7, c7, 1, 7, 1, 0, 3, T1, c7, 0));
+        MD_TRY(c16(T1, H, W, c7, c7, 7, 1, 1, 3, 0, T2, c7, 0));
+        MD_TRY(c16(T2, H, W, c7, 192, 1, 7, 1, 0, 3, Y, ld, 384));
+        MD_TRY(pool(X, H, W, cin, MAPDIT_INC_POOL_AVG, T1, cin, 0));
+        MD_TRY(c16(T1, H, W, cin, 192, 1, 1, 1, 0, 0, Y, ld, 576));
         swap_xy();
         return MAPDIT_OK;
     }
@@ -521,13 +329,13 @@ struct IncWalk {
     int block_d(int* H, int* W) {
         const int h = *H, w = *W, cin = 768, ld = 1280;
         MD_CHECK(h >= 3 && w >= 3, "inception: the image size is too small: Mixed_7a meets a %d x %d input", h, w);
-        INC_TRY(c16(X, h, w, cin, 192, 1, 1, 1, 0, 0, T1, 192, 0));
-        INC_TRY(c16(T1, h, w, 192, 320, 3, 3, 2, 0, 0, Y, ld, 0));
-        INC_TRY(c16(X, h, w, cin, 192, 1, 1, 1, 0, 0, T1, 192, 0));
-        INC_TRY(c16(T1, h, w, 192, 192, 1, 7, 1, 0, 3, T2, 192, 0));
-        INC_TRY(c16(T2, h, w, 192, 192, 7, 1, 1, 3, 0, T1, 192, 0));
-        INC_TRY(c16(T1, h, w, 192, 192, 3, 3, 2, 0, 0, Y, ld, 320));
-        INC_TRY(pool(X, h, w, cin, MAPDIT_INC_POOL_MAX_S2, Y, ld, 512));
+        MD_TRY(c16(X, h, w, cin, 192, 1, 1, 1, 0, 0, T1, 192, 0));
+        MD_TRY(c16(T1, h, w, 192, 320, 3, 3, 2, 0, 0, Y, ld, 0));
+        MD_TRY(c16(X, h, w, cin, 192, 1, 1, 1, 0, 0, T1, 192, 0));
+        MD_TRY(c16(T1, h, w, 192, 192, 1, 7, 1, 0, 3, T2, 192, 0));
+        MD_TRY(c16(T2, h, w, 192, 192, 7, 1, 1, 3, 0, T1, 192, 0));
+        MD_TRY(c16(T1, h, w, 192, 192, 3, 3, 2, 0, 0, Y, ld, 320));
+        MD_TRY(pool(X, h, w, cin, MAPDIT_INC_POOL_MAX_S2, Y, ld, 512));
         *H = (h - 3) / 2 + 1;
         *W = (w - 3) / 2 + 1;
         swap_xy();
@@ -538,16 +346,16 @@ struct IncWalk {
         const int ld = 2048, ok = last ? MAPDIT_INC_OUT_F32 : MAPDIT_INC_OUT_16;
         void* O = last ? (void*)FIN : (void*)Y;
         const int k16 = MAPDIT_INC_IN_16;
-        INC_TRY(conv(X, k16, H, W, cin, 320, 1, 1, 1, 0, 0, O, ok, ld, 0, nullptr, nullptr));
-        INC_TRY(c16(X, H, W, cin, 384, 1, 1, 1, 0, 0, T1, 384, 0));
-        INC_TRY(conv(T1, k16, H, W, 384, 384, 1, 3, 1, 0, 1, O, ok, ld, 320, nullptr, nullptr));
-        INC_TRY(conv(T1, k16, H, W, 384, 384, 3, 1, 1, 1, 0, O, ok, ld, 704, nullptr, nullptr));
-        INC_TRY(c16(X, H, W, cin, 448, 1, 1, 1, 0, 0, T1, 448, 0));
-        INC_TRY(c16(T1, H, W, 448, 384, 3, 3, 1, 1, 1, T2, 384, 0));
-        INC_TRY(conv(T2, k16, H, W, 384, 384, 1, 3, 1, 0, 1, O, ok, ld, 1088, nullptr, nullptr));
-        INC_TRY(conv(T2, k16, H, W, 384, 384, 3, 1, 1, 1, 0, O, ok, ld, 1472, nullptr, nullptr));
-        INC_TRY(pool(X, H, W, cin, pool_mode, T1, cin, 0));
-        INC_TRY(conv(T1, k16, H, W, cin, 192, 1, 1, 1, 0, 0, O, ok, ld, 1856, nullptr, nullptr));
+        MD_TRY(conv(X, k16, H, W, cin, 320, 1, 1, 1, 0, 0, O, ok, ld, 0, nullptr, nullptr));
+        MD_TRY(c16(X, H, W, cin, 384, 1, 1, 1, 0, 0, T1, 384, 0));
+        MD_TRY(conv(T1, k16, H, W, 384, 384, 1, 3, 1, 0, 1, O, ok, ld, 320, nullptr, nullptr));
+        MD_TRY(conv(T1, k16, H, W, 384, 384, 3, 1, 1, 1, 0, O, ok, ld, 704, nullptr, nullptr));
+        MD_TRY(c16(X, H, W, cin, 448, 1, 1, 1, 0, 0, T1, 448, 0));
+        MD_TRY(c16(T1, H, W, 448, 384, 3, 3, 1, 1, 1, T2, 384, 0));
+        MD_TRY(conv(T2, k16, H, W, 384, 384, 1, 3, 1, 0, 1, O, ok, ld, 1088, nullptr, nullptr));
+        MD_TRY(conv(T2, k16, H, W, 384, 384, 3, 1, 1, 1, 0, O, ok, ld, 1472, nullptr, nullptr));
+        MD_TRY(pool(X, H, W, cin, pool_mode, T1, cin, 0));
+        MD_TRY(conv(T1, k16, H, W, cin, 192, 1, 1, 1, 0, 0, O, ok, ld, 1856, nullptr, nullptr));
         if (!last) swap_xy();
         return MAPDIT_OK;
     }
@@ -557,28 +365,28 @@ struct IncWalk {
         int H = S, W = S;
         li = 0;
         maxE = finE = 0;
-        INC_TRY(conv(IMG, MAPDIT_INC_IN_F32, H, W, 3, 32, 3, 3, 2, 0, 0, X, MAPDIT_INC_OUT_16, 32, 0, &H, &W));        // Conv2d_1a_3x3
-        INC_TRY(conv(X, MAPDIT_INC_IN_16, H, W, 32, 32, 3, 3, 1, 0, 0, Y, MAPDIT_INC_OUT_16, 32, 0, &H, &W));          // Conv2d_2a_3x3
-        INC_TRY(c16(Y, H, W, 32, 64, 3, 3, 1, 1, 1, X, 64, 0));                                                        // Conv2d_2b_3x3
-        INC_TRY(pool(X, H, W, 64, MAPDIT_INC_POOL_MAX_S2, Y, 64, 0));
+        MD_TRY(conv(IMG, MAPDIT_INC_IN_F32, H, W, 3, 32, 3, 3, 2, 0, 0, X, MAPDIT_INC_OUT_16, 32, 0, &H, &W));        // Conv2d_1a_3x3
+        MD_TRY(conv(X, MAPDIT_INC_IN_16, H, W, 32, 32, 3, 3, 1, 0, 0, Y, MAPDIT_INC_OUT_16, 32, 0, &H, &W));          // Conv2d_2a_3x3
+        MD_TRY(c16(Y, H, W, 32, 64, 3, 3, 1, 1, 1, X, 64, 0));                                                        // Conv2d_2b_3x3
+        MD_TRY(pool(X, H, W, 64, MAPDIT_INC_POOL_MAX_S2, Y, 64, 0));
         H = (H - 3) / 2 + 1;
         W = (W - 3) / 2 + 1;
-        INC_TRY(c16(Y, H, W, 64, 80, 1, 1, 1, 0, 0, X, 80, 0));                                                        // Conv2d_3b_1x1
-        INC_TRY(conv(X, MAPDIT_INC_IN_16, H, W, 80, 192, 3, 3, 1, 0, 0, Y, MAPDIT_INC_OUT_16, 192, 0, &H, &W));        // Conv2d_4a_3x3
-        INC_TRY(pool(Y, H, W, 192, MAPDIT_INC_POOL_MAX_S2, X, 192, 0));
+        MD_TRY(c16(Y, H, W, 64, 80, 1, 1, 1, 0, 0, X, 80, 0));                                                        // Conv2d_3b_1x1
+        MD_TRY(conv(X, MAPDIT_INC_IN_16, H, W, 80, 192, 3, 3, 1, 0, 0, Y, MAPDIT_INC_OUT_16, 192, 0, &H, &W));        // Conv2d_4a_3x3
+        MD_TRY(pool(Y, H, W, 192, MAPDIT_INC_POOL_MAX_S2, X, 192, 0));
         H = (H - 3) / 2 + 1;
         W = (W - 3) / 2 + 1;
-        INC_TRY(block_a(H, W, 192, 32));
-        INC_TRY(block_a(H, W, 256, 64));
-        INC_TRY(block_a(H, W, 288, 64));
-        INC_TRY(block_b(&H, &W));
-        INC_TRY(block_c(H, W, 128));
-        INC_TRY(block_c(H, W, 160));
-        INC_TRY(block_c(H, W, 160));
-        INC_TRY(block_c(H, W, 192));
-        INC_TRY(block_d(&H, &W));
-        INC_TRY(block_e(H, W, 1280, MAPDIT_INC_POOL_AVG, false));
-        INC_TRY(block_e(H, W, 2048, MAPDIT_INC_POOL_MAX_S1, true));
+        MD_TRY(block_a(H, W, 192, 32));
+        MD_TRY(block_a(H, W, 256, 64));
+        MD_TRY(block_a(H, W, 288, 64));
+        MD_TRY(block_b(&H, &W));
+        MD_TRY(block_c(H, W, 128));
+        MD_TRY(block_c(H, W, 160));
+        MD_TRY(block_c(H, W, 160));
+        MD_TRY(block_c(H, W, 192));
+        MD_TRY(block_d(&H, &W));
+        MD_TRY(block_e(H, W, 1280, MAPDIT_INC_POOL_AVG, false));
+        MD_TRY(block_e(H, W, 2048, MAPDIT_INC_POOL_MAX_S1, true));
         MD_CHECK(li == MAPDIT_INC_NUM_CONV, "inception: %d convolutions walked, %d declared", li, MAPDIT_INC_NUM_CONV);
         *Hf = H;
         *Wf = W;
@@ -600,14 +408,14 @@ int inc_plan(const mapdit_inc_config_t* cfg, int N, IncWalk* wk, IncPlan* pl) {
     *wk = IncWalk{};
     wk->dry = true;
     wk->N = N;
-    INC_TRY(wk->run(cfg->image_size, &pl->Hf, &pl->Wf));
+    MD_TRY(wk->run(cfg->image_size, &pl->Hf, &pl->Wf));
     size_t o = 0;
-    pl->off_img = o; o += inc_up256((size_t)N * cfg->image_size * cfg->image_size * 3 * 4);
-    pl->off_fin = o; o += inc_up256(wk->finE * 4);
-    pl->off_x = o; o += inc_up256(wk->maxE * 2);
-    pl->off_y = o; o += inc_up256(wk->maxE * 2);
-    pl->off_t1 = o; o += inc_up256(wk->maxE * 2);
-    pl->off_t2 = o; o += inc_up256(wk->maxE * 2);
+    pl->off_img = o; o += md_up256((size_t)N * cfg->image_size * cfg->image_size * 3 * 4);
+    pl->off_fin = o; o += md_up256(wk->finE * 4);
+    pl->off_x = o; o += md_up256(wk->maxE * 2);
+    pl->off_y = o; o += md_up256(wk->maxE * 2);
+    pl->off_t1 = o; o += md_up256(wk->maxE * 2);
+    pl->off_t2 = o; o += md_up256(wk->maxE * 2);
     pl->total = o;
     return MAPDIT_OK;
 }
@@ -626,7 +434,7 @@ extern "C" int mapdit_inc_layer_shape(int index, int* cin, int* cout, int* kh, i
     const mapdit_inc_config_t cfg{299};
     IncWalk wk;
     IncPlan pl;
-    INC_TRY(inc_plan(&cfg, 1, &wk, &pl));
+    MD_TRY(inc_plan(&cfg, 1, &wk, &pl));
     const IncLayer& l = wk.layers[index];
     *cin = l.cin;
     *cout = l.cout;
@@ -641,7 +449,7 @@ extern "C" int MD_SYM(inc_features)(const mapdit_inc_config_t* cfg, const void* 
                                     float* feat, void* workspace, size_t ws_bytes, void* stream) {
     IncWalk wk;
     IncPlan pl;
-    INC_TRY(inc_plan(cfg, N, &wk, &pl));
+    MD_TRY(inc_plan(cfg, N, &wk, &pl));
     MD_CHECK(wt && images && feat && workspace, "inc_features: null argument");
     MD_CHECK(img_kind == MAPDIT_INC_IMG_U8_NHWC || img_kind == MAPDIT_INC_IMG_F32_NCHW, "inc_features: bad img_kind %d", img_kind);
     MD_CHECK(H >= 8 && W >= 8, "inc_features: images of %d x %d (8 x 8 at the least)", H, W);
@@ -661,9 +469,9 @@ extern "C" int MD_SYM(inc_features)(const mapdit_inc_config_t* cfg, const void* 
     wk.T1 = (uint16_t*)(ws + pl.off_t1);
     wk.T2 = (uint16_t*)(ws + pl.off_t2);
     const int S = cfg->image_size;
-    if (img_kind == MAPDIT_INC_IMG_U8_NHWC) INC_TRY(mapdit_inc_resize_u8((const uint8_t*)images, wk.IMG, N, H, W, 3, S, stream));
-    else INC_TRY(mapdit_inc_resize_f32((const float*)images, wk.IMG, N, H, W, 3, S, stream));
+    if (img_kind == MAPDIT_INC_IMG_U8_NHWC) MD_TRY(mapdit_inc_resize_u8((const uint8_t*)images, wk.IMG, N, H, W, 3, S, stream));
+    else MD_TRY(mapdit_inc_resize_f32((const float*)images, wk.IMG, N, H, W, 3, S, stream));
     int Hf = 0, Wf = 0;
-    INC_TRY(wk.run(S, &Hf, &Wf));
+    MD_TRY(wk.run(S, &Hf, &Wf));
     return MD_SYM(inc_global_avg)(wk.FIN, MAPDIT_INC_IN_F32, feat, N, Hf * Wf, 2048, stream);
 }

@@ -1,235 +1,14 @@
-// VAE (AutoencoderKL layout), both directions: convolution as an implicit GEMM on the MFMA, GroupNorm(+SiLU) over NHWC, a row softmax,
-// the encoder's pointwise kernels (image preparation, posterior head, latent statistics) and the two host plans that sequence a decode
-// or an encode on one stream (mapdit.h, "VAE").  Built once per 16-bit operand format (csrc/Makefile).
+// VAE (AutoencoderKL layout), both directions: GroupNorm(+SiLU) over NHWC, a row softmax, the encoder's pointwise kernels (image
+// preparation, posterior head, latent statistics), the convolution entry points and the two host plans that sequence a decode or an
+// encode on one stream (mapdit.h, "VAE").  Built once per 16-bit operand format (csrc/Makefile).
 //
-// Convolution.  out[m][co] = sum_K A[m][K] * w[co][K] with m = (n, y, x) flattened and K = (ky, kx, c): the weight is a plain row-major
-// [Cout][k*k*Cin] B operand, the A operand is gathered.  A workgroup (4 waves) owns 128 pixels x 64 or 128 output channels; a K tile is 64
-// channels of ONE tap (Cin % 64 == 0), so a thread's 16 staged channels share one (ky, kx) and one bounds decision.  A tile of 128
-// consecutive m straddles image rows and, for small images, samples: each staged row derives (n, y, x) from its own m once and
-// tests y + ky - pad, x + kx - pad against the image - never the flat index.  An out-of-image tap (or a row past M) stages zeros
-// without forming its address.  Global -> registers -> LDS -> v_mfma_f32_16x16x32 (the two tile forms: at the kernel).  LDS rows are
-// padded to 72 elements (144 B: 16-byte aligned, consecutive rows 4 banks apart).
-// The K order of every output element is fixed and does not depend on where its pixel falls in a tile: a sample decoded alone and
-// in a batch gives the same bits.
-// One coordinate map serves the three forms: output pixel (y, x), tap (ky, kx) reads logical input (y * st + ky - pad, x * st + kx - pad),
-// tested against the logical extent (Hb, Wb), and stored at (yy >> up2, xx >> up2) of a [N, Hs, Ws, Cin] source.  "Same" convolution:
-// st = 1, pad = k / 2, extent = the output size.  up2: the extent is the upsampled size, the source half of it.  Stride-2 downsample
-// (F.pad(x, (0, 1, 0, 1)) + a 3 x 3 convolution of stride 2 without padding): st = 2, pad = 0, extent = source = (Hin, Win) - the pad row
-// and column are the taps at 2 y + ky == Hin, 2 x + kx == Win, zeros that are never loaded; nothing is added at the top or left.
+// Convolution: conv.hip's kernels behind one coordinate map (common.h, md_conv_t).  "Same" convolution: st = 1, pad = k / 2, extent =
+// the output size.  up2: the extent is the upsampled size, the source half of it.  Stride-2 downsample (F.pad(x, (0, 1, 0, 1)) + a 3 x 3
+// convolution of stride 2 without padding): st = 2, pad = 0, extent = source = (Hin, Win) - the pad row and column are the taps at
+// 2 y + ky == Hin, 2 x + kx == Win, zeros that are never loaded; nothing is added at the top or left.
 #include "common.h"
 
 MD_NS_OPEN
-
-// fp32 -> operand format; fp16 saturates at its largest finite value instead of becoming inf (NaN stays NaN)
-__device__ __forceinline__ float sat16f(float v) {
-#if MAPDIT_DT == 1
-    v = v > 65504.f ? 65504.f : v;
-    v = v < -65504.f ? -65504.f : v;
-#endif
-    return v;
-}
-__device__ __forceinline__ bf16_t cvt16s(float v) { return cvt16(sat16f(v)); }
-__device__ __forceinline__ uint32_t pack16s(float lo, float hi) { return pack16(sat16f(lo), sat16f(hi)); }
-
-struct ConvP {
-    const void* in;
-    const bf16_t* w;
-    const float* bias;
-    const float* res;
-    void* out;
-    int N, H, W, Cin, Cout, k, up2;
-    long M;
-    int st, pad, Hb, Wb, Hs, Ws;      // the coordinate map (above)
-};
-
-constexpr int CBM = 128, CBK = 64, CLD = CBK + 8;
-
-// 16 consecutive channels of one input pixel as 16-bit operands (8 packed words)
-template <int IN_F32> __device__ __forceinline__ void load16(const void* in, size_t elem, uint4& lo, uint4& hi) {
-    if constexpr (IN_F32) {
-        const float4* p = (const float4*)((const float*)in + elem);
-        const float4 a = p[0], b = p[1], c = p[2], d = p[3];
-        lo = uint4{pack16s(a.x, a.y), pack16s(a.z, a.w), pack16s(b.x, b.y), pack16s(b.z, b.w)};
-        hi = uint4{pack16s(c.x, c.y), pack16s(c.z, c.w), pack16s(d.x, d.y), pack16s(d.z, d.w)};
-    } else {
-        const uint4* p = (const uint4*)((const bf16_t*)in + elem);
-        lo = p[0];
-        hi = p[1];
-    }
-}
-
-// BN = 64: each wave 32 x 64 (2 x 4 MFMA tiles), two LDS buffers and one barrier per K tile.  BN = 128 (Cout % 128 == 0): the waves form
-// 2 x 2, each 64 x 64 (4 x 4 tiles: half the LDS reads per MFMA), ONE LDS buffer (two would pass the 64 KiB of static LDS) and two
-// barriers per K tile, the next tile's global loads in flight across the compute.  Same K order: the two forms give the same bits.
-template <int IN_F32, int OUT16, int BN>
-__global__ __launch_bounds__(256) void vae_conv_mfma_kernel(const ConvP p) {
-    constexpr int NBUF = BN == 128 ? 1 : 2, NB = BN / 64, WI = BN == 128 ? 4 : 2;
-    __shared__ __attribute__((aligned(16))) bf16_t As[NBUF][CBM * CLD];
-    __shared__ __attribute__((aligned(16))) bf16_t Bs[NBUF][BN * CLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const long m0 = (long)blockIdx.x * CBM;
-    const int co0 = blockIdx.y * BN;
-    const int wr0 = BN == 128 ? (wave & 1) * 64 : wave * 32, wc0 = BN == 128 ? (wave >> 1) * 64 : 0;      // the wave's corner in the tile
-    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.pad, st = p.st;
-    const int Hb = p.Hb, Wb = p.Wb, Hs = p.Hs, Ws = p.Ws;
-    const int cpt = Cin / CBK, nk = k * k * cpt;
-    const size_t Ktot = (size_t)k * k * Cin;
-
-    // staging role: rows srow and srow + 64 of the A tile, row srow (and srow + 64: BN = 128) of the B tile, 16 channels at kq
-    const int srow = tid >> 2, kq = (tid & 3) * 16;
-    int pn[2], py[2], px[2];
-    bool pv[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const long m = m0 + srow + 64 * t;
-        pv[t] = m < p.M;
-        const long mm = pv[t] ? m : 0;
-        pn[t] = (int)(mm / ((long)H * W));
-        const int rem = (int)(mm % ((long)H * W));
-        py[t] = rem / W;
-        px[t] = rem % W;
-    }
-    const bf16_t* wrow = p.w + (size_t)(co0 + srow) * Ktot + kq;
-
-    uint4 ra[2][2], rb[NB][2];
-    auto fetch = [&](int kt) {
-        const int tap = kt / cpt, c0 = (kt - tap * cpt) * CBK + kq;
-        const int ky = tap / k, kx = tap - ky * k;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int yy = py[t] * st + ky - pad, xx = px[t] * st + kx - pad;
-            ra[t][0] = uint4{0u, 0u, 0u, 0u};
-            ra[t][1] = uint4{0u, 0u, 0u, 0u};
-            if (pv[t] && yy >= 0 && yy < Hb && xx >= 0 && xx < Wb) {
-                const int ys = p.up2 ? yy >> 1 : yy, xs = p.up2 ? xx >> 1 : xx;
-                load16<IN_F32>(p.in, (((size_t)pn[t] * Hs + ys) * Ws + xs) * Cin + c0, ra[t][0], ra[t][1]);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const uint4* wp = (const uint4*)(wrow + (size_t)t * 64 * Ktot + (size_t)kt * CBK);
-            rb[t][0] = wp[0];
-            rb[t][1] = wp[1];
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            uint4* d = (uint4*)(&As[buf][(srow + 64 * t) * CLD + kq]);
-            d[0] = ra[t][0];
-            d[1] = ra[t][1];
-        }
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            uint4* d = (uint4*)(&Bs[buf][(srow + 64 * t) * CLD + kq]);
-            d[0] = rb[t][0];
-            d[1] = rb[t][1];
-        }
-    };
-
-    f32x4_t acc[WI][4];
-#pragma unroll
-    for (int i = 0; i < WI; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = NBUF == 2 ? kt & 1 : 0;
-        if (kt + 1 < nk) fetch(kt + 1);
-#pragma unroll
-        for (int ks = 0; ks < CBK / 32; ++ks) {
-            bf16x8_t a[WI], b[4];
-#pragma unroll
-            for (int i = 0; i < WI; ++i) a[i] = *(const bf16x8_t*)(&As[buf][(wr0 + i * 16 + r) * CLD + ks * 32 + q * 8]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *(const bf16x8_t*)(&Bs[buf][(wc0 + j * 16 + r) * CLD + ks * 32 + q * 8]);
-#pragma unroll
-            for (int i = 0; i < WI; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(a[i], b[j], acc[i][j]);
-        }
-        if constexpr (NBUF == 1) __syncthreads();       // one buffer: every wave has read K tile kt before it is overwritten
-        // (two buffers: the other one was last read by the compute of K tile kt - 1, which every wave left before the previous barrier)
-        if (kt + 1 < nk) stash(NBUF == 2 ? buf ^ 1 : 0);
-        __syncthreads();
-    }
-
-    // accumulator element e of a lane: pixel row 4 q + e of the 16 x 16 tile, output channel r
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int co = co0 + wc0 + j * 16 + r;
-        const float bv = p.bias[co];
-#pragma unroll
-        for (int i = 0; i < WI; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const long m = m0 + wr0 + i * 16 + q * 4 + e;
-                if (m >= p.M) continue;
-                const size_t o = (size_t)m * p.Cout + co;
-                float v = acc[i][j][e] + bv;
-                if (p.res) v += p.res[o];
-                if constexpr (OUT16) ((bf16_t*)p.out)[o] = cvt16s(v);
-                else ((float*)p.out)[o] = v;
-            }
-    }
-}
-
-// Every other shape (conv_in: K = 36; conv_out: 3 outputs, NCHW store; post_quant_conv: 4 -> 4 from NCHW): one thread per output
-// element, the same operand rounding, a serial fp32 sum in (ky, kx, c) order.
-__global__ __launch_bounds__(256) void vae_conv_plain_kernel(const ConvP p, int in_kind, int out_kind) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.M * p.Cout) return;
-    const int co = (int)(idx % p.Cout);
-    const long m = idx / p.Cout;
-    const int H = p.H, W = p.W, Cin = p.Cin, k = p.k, pad = p.pad, st = p.st;
-    const int Hb = p.Hb, Wb = p.Wb, Hs = p.Hs, Ws = p.Ws;
-    const int n = (int)(m / ((long)H * W)), rem = (int)(m % ((long)H * W)), y = rem / W, x = rem % W;
-    const bf16_t* wr = p.w + (size_t)co * k * k * Cin;
-    float acc = 0.f;
-    for (int ky = 0; ky < k; ++ky) {
-        const int yy = y * st + ky - pad;
-        if (yy < 0 || yy >= Hb) continue;
-        for (int kx = 0; kx < k; ++kx) {
-            const int xx = x * st + kx - pad;
-            if (xx < 0 || xx >= Wb) continue;
-            const int ys = p.up2 ? yy >> 1 : yy, xs = p.up2 ? xx >> 1 : xx;
-            const bf16_t* wt = wr + (size_t)(ky * k + kx) * Cin;
-            if (in_kind == MAPDIT_VAE_IN_16) {
-                const bf16_t* ip = (const bf16_t*)p.in + (((size_t)n * Hs + ys) * Ws + xs) * Cin;
-                int c = 0;
-                if (Cin % 8 == 0 && !(((uintptr_t)ip | (uintptr_t)wt) & 15))        // eight channels per 16-byte load, the same serial order
-                    for (; c < Cin; c += 8) {
-                        const uint4 xv = *(const uint4*)(ip + c), wv = *(const uint4*)(wt + c);
-                        const uint32_t xw[4] = {xv.x, xv.y, xv.z, xv.w}, ww[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            acc = fmaf(lo16(xw[e]), lo16(ww[e]), acc);
-                            acc = fmaf(hi16(xw[e]), hi16(ww[e]), acc);
-                        }
-                    }
-                for (; c < Cin; ++c) acc = fmaf(up16(ip[c]), up16(wt[c]), acc);
-            } else if (in_kind == MAPDIT_VAE_IN_F32) {
-                const float* ip = (const float*)p.in + (((size_t)n * Hs + ys) * Ws + xs) * Cin;
-                for (int c = 0; c < Cin; ++c) acc = fmaf(up16(cvt16s(ip[c])), up16(wt[c]), acc);
-            } else {
-                const float* ip = (const float*)p.in + ((size_t)n * Cin * Hs + ys) * Ws + xs;
-                for (int c = 0; c < Cin; ++c) acc = fmaf(up16(cvt16s(ip[(size_t)c * Hs * Ws])), up16(wt[c]), acc);
-            }
-        }
-    }
-    float v = acc + p.bias[co];
-    if (out_kind == MAPDIT_VAE_OUT_F32_NCHW) {
-        ((float*)p.out)[(((size_t)n * p.Cout + co) * H + y) * W + x] = v;
-        return;
-    }
-    if (p.res) v += p.res[idx];
-    if (out_kind == MAPDIT_VAE_OUT_16) ((bf16_t*)p.out)[idx] = cvt16s(v);
-    else ((float*)p.out)[idx] = v;
-}
 
 // ---- GroupNorm (+ SiLU) over NHWC -----------------------------------------------------------------------------------------------
 // One workgroup per (sample, group).  Statistics in ONE pass over d = x - x[first element of the group] with fp64 sums of d and d * d
@@ -506,12 +285,6 @@ __global__ void vae_stats_finish_kernel(const double* __restrict__ acc, double c
 
 MD_NS_CLOSE
 
-#define VAE_TRY(call)                    \
-    do {                                 \
-        const int rc_ = (call);          \
-        if (rc_ != MAPDIT_OK) return rc_; \
-    } while (0)
-
 // ---- entry points -----------------------------------------------------------------------------------------------------------------
 // mapdit_vae_conv (Hin = Win = 0) and mapdit_vae_conv_down (the input size) are one launch path: only the coordinate map differs.
 static int vae_conv_launch(const char* who, const mapdit_vae_conv_t* a, int Hin, int Win, bool down, void* stream) {
@@ -534,31 +307,14 @@ static int vae_conv_launch(const char* who, const mapdit_vae_conv_t* a, int Hin,
     MD_CHECK(!(a->res && a->out_kind == MAPDIT_VAE_OUT_F32_NCHW), "%s: no residual with the NCHW store", who);
     const long M = (long)a->N * a->H * a->W;
     MD_CHECK(M * a->Cout < (1L << 40) && M < (1L << 31), "%s: %ld output pixels are too many", who, M);
-    hipStream_t st = (hipStream_t)stream;
-    const int up2 = a->up2 ? 1 : 0;
-    const ConvP p{a->in, (const bf16_t*)a->w, a->bias, a->res, a->out, a->N, a->H, a->W, a->Cin, a->Cout, a->k, up2, M,
-                  down ? 2 : 1, down ? 0 : a->k >> 1, down ? Hin : a->H, down ? Win : a->W,
-                  down ? Hin : up2 ? a->H >> 1 : a->H, down ? Win : up2 ? a->W >> 1 : a->W};
+    const int up2 = a->up2 ? 1 : 0, st = down ? 2 : 1, pad = down ? 0 : a->k >> 1;
+    const md_conv_t p{a->in, (const bf16_t*)a->w, a->bias, a->res, a->out, a->in_kind, a->out_kind,
+                      down ? Hin : a->H >> up2, down ? Win : a->W >> up2, down ? Hin : a->H, down ? Win : a->W, up2,
+                      a->k, a->k, st, pad, pad, a->H, a->W, a->Cin, a->Cout, (int)((long)a->k * a->k * a->Cin), M, a->Cout, 0, 0};
+    // the MFMA path exactly for 64-channel multiples on both sides, NHWC, aligned; the wide tile exactly when Cout % 128 == 0
     const bool aligned = !(((uintptr_t)a->in | (uintptr_t)a->w) & 15);
-    if (a->Cin % CBK == 0 && a->Cout % 64 == 0 && a->in_kind != MAPDIT_VAE_IN_F32_NCHW && a->out_kind != MAPDIT_VAE_OUT_F32_NCHW && aligned) {
-        const bool f32 = a->in_kind == MAPDIT_VAE_IN_F32, o16 = a->out_kind == MAPDIT_VAE_OUT_16, wide = a->Cout % 128 == 0;
-        const dim3 grid((unsigned)cdiv(M, CBM), (unsigned)(a->Cout / (wide ? 128 : 64)));
-#define VAE_CONV_GO(F, O)                                                          \
-    do {                                                                           \
-        if (wide) vae_conv_mfma_kernel<F, O, 128><<<grid, 256, 0, st>>>(p);        \
-        else vae_conv_mfma_kernel<F, O, 64><<<grid, 256, 0, st>>>(p);              \
-    } while (0)
-        if (f32 && o16) VAE_CONV_GO(1, 1);
-        else if (f32) VAE_CONV_GO(1, 0);
-        else if (o16) VAE_CONV_GO(0, 1);
-        else VAE_CONV_GO(0, 0);
-#undef VAE_CONV_GO
-    } else {
-        MD_CHECK(M * a->Cout < (1L << 38), "%s: %ld x %d outputs are too many for the plain kernel", who, M, a->Cout);
-        vae_conv_plain_kernel<<<cdiv(M * a->Cout, 256), 256, 0, st>>>(p, a->in_kind, a->out_kind);
-    }
-    MD_LAUNCH_CHECK();
-    return MAPDIT_OK;
+    const bool mfma = a->Cin % 64 == 0 && a->Cout % 64 == 0 && a->in_kind != MAPDIT_VAE_IN_F32_NCHW && a->out_kind != MAPDIT_VAE_OUT_F32_NCHW && aligned;
+    return MD_SYM(conv_launch)(who, &p, !mfma ? MD_CONV_PLAIN : a->Cout % 128 == 0 ? MD_CONV_128 : MD_CONV_64, stream);
 }
 
 extern "C" int MD_SYM(vae_conv)(const mapdit_vae_conv_t* a, void* stream) { return vae_conv_launch("vae_conv", a, 0, 0, false, stream); }
@@ -644,8 +400,6 @@ struct VaePlan {
     size_t off_x, off_y, off_h, off_a, off_qkv, off_s, off_p, off_gn, gn_bytes, total;
 };
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the config checks both directions share; fills nb and C.  0 = ok; otherwise the message is set
 int vae_plan_config(const mapdit_vae_config_t* cfg, int N, int h, int w, bool reversed, VaePlan* pl) {
     MD_CHECK(cfg, "vae: null config");
@@ -670,21 +424,21 @@ int vae_plan_config(const mapdit_vae_config_t* cfg, int N, int h, int w, bool re
 void vae_plan_layout(VaePlan* pl, size_t maxE, int N, size_t T, int Cmid, size_t max_hw, int G) {
     pl->maxE = maxE;
     size_t o = 0;
-    pl->off_x = o; o += up256(maxE * 4);
-    pl->off_y = o; o += up256(maxE * 4);
-    pl->off_h = o; o += up256(maxE * 4);
-    pl->off_a = o; o += up256(maxE * 2);
-    pl->off_qkv = o; o += up256((size_t)N * T * 3 * Cmid * 2);
-    pl->off_s = o; o += up256(T * T * 4);
-    pl->off_p = o; o += up256(T * T * 2);
+    pl->off_x = o; o += md_up256(maxE * 4);
+    pl->off_y = o; o += md_up256(maxE * 4);
+    pl->off_h = o; o += md_up256(maxE * 4);
+    pl->off_a = o; o += md_up256(maxE * 2);
+    pl->off_qkv = o; o += md_up256((size_t)N * T * 3 * Cmid * 2);
+    pl->off_s = o; o += md_up256(T * T * 4);
+    pl->off_p = o; o += md_up256(T * T * 2);
     // partial sums of the split GroupNorm: per sample, 1,024-pixel chunk of the largest image and group, two fp64
     pl->gn_bytes = (size_t)N * (size_t)cdiv((long)max_hw, GN_PX) * G * 2 * sizeof(double);
-    pl->off_gn = o; o += up256(pl->gn_bytes);
+    pl->off_gn = o; o += md_up256(pl->gn_bytes);
     pl->total = o;
 }
 
 int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
-    VAE_TRY(vae_plan_config(cfg, N, h, w, true, pl));
+    MD_TRY(vae_plan_config(cfg, N, h, w, true, pl));
     MD_CHECK((long)h * w % 8 == 0, "vae: h*w = %ld tokens in the mid-block attention must be a multiple of 8 (operand alignment of its GEMMs)", (long)h * w);
     MD_CHECK((long)N * h * w * (1L << (2 * (pl->nb - 1))) < (1L << 31), "vae: N=%d latents of %d x %d are too many output pixels for one call", N, h, w);
     size_t px = (size_t)N * h * w, maxE = px * (size_t)pl->C[0];
@@ -704,7 +458,7 @@ int vae_plan(const mapdit_vae_config_t* cfg, int N, int h, int w, VaePlan* pl) {
 
 // the encoder: N images of H x W
 int vae_encode_plan(const mapdit_vae_config_t* cfg, int N, int H, int W, VaePlan* pl) {
-    VAE_TRY(vae_plan_config(cfg, N, H, W, false, pl));
+    MD_TRY(vae_plan_config(cfg, N, H, W, false, pl));
     const int s = 1 << (pl->nb - 1);
     MD_CHECK(H % s == 0 && W % s == 0, "vae encode: an image of %d x %d is not a multiple of %d (2^(num_blocks - 1): every downsample halves an even size)", H, W, s);
     const long T = (long)(H / s) * (W / s);
@@ -773,20 +527,20 @@ struct VaeRun {
     int resnet(const void* const* r, int rix, int H, int W, int cin, int cout) const {
         const bool sc = cin != cout;
         MD_CHECK(!sc || (r[MAPDIT_VAE_R_SC_W] && r[MAPDIT_VAE_R_SC_B]), "%s: resnet %d maps %d -> %d channels and has no conv_shortcut", who, rix, cin, cout);
-        VAE_TRY(gn(X, r[MAPDIT_VAE_R_N1_G], r[MAPDIT_VAE_R_N1_B], 1, H * W, cin));
-        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C1_W], r[MAPDIT_VAE_R_C1_B], nullptr, Hb, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 3, 0));
-        VAE_TRY(gn(Hb, r[MAPDIT_VAE_R_N2_G], r[MAPDIT_VAE_R_N2_B], 1, H * W, cout));
-        if (sc) VAE_TRY(conv(X, MAPDIT_VAE_IN_F32, r[MAPDIT_VAE_R_SC_W], r[MAPDIT_VAE_R_SC_B], nullptr, Y, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 1, 0));
+        MD_TRY(gn(X, r[MAPDIT_VAE_R_N1_G], r[MAPDIT_VAE_R_N1_B], 1, H * W, cin));
+        MD_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C1_W], r[MAPDIT_VAE_R_C1_B], nullptr, Hb, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 3, 0));
+        MD_TRY(gn(Hb, r[MAPDIT_VAE_R_N2_G], r[MAPDIT_VAE_R_N2_B], 1, H * W, cout));
+        if (sc) MD_TRY(conv(X, MAPDIT_VAE_IN_F32, r[MAPDIT_VAE_R_SC_W], r[MAPDIT_VAE_R_SC_B], nullptr, Y, MAPDIT_VAE_OUT_F32, H, W, cin, cout, 1, 0));
         // (same widths: the residual is read and the sum written in place, element by element, by the thread that owns it)
-        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C2_W], r[MAPDIT_VAE_R_C2_B], sc ? Y : X, X, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 0));
+        MD_TRY(conv(A16, MAPDIT_VAE_IN_16, r[MAPDIT_VAE_R_C2_W], r[MAPDIT_VAE_R_C2_B], sc ? Y : X, X, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 0));
         return MAPDIT_OK;
     }
     // the mid block's single-head attention over the T = H * W pixels of each sample, X += out(softmax(q k^T / sqrt(C)) v)
     int attention(const void* gn_g, const void* gn_b, const void* qkv_w, const void* qkv_b, const void* out_w, const void* out_b, int H, int W,
                   int C0) const {
         const int T = H * W;
-        VAE_TRY(gn(X, gn_g, gn_b, 0, T, C0));
-        VAE_TRY(conv(A16, MAPDIT_VAE_IN_16, qkv_w, qkv_b, nullptr, QKV, MAPDIT_VAE_OUT_16, H, W, C0, 3 * C0, 1, 0));
+        MD_TRY(gn(X, gn_g, gn_b, 0, T, C0));
+        MD_TRY(conv(A16, MAPDIT_VAE_IN_16, qkv_w, qkv_b, nullptr, QKV, MAPDIT_VAE_OUT_16, H, W, C0, 3 * C0, 1, 0));
         for (int n = 0; n < N; ++n) {
             const uint16_t* qn = QKV + (size_t)n * T * 3 * C0;
             mapdit_epilogue_t e{};
@@ -794,14 +548,14 @@ struct VaeRun {
             e.out = S;
             e.ldo = T;
             e.alpha = 1.f / sqrtf((float)C0);
-            VAE_TRY(MD_SYM_GEMM(MAPDIT_NT, T, T, C0, qn, 3 * C0, qn + C0, 3 * C0, &e, stream));
-            VAE_TRY(MD_SYM(vae_softmax)(S, T, P, T, T, T, stream));
+            MD_TRY(MD_SYM_GEMM(MAPDIT_NT, T, T, C0, qn, 3 * C0, qn + C0, 3 * C0, &e, stream));
+            MD_TRY(MD_SYM(vae_softmax)(S, T, P, T, T, T, stream));
             mapdit_epilogue_t e2{};
             e2.kind = MAPDIT_EPI_STORE_F32;
             e2.out = Hb + (size_t)n * T * C0;
             e2.ldo = C0;
             e2.alpha = 1.f;
-            VAE_TRY(MD_SYM_GEMM(MAPDIT_NN, T, C0, T, P, T, qn + 2 * C0, 3 * C0, &e2, stream));
+            MD_TRY(MD_SYM_GEMM(MAPDIT_NN, T, C0, T, P, T, qn + 2 * C0, 3 * C0, &e2, stream));
         }
         return conv(Hb, MAPDIT_VAE_IN_F32, out_w, out_b, X, X, MAPDIT_VAE_OUT_F32, H, W, C0, C0, 1, 0);
     }
@@ -835,12 +589,12 @@ extern "C" size_t mapdit_vae_encode_workspace_bytes(const mapdit_vae_config_t* c
 extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* const* wt, const float* z, float* out, int N, int h, int w,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     VaePlan pl;
-    VAE_TRY(vae_plan(cfg, N, h, w, &pl));
+    MD_TRY(vae_plan(cfg, N, h, w, &pl));
     MD_CHECK(wt && z && out && workspace, "vae_decode: null argument");
     MD_CHECK(workspace_bytes >= pl.total, "vae_decode: workspace of %zu bytes, %zu needed (mapdit_vae_workspace_bytes)", workspace_bytes, pl.total);
     MD_CHECK(!((uintptr_t)workspace & 255), "vae_decode: the workspace must be 256-byte aligned");
     const int nres = 2 + pl.nb * (cfg->layers_per_block + 1);
-    VAE_TRY(vae_check_table("vae_decode", wt, MAPDIT_VAE_NUM_GLOBAL, nres, (pl.nb - 1) * MAPDIT_VAE_NUM_UP));
+    MD_TRY(vae_check_table("vae_decode", wt, MAPDIT_VAE_NUM_GLOBAL, nres, (pl.nb - 1) * MAPDIT_VAE_NUM_UP));
     VaeRun r("vae_decode", cfg, pl, N, workspace, stream);
     int rix = 0;      // resnets in execution order
     auto resnet = [&](int H, int W, int cin, int cout) {
@@ -851,32 +605,32 @@ extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* co
     int H = h, W = w;
     const int C0 = pl.C[0], L = cfg->latent_channels;
     // post_quant_conv (reads z as NCHW) and conv_in
-    VAE_TRY(r.conv(z, MAPDIT_VAE_IN_F32_NCHW, wt[MAPDIT_VAE_W_PQ_W], wt[MAPDIT_VAE_W_PQ_B], nullptr, r.Hb, MAPDIT_VAE_OUT_F32, H, W, L, L, 1, 0));
-    VAE_TRY(r.conv(r.Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_CONV_IN_W], wt[MAPDIT_VAE_W_CONV_IN_B], nullptr, r.X, MAPDIT_VAE_OUT_F32, H, W, L, C0, 3, 0));
+    MD_TRY(r.conv(z, MAPDIT_VAE_IN_F32_NCHW, wt[MAPDIT_VAE_W_PQ_W], wt[MAPDIT_VAE_W_PQ_B], nullptr, r.Hb, MAPDIT_VAE_OUT_F32, H, W, L, L, 1, 0));
+    MD_TRY(r.conv(r.Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_W_CONV_IN_W], wt[MAPDIT_VAE_W_CONV_IN_B], nullptr, r.X, MAPDIT_VAE_OUT_F32, H, W, L, C0, 3, 0));
     // mid block
-    VAE_TRY(resnet(H, W, C0, C0));
-    VAE_TRY(r.attention(wt[MAPDIT_VAE_W_ATTN_GN_G], wt[MAPDIT_VAE_W_ATTN_GN_B], wt[MAPDIT_VAE_W_ATTN_QKV_W], wt[MAPDIT_VAE_W_ATTN_QKV_B],
+    MD_TRY(resnet(H, W, C0, C0));
+    MD_TRY(r.attention(wt[MAPDIT_VAE_W_ATTN_GN_G], wt[MAPDIT_VAE_W_ATTN_GN_B], wt[MAPDIT_VAE_W_ATTN_QKV_W], wt[MAPDIT_VAE_W_ATTN_QKV_B],
                         wt[MAPDIT_VAE_W_ATTN_OUT_W], wt[MAPDIT_VAE_W_ATTN_OUT_B], H, W, C0));
-    VAE_TRY(resnet(H, W, C0, C0));
+    MD_TRY(resnet(H, W, C0, C0));
     // up blocks
     int cin = C0;
     const void* const* ups = wt + MAPDIT_VAE_NUM_GLOBAL + nres * MAPDIT_VAE_NUM_RESNET;
     for (int i = 0; i < pl.nb; ++i) {
         const int cout = pl.C[i];
         for (int j = 0; j <= cfg->layers_per_block; ++j) {
-            VAE_TRY(resnet(H, W, cin, cout));
+            MD_TRY(resnet(H, W, cin, cout));
             cin = cout;
         }
         if (i < pl.nb - 1) {
             const void* const* u = ups + i * MAPDIT_VAE_NUM_UP;
             H *= 2;
             W *= 2;
-            VAE_TRY(r.conv(r.X, MAPDIT_VAE_IN_F32, u[MAPDIT_VAE_U_W], u[MAPDIT_VAE_U_B], nullptr, r.Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 1));
+            MD_TRY(r.conv(r.X, MAPDIT_VAE_IN_F32, u[MAPDIT_VAE_U_W], u[MAPDIT_VAE_U_B], nullptr, r.Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout, 3, 1));
             r.swap_xy();
         }
     }
-    VAE_TRY(r.gn(r.X, wt[MAPDIT_VAE_W_NORM_OUT_G], wt[MAPDIT_VAE_W_NORM_OUT_B], 1, H * W, cin));
-    VAE_TRY(r.conv(r.A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_CONV_OUT_W], wt[MAPDIT_VAE_W_CONV_OUT_B], nullptr, out, MAPDIT_VAE_OUT_F32_NCHW, H, W, cin,
+    MD_TRY(r.gn(r.X, wt[MAPDIT_VAE_W_NORM_OUT_G], wt[MAPDIT_VAE_W_NORM_OUT_B], 1, H * W, cin));
+    MD_TRY(r.conv(r.A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_W_CONV_OUT_W], wt[MAPDIT_VAE_W_CONV_OUT_B], nullptr, out, MAPDIT_VAE_OUT_F32_NCHW, H, W, cin,
                    cfg->out_channels, 3, 0));
     return MAPDIT_OK;
 }
@@ -885,13 +639,13 @@ extern "C" int MD_SYM(vae_decode)(const mapdit_vae_config_t* cfg, const void* co
 extern "C" int MD_SYM(vae_encode)(const mapdit_vae_config_t* cfg, const void* const* wt, const float* x, int x_kind, float* mean, float* std, int N,
                                   int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
     VaePlan pl;
-    VAE_TRY(vae_encode_plan(cfg, N, H, W, &pl));
+    MD_TRY(vae_encode_plan(cfg, N, H, W, &pl));
     MD_CHECK(wt && x && mean && std && workspace, "vae_encode: null argument");
     MD_CHECK(x_kind == MAPDIT_VAE_IN_F32 || x_kind == MAPDIT_VAE_IN_F32_NCHW, "vae_encode: x_kind=%d (MAPDIT_VAE_IN_F32 or MAPDIT_VAE_IN_F32_NCHW)", x_kind);
     MD_CHECK(workspace_bytes >= pl.total, "vae_encode: workspace of %zu bytes, %zu needed (mapdit_vae_encode_workspace_bytes)", workspace_bytes, pl.total);
     MD_CHECK(!((uintptr_t)workspace & 255), "vae_encode: the workspace must be 256-byte aligned");
     const int nres = pl.nb * cfg->layers_per_block + 2;
-    VAE_TRY(vae_check_table("vae_encode", wt, MAPDIT_VAE_E_NUM_GLOBAL, nres, (pl.nb - 1) * MAPDIT_VAE_NUM_DOWN));
+    MD_TRY(vae_check_table("vae_encode", wt, MAPDIT_VAE_E_NUM_GLOBAL, nres, (pl.nb - 1) * MAPDIT_VAE_NUM_DOWN));
     VaeRun r("vae_encode", cfg, pl, N, workspace, stream);
     int rix = 0;
     auto resnet = [&](int h, int w, int cin, int cout) {
@@ -900,32 +654,32 @@ extern "C" int MD_SYM(vae_encode)(const mapdit_vae_config_t* cfg, const void* co
     };
 
     const int L2 = 2 * cfg->latent_channels;
-    VAE_TRY(r.conv(x, x_kind, wt[MAPDIT_VAE_E_CONV_IN_W], wt[MAPDIT_VAE_E_CONV_IN_B], nullptr, r.X, MAPDIT_VAE_OUT_F32, H, W, cfg->out_channels, pl.C[0], 3, 0));
+    MD_TRY(r.conv(x, x_kind, wt[MAPDIT_VAE_E_CONV_IN_W], wt[MAPDIT_VAE_E_CONV_IN_B], nullptr, r.X, MAPDIT_VAE_OUT_F32, H, W, cfg->out_channels, pl.C[0], 3, 0));
     // down blocks
     int cin = pl.C[0];
     const void* const* downs = wt + MAPDIT_VAE_E_NUM_GLOBAL + nres * MAPDIT_VAE_NUM_RESNET;
     for (int i = 0; i < pl.nb; ++i) {
         const int cout = pl.C[i];
         for (int j = 0; j < cfg->layers_per_block; ++j) {
-            VAE_TRY(resnet(H, W, cin, cout));
+            MD_TRY(resnet(H, W, cin, cout));
             cin = cout;
         }
         if (i < pl.nb - 1) {
             const void* const* d = downs + i * MAPDIT_VAE_NUM_DOWN;
-            VAE_TRY(r.conv_down(r.X, MAPDIT_VAE_IN_F32, d[MAPDIT_VAE_D_W], d[MAPDIT_VAE_D_B], r.Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout));
+            MD_TRY(r.conv_down(r.X, MAPDIT_VAE_IN_F32, d[MAPDIT_VAE_D_W], d[MAPDIT_VAE_D_B], r.Y, MAPDIT_VAE_OUT_F32, H, W, cout, cout));
             r.swap_xy();
             H /= 2;
             W /= 2;
         }
     }
     // mid block
-    VAE_TRY(resnet(H, W, cin, cin));
-    VAE_TRY(r.attention(wt[MAPDIT_VAE_E_ATTN_GN_G], wt[MAPDIT_VAE_E_ATTN_GN_B], wt[MAPDIT_VAE_E_ATTN_QKV_W], wt[MAPDIT_VAE_E_ATTN_QKV_B],
+    MD_TRY(resnet(H, W, cin, cin));
+    MD_TRY(r.attention(wt[MAPDIT_VAE_E_ATTN_GN_G], wt[MAPDIT_VAE_E_ATTN_GN_B], wt[MAPDIT_VAE_E_ATTN_QKV_W], wt[MAPDIT_VAE_E_ATTN_QKV_B],
                         wt[MAPDIT_VAE_E_ATTN_OUT_W], wt[MAPDIT_VAE_E_ATTN_OUT_B], H, W, cin));
-    VAE_TRY(resnet(H, W, cin, cin));
+    MD_TRY(resnet(H, W, cin, cin));
     // conv_norm_out + SiLU, conv_out, quant_conv, the posterior head
-    VAE_TRY(r.gn(r.X, wt[MAPDIT_VAE_E_NORM_OUT_G], wt[MAPDIT_VAE_E_NORM_OUT_B], 1, H * W, cin));
-    VAE_TRY(r.conv(r.A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_E_CONV_OUT_W], wt[MAPDIT_VAE_E_CONV_OUT_B], nullptr, r.Hb, MAPDIT_VAE_OUT_F32, H, W, cin, L2, 3, 0));
-    VAE_TRY(r.conv(r.Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_E_QUANT_W], wt[MAPDIT_VAE_E_QUANT_B], nullptr, r.Y, MAPDIT_VAE_OUT_F32, H, W, L2, L2, 1, 0));
+    MD_TRY(r.gn(r.X, wt[MAPDIT_VAE_E_NORM_OUT_G], wt[MAPDIT_VAE_E_NORM_OUT_B], 1, H * W, cin));
+    MD_TRY(r.conv(r.A16, MAPDIT_VAE_IN_16, wt[MAPDIT_VAE_E_CONV_OUT_W], wt[MAPDIT_VAE_E_CONV_OUT_B], nullptr, r.Hb, MAPDIT_VAE_OUT_F32, H, W, cin, L2, 3, 0));
+    MD_TRY(r.conv(r.Hb, MAPDIT_VAE_IN_F32, wt[MAPDIT_VAE_E_QUANT_W], wt[MAPDIT_VAE_E_QUANT_B], nullptr, r.Y, MAPDIT_VAE_OUT_F32, H, W, L2, L2, 1, 0));
     return mapdit_vae_posterior(r.Y, mean, std, nullptr, N, H * W, cfg->latent_channels, stream);
 }

@@ -134,6 +134,32 @@ def test_conv_is_batch_independent(prec):
         assert not torch.equal(three[0], alone[0])
 
 
+@pytest.mark.parametrize("prec", ["f16", "bf16"])
+@pytest.mark.parametrize("N, H, W, Cin, Cout, k", [
+    (2, 5, 7, 64, 64, 3),            # the 64 tile both ways; a sample boundary inside a tile
+    (1, 8, 8, 128, 128, 3),          # mapdit_vae_conv takes the 128 tile, mapdit_inc_conv the 64 tile: the two tile forms give the same bits
+    (2, 4, 6, 64, 64, 1),
+], ids=["2x5x7-64-64-3x3", "1x8x8-128-128-3x3", "2x4x6-64-64-1x1"])
+def test_vae_conv_and_inc_conv_are_one_convolution(prec, N, H, W, Cin, Cout, k):
+    """The two entry points run the same kernels (csrc/conv.hip): the same 16-bit operands, one packed [Cout][ky][kx][Cin] weight, bias,
+    no ReLU, no residual, fp32 output, "same" padding through mapdit_vae_conv and pad k / 2 through mapdit_inc_conv - equal bits."""
+    L = _L()
+    x, w, b = _operands(prec, N, Cin, H, W, Cout, k, k, seed=61)
+    xd = x.permute(0, 2, 3, 1).contiguous().to(DTYPES[prec]).to(DEV)
+    wd = w.permute(0, 2, 3, 1).contiguous().to(DTYPES[prec]).to(DEV)
+    bd = b.to(torch.float32).to(DEV)
+    via_vae = torch.full((N, H, W, Cout), float("nan"), device=DEV)
+    via_inc = torch.full((N, H, W, Cout), float("nan"), device=DEV)
+    va = L.VaeConv(xd.data_ptr(), L.VAE_IN_16, wd.data_ptr(), bd.data_ptr(), None, via_vae.data_ptr(), L.VAE_OUT_F32, N, H, W, Cin, Cout, k, 0)
+    _fn("vae_conv", prec)(C.byref(va), L.cur_stream())
+    ia = L.IncConv(xd.data_ptr(), L.INC_IN_16, wd.data_ptr(), bd.data_ptr(), via_inc.data_ptr(), L.INC_OUT_F32, N, H, W, Cin, Cout, k, k, 1, k // 2, k // 2,
+                   0, Cout, 0)
+    _fn("inc_conv", prec)(C.byref(ia), L.cur_stream())
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(via_vae).all()) and bool((via_vae < 0).any())
+    assert torch.equal(via_vae, via_inc)
+
+
 def test_conv_refusals():
     L = _L()
     x, w, b = _operands("bf16", 1, 16, 4, 4, 16, 3, 3, seed=1)
