@@ -1044,6 +1044,39 @@ int mapdit_inc_features(const mapdit_inc_config_t* cfg, const void* const* weigh
 int mapdit_inc_stats_accumulate(const float* feat, int N, int D, double* sum, double* outer, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Sample-quality metrics on feature sets (csrc/manifold.hip; metrics.py builds precision / recall, density / coverage and KID on them).
+ * Every set is row-major fp32 [rows, D] on the device, 16-byte aligned, D a multiple of 4 and at most 65,536, 1 .. 2^30 rows.  One
+ * tiled kernel forms the Gram matrix g(i, j) = x_i . y_j on the fp32-input MFMA (exact fp32 products, one fp32 rounding per step, the
+ * same K order for every element: g(i, j) == g(j, i) bit for bit) and reduces each 128 x 128 tile in its epilogue; the N x M matrix
+ * is never stored.  Squared distances are d2(i, j) = max(0, fma(-2, g, n_i + n_j)) with the squared row norms n summed in fp64 and
+ * rounded once to fp32 (mapdit_row_sqnorm), so d2(i, j) == d2(j, i) too.
+ * The grid is query tiles x `chunks` slices of the reference rows; partial results go to the workspace and a second kernel merges
+ * them.  chunks = 0 lets the library choose; a positive value (at most 65,535) forces that many slices.  No result depends on chunks:
+ * a k-smallest set, an integer count and a sum of per-tile fp64 partials in a fixed order; no atomics.  Each *_workspace_bytes is a
+ * host query (0 with a message in mapdit_last_error() when the shape is refused); the workspace is 256-byte aligned.  Every launch
+ * goes to `stream`; no allocation, no synchronisation.  Refusals (MAPDIT_ERR_ARG, before any launch): null or misaligned pointers,
+ * D, row counts, chunks outside the ranges above, a workspace that is too small, and what each function lists.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* out[i] = sum_d X[i][d]^2, added in fp64 (a fixed order per row), rounded once to fp32. */
+int mapdit_row_sqnorm(const float* X, int N, int D, float* out, void* stream);
+/* radii[i] = the k-th smallest d2(i, j) over j != i, 1 <= k <= 8 and k < N.  The row itself is left out by index, not by value: a
+ * duplicate row at another index is a neighbour at distance 0. */
+size_t mapdit_knn_radii_workspace_bytes(int N, int D, int chunks);
+int mapdit_knn_radii(const float* X, int N, int D, int k, float* radii, int chunks, void* workspace, size_t ws_bytes, void* stream);
+/* count[q] = #{r : d2(q, r) <= rad[r]} (MAPDIT_BALL_REF_RADIUS, rad [Nr]: precision, recall, density) or #{r : d2(q, r) <= rad[q]}
+ * (MAPDIT_BALL_QUERY_RADIUS, rad [Nq]: coverage).  <=: a tie is inside.  self = 1 skips r == q by index and needs Q == R, Nq == Nr. */
+enum { MAPDIT_BALL_REF_RADIUS = 0, MAPDIT_BALL_QUERY_RADIUS = 1 };
+size_t mapdit_ball_count_workspace_bytes(int Nq, int Nr, int D, int chunks);
+int mapdit_ball_count(const float* Q, int Nq, const float* R, int Nr, int D, const float* rad, int mode, int self, uint32_t* count,
+                      int chunks, void* workspace, size_t ws_bytes, void* stream);
+/* *out (fp64, device) = sum over i < Na, j < Nb of (gamma * g(i, j) + coef0)^degree, degree 1 .. 4: the fp32 Gram value is converted
+ * to fp64 before the polynomial; one fp64 partial per tile pair and wave, added in index order.  skip_diag = 1 drops i == j and needs
+ * A == B, Na == Nb. */
+size_t mapdit_poly_kernel_sum_workspace_bytes(int Na, int Nb, int D, int chunks);
+int mapdit_poly_kernel_sum(const float* A, int Na, const float* B, int Nb, int D, double gamma, double coef0, int degree, int skip_diag,
+                           double* out, int chunks, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
  * holds fp16 bits instead of bf16 bits.  (mapdit_weightnorm_fwd*_f16: w_bf16 receives fp16; the w_split3 image stays a bf16
  * split - the fp32-accurate conditioning GEMMs run on bf16 terms in every engine.)

@@ -3,7 +3,12 @@
 (``mapdit_inc_stats_accumulate``) and the Fréchet distance of the two Gaussian fits on the host.
 
     python -m mapdit_amd.fid stats --images A.npz --inception-weights FILE --output ref.npz
-    python -m mapdit_amd.fid compare a.npz b.npz [--inception-weights FILE]
+    python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz
+    python -m mapdit_amd.fid compare a.npz b.npz [--inception-weights FILE] [--metrics fid,pr,kid]
+
+``features`` writes the ``pool_3`` features [N, 2048] fp32 beside ``mu`` and ``sigma``, so the file still loads as a statistics file.
+``--metrics``: ``pr`` (precision, recall, density, coverage) and ``kid`` (metrics.py) need the features of both sides - an image
+array with the weights, or a file that holds ``pool_3``; ``a`` is the reference (real) side, ``b`` the samples.
 
 Parity with the hub weights is unpinned: the network is restated from its public description and checked against an independent
 fp64 restatement on random weights (tests/inception_reference.py), not against ``pytorch-fid``.  The first FID quoted from this
@@ -18,6 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import metrics as M
+from .metrics import METRICS, add_metric_flags, parse_metrics  # noqa: F401  (the --metrics flags, shared with sample_fid.py)
 from .vae import PRECISIONS, load_state_dict_file
 
 BN_EPS = 1e-3
@@ -266,6 +273,57 @@ def load_stats(path):
 
 FeatureStats.load = staticmethod(load_stats)
 
+FEATURES_KEY = "pool_3"
+
+
+def save_features(path, feat, mu, sigma):
+    """``pool_3`` fp32 [N, D] beside ``mu`` and ``sigma``: a statistics file that also carries what precision / recall and KID need."""
+    with open(path, "wb") as f:
+        np.savez(f, **{FEATURES_KEY: np.asarray(feat, np.float32)}, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64))
+
+
+def features_rows(path):
+    """The number of rows of ``pool_3`` in an ``.npz``, read from the array's header alone; None when the file holds none."""
+    import zipfile
+    if not str(path).endswith(".npz"):
+        return None
+    with zipfile.ZipFile(path) as z:
+        if FEATURES_KEY + ".npy" not in z.namelist():
+            return None
+        with z.open(FEATURES_KEY + ".npy") as f:
+            np.lib.format.read_magic(f)                        # (np.savez writes format 1.0 for arrays of this size)
+            shape = np.lib.format.read_array_header_1_0(f)[0]
+    if len(shape) != 2:
+        raise ValueError(f"{path}: {FEATURES_KEY} of shape {shape} is no [N, D]")
+    return int(shape[0])
+
+
+def has_features(path) -> bool:
+    return features_rows(path) is not None
+
+
+def load_features(path):
+    """fp32 [N, D] ``pool_3`` of a file written by the ``features`` subcommand."""
+    with np.load(path) as z:
+        if FEATURES_KEY not in z.files:
+            raise KeyError(f"{path}: no {FEATURES_KEY!r} in the file (it holds {sorted(z.files)}): write one with "
+                           "`python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz`")
+        feat = np.ascontiguousarray(z[FEATURES_KEY], np.float32)
+    if feat.ndim != 2:
+        raise ValueError(f"{path}: {FEATURES_KEY} of shape {feat.shape} is no [N, D]")
+    return feat
+
+
+# ---- metrics beside the FID ---------------------------------------------------------------------------------------------------------
+def extra_metrics(real, fake, names, args) -> dict:
+    """The values of ``pr`` and ``kid`` (those in ``names``) of two fp32 CUDA feature tensors, in printing order."""
+    out = {}
+    if "pr" in names:
+        out.update(M.precision_recall(real, fake))
+    if "kid" in names:
+        out["kid"], out["kid_std"] = M.kid(real, fake, args.kid_subsets, args.kid_subset_size)
+    return out
+
 
 def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
     """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) in fp64 on the host.  tr (S1 S2)^(1/2) is the sum of the square roots of the
@@ -304,6 +362,15 @@ def stats_of_images(images, net, batch_size=64, device="cuda") -> FeatureStats:
     return st
 
 
+def features_of_images(images, net, batch_size=64, device="cuda"):
+    """(fp32 [N, 2048] on the device, FeatureStats): stats_of_images that keeps the features."""
+    st, feats = FeatureStats(FEATURE_DIM, device), []
+    for i in range(0, len(images), batch_size):
+        feats.append(net.features(torch.from_numpy(np.ascontiguousarray(images[i:i + batch_size])).to(device)))
+        st.update(feats[-1])
+    return torch.cat(feats), st
+
+
 def _is_stats(path) -> bool:
     if not str(path).endswith(".npz"):
         return False
@@ -317,10 +384,14 @@ def build_parser():
     s = sub.add_parser("stats", help="feature statistics (mu, sigma) of an image array")
     s.add_argument("--images", required=True, help=".npz / .npy of uint8 [N, H, W, 3]")
     s.add_argument("--output", required=True)
-    c = sub.add_parser("compare", help="FID of two statistics files or image arrays")
-    c.add_argument("a")
-    c.add_argument("b")
-    for q in (s, c):
+    f = sub.add_parser("features", help="pool_3 features of an image array, with their mu and sigma")
+    f.add_argument("--images", required=True, help=".npz / .npy of uint8 [N, H, W, 3]")
+    f.add_argument("--output", required=True)
+    c = sub.add_parser("compare", help="FID (and with --metrics precision / recall, KID) of two statistics or feature files or image arrays")
+    c.add_argument("a", help="the reference (real) side")
+    c.add_argument("b", help="the samples")
+    add_metric_flags(c)
+    for q in (s, f, c):
         q.add_argument("--inception-weights", default=None, help="pt_inception-2015-12-05 weights (.safetensors, or a torch state dict)")
         q.add_argument("--batch-size", type=int, default=64)
         q.add_argument("--precision", choices=sorted(PRECISIONS), default="f16")
@@ -345,10 +416,41 @@ def main(argv=None):
         st.save(args.output)
         print(f"{args.output}: mu, sigma of {st.n} images")
         return args.output
-    pairs = [load_stats(f) if _is_stats(f) else stats_of_images(load_images(f), network(), args.batch_size).mean_cov() for f in (args.a, args.b)]
-    fid = frechet_distance(*pairs[0], *pairs[1])
-    print(f"fid: {fid:.6f}")
-    return fid
+    if args.cmd == "features":
+        images = load_images(args.images)
+        feat, st = features_of_images(images, network(), args.batch_size)
+        save_features(args.output, feat.cpu().numpy(), *st.mean_cov())
+        print(f"{args.output}: {FEATURES_KEY}, mu, sigma of {st.n} images")
+        return args.output
+    names = parse_metrics(args.metrics)
+    if names == ("fid",):
+        pairs = [load_stats(f) if _is_stats(f) else stats_of_images(load_images(f), network(), args.batch_size).mean_cov() for f in (args.a, args.b)]
+        fid = frechet_distance(*pairs[0], *pairs[1])
+        print(f"fid: {fid:.6f}")
+        return fid
+    kinds = ["features" if has_features(f) else "stats" if _is_stats(f) else "images" for f in (args.a, args.b)]
+    for f, kind in zip((args.a, args.b), kinds):               # refused before the network is built or a kernel runs
+        if kind == "stats":
+            raise ValueError(f"{f} holds statistics only: --metrics {args.metrics} needs the features of both sides; write them with "
+                             "`python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz`")
+        if kind == "images" and args.inception_weights is None:
+            raise ValueError(f"{f} is an image array: it needs --inception-weights")
+    feats, pairs = [], []
+    for f, kind in zip((args.a, args.b), kinds):
+        if kind == "features":
+            feats.append(torch.from_numpy(load_features(f)).to("cuda"))
+            pairs.append(load_stats(f) if "fid" in names else None)
+        else:
+            feat, st = features_of_images(load_images(f), network(), args.batch_size)
+            feats.append(feat)
+            pairs.append(st.mean_cov() if "fid" in names else None)
+    values = {}
+    if "fid" in names:
+        values["fid"] = frechet_distance(*pairs[0], *pairs[1])
+    values.update(extra_metrics(feats[0], feats[1], names, args))
+    for k, v in values.items():
+        print(f"{k}: {v:.6f}")
+    return values
 
 
 if __name__ == "__main__":

@@ -5,7 +5,9 @@ the batch shape and replayed for every batch (``--sampler dpm++``: DPM-Solver++ 
 latents clamped to [-1, 1] and quantised the same way; with ``--vae-weights FILE`` the native VAE decoder (map-dit_amd/vae.py) turns
 them into pixels first (``arr_0``: [n, 8S, 8S, 3]).  ``--fid-ref REF.npz --inception-weights FILE`` (together, and with pixels): the
 FID of the samples against the reference statistics, accumulated batch by batch on the device (map-dit_amd/fid.py), printed, returned
-and written to ``fid_samples/<output-file>.fid.json``; the array is written as before."""
+and written to ``fid_samples/<output-file>.fid.json``; the array is written as before.  ``--metrics fid,pr,kid`` (default ``fid``)
+adds precision / recall / density / coverage and KID (map-dit_amd/metrics.py) to that file (under its key ``metrics``) and to the output: ``--fid-ref`` must then
+be a file of ``python -m mapdit_amd.fid features`` (it holds ``pool_3``); the samples' features stay on the device."""
 from __future__ import annotations
 
 import argparse
@@ -43,12 +45,19 @@ def build_parser():
     p.add_argument("--inception-weights", type=str, default=None,
                    help="pt_inception-2015-12-05 weights (.safetensors, or a torch state dict) for --fid-ref")
     p.add_argument("--inception-precision", choices=["f16", "bf16"], default="f16", help="16-bit operand format of the feature network")
+    from .metrics import add_metric_flags
+    add_metric_flags(p)                                                   # --metrics fid,pr,kid (default fid): pr and kid need pool_3 in --fid-ref
     return p
 
 
 def check_fid_flags(args) -> bool:
     """Before anything is built: --fid-ref and --inception-weights go together, name files, and need pixels."""
+    from .metrics import parse_metrics
+    metrics = getattr(args, "metrics", None)
+    names = parse_metrics(metrics)                                        # (an unknown name is refused here too)
     if args.fid_ref is None and args.inception_weights is None:
+        if metrics is not None:
+            raise ValueError(f"--metrics {metrics} needs --fid-ref and --inception-weights: the metrics compare the samples with a reference")
         return False
     if args.fid_ref is None or args.inception_weights is None:
         raise ValueError("--fid-ref and --inception-weights go together: the FID needs the reference statistics and the feature network")
@@ -57,6 +66,15 @@ def check_fid_flags(args) -> bool:
             raise FileNotFoundError(f"{flag} {path}: no such file")
     if not args.use_vae:
         raise ValueError("--fid-ref needs pixels: the feature network reads 3-channel images, --use-vae false writes latents")
+    if names != ("fid",):
+        from .fid import features_rows
+        rows = features_rows(args.fid_ref)
+        if rows is None:
+            raise ValueError(f"--metrics {metrics} needs the reference's features: --fid-ref {args.fid_ref} holds no 'pool_3'; write one with "
+                             "`python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz`")
+        if "kid" in names and args.kid_subset_size > min(rows, args.num_samples):
+            raise ValueError(f"--metrics {metrics}: --kid-subset-size {args.kid_subset_size} exceeds the smaller set (--num-samples "
+                             f"{args.num_samples}, {rows} reference features)")
     return True
 
 
@@ -87,6 +105,9 @@ def main(argv=None):
             raise ValueError(f"--fid-ref {args.fid_ref}: statistics of {ref_mu.shape[0]} dimensions, the pool features have {FID.FEATURE_DIM}")
         fid_net = FID.InceptionFeatures.from_file(args.inception_weights, device, args.inception_precision)
         fid_stats = FID.FeatureStats(FID.FEATURE_DIM, device)
+        metric_names = FID.parse_metrics(args.metrics)
+        keep_feats = metric_names != ("fid",)                             # pr / kid: the samples' features stay on the device
+        feats = []
 
     n = args.batch_size
     use_cfg = args.cfg_scale > 1.0
@@ -115,7 +136,10 @@ def main(argv=None):
         if want_fid:                                                      # the stored bytes, cut where the array is cut
             keep = min(len(gathered[-1]), args.num_samples - fid_stats.n)
             if keep > 0:
-                fid_stats.update(fid_net.features(torch.from_numpy(gathered[-1][:keep]).to(device)))
+                feat = fid_net.features(torch.from_numpy(gathered[-1][:keep]).to(device))
+                fid_stats.update(feat)
+                if keep_feats:
+                    feats.append(feat)
     out = np.concatenate(gathered, axis=0)[: args.num_samples]
     os.makedirs(os.path.join(args.result_dir, "fid_samples"), exist_ok=True)
     path = os.path.join(args.result_dir, "fid_samples", args.output_file)
@@ -123,9 +147,17 @@ def main(argv=None):
     if want_fid:
         import json
         value = FID.frechet_distance(*fid_stats.mean_cov(), ref_mu, ref_sigma)
+        record = {"fid": value, "n": fid_stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}
+        extra = {}
+        if keep_feats:
+            ref_feat = torch.from_numpy(FID.load_features(args.fid_ref)).to(device)
+            extra = FID.extra_metrics(ref_feat, torch.cat(feats), metric_names, args)
+            record["metrics"] = extra                                      # (its "precision" is not the record's: that is the operand format)
         with open(path + ".fid.json", "w") as f:
-            json.dump({"fid": value, "n": fid_stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}, f)
+            json.dump(record, f)
         print(f"fid: {value:.6f}")
+        for k, v in extra.items():
+            print(f"{k}: {v:.6f}")
         return value
     return path
 
