@@ -698,6 +698,52 @@ int mapdit_step_draw(uint64_t seed, uint32_t step, long first_slot, int count, l
                      float* eps, float* x_syn, int64_t* t, double* u, double* z, int64_t* drop, int64_t* y_syn, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Counter-based sampler draws (sample_rng.py, --sample-rng counter of sample.py / sample_fid.py / sample_ema.py), additive within
+ * abi 5: everything random in the sampling of one image - its initial latent, its label, the noise of every reverse step - as a pure
+ * function of (seed, s), s the image's SAMPLE INDEX, 0 <= s < 2^32.  Neither the batch size, the position in a batch, the process nor
+ * anything drawn before enters a counter, so a sampling run can be sharded, stopped and continued.  No state, no host read, no
+ * allocation, no synchronisation: every entry is capturable.  THE LAYOUT BELOW IS A CONTRACT: a finished sample file has the same
+ * bits whatever history produced it only while it holds.
+ *   Generator, key and the fp32 normal recipe: those of the data set above (Philox4x32-10, key = (seed & 0xffffffff, seed >> 32),
+ *     normals within 8 ulp of the real value).  The tags below sit in counter word c3 and differ from TAG_PERM, TAG_NOISE and the
+ *     three tags of the step draws: no counter of one family is a counter of another.
+ *   z0[s][i]       = normal i & 3 of philox(counter = (i >> 2, s, 0, MAPDIT_TAG_SMPZ))        the initial latent
+ *   noise[s][t][i] = normal i & 3 of philox(counter = (i >> 2, s, t, MAPDIT_TAG_SMPN))        the noise of the step taken at t
+ *     t is the index into the (respaced) schedule the step is taken at: the value the step kernels' `t` array holds.  The step at
+ *     t = 0 adds no noise (and draws none).  DDIM with eta > 0 uses the same words.
+ *   y[s]           = (uint64(w0) * num_classes) >> 32 of philox(counter = (0, s, 0, MAPDIT_TAG_SMPY))     in [0, num_classes)
+ *   The sample index of row j is index[j], a DEVICE array (int64 [N]), not first + j: the two halves of a classifier-free-guidance
+ *     batch carry the same indices and so the same noise, a shard or a continued run passes the indices it owns, and
+ *     a captured graph is re-aimed by copying into that buffer.  The kernels read the LOW 32 BITS of an index (and, in
+ *     mapdit_sample_noise, of t); keeping an index inside [0, 2^32) is the caller's (SampleRNG.check_index refuses others).
+ *   mapdit_sample_draw: z fp32 [N][per] and y int64 [N] are nullable and a null one costs nothing; N >= 1, per >= 1, N * per <= 2^34,
+ *     num_classes >= 1 where y is asked for.
+ *   mapdit_sample_noise: noise fp32 [N][per] = noise[index[j]][t[j]], at t = 0 too (that a step adds none there is the step's
+ *     business).  What the hooked steps hand mapdit_obj_step_guided, and the yardstick of the two fused steps below.
+ *   mapdit_psample_step_counter: mapdit_psample_step (EPSILON / LEARNED_RANGE) with the noise generated in the kernel; the SAME BITS
+ *     as mapdit_psample_step fed with mapdit_sample_noise's tensor.
+ *   mapdit_obj_step_counter: mapdit_obj_step's mode 0 (p_sample, every mean / variance type) and mode 1 (DDIM, eta >= 0) likewise,
+ *     the same bits as mapdit_obj_step on that tensor; mode 2 (the reverse ODE) draws no noise and is refused.
+ *   In all four one lane makes one Philox call for four consecutive normals of one row; the steps load the lane's four x, mean-channel
+ *     ([n][e]) and variance-channel ([n][per + e]) values and store four results.  Where per % 4 == 0 and every plane is 16-byte
+ *     aligned each moves as 16 bytes, otherwise element by element (the ragged tail, a plane off a 16-byte boundary).  A lane reads
+ *     all it needs before it writes and no two lanes share an element: `sample` MAY BE `x` ITSELF (an in-place step); pred_xstart
+ *     (nullable) overlaps nothing, and no partial overlap is accepted.  A timestep outside [0, nsteps) is clamped and recorded for
+ *     mapdit_device_error_poll.  The tags are fixed: changing one changes every run.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define MAPDIT_TAG_SMPZ 0x534D505A
+#define MAPDIT_TAG_SMPN 0x534D504E
+#define MAPDIT_TAG_SMPY 0x534D5059
+int mapdit_sample_draw(uint64_t seed, const int64_t* index, int N, long per, int num_classes, float* z, int64_t* y, void* stream);
+int mapdit_sample_noise(uint64_t seed, const int64_t* index, const int64_t* t, int N, long per, float* noise, void* stream);
+int mapdit_psample_step_counter(const float* model_out, const float* x, uint64_t seed, const int64_t* index, const int64_t* t,
+                                const float* tab, int nsteps, int clip_denoised, float* sample, float* pred_xstart, int N,
+                                int per_sample, void* stream);
+int mapdit_obj_step_counter(const float* model_out, const float* x, uint64_t seed, const int64_t* index, const int64_t* t,
+                            const float* tab, const float* otab, int nsteps, int mean_type, int var_type, int clip_denoised, int mode,
+                            float eta, float* sample, float* pred_xstart, int N, int per_sample, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Engine: the whole DiT forward / backward sequenced from C++ on one stream (src/dit.py:70-105 and its autograd).
  * ------------------------------------------------------------------------------------------------------------ */
 enum { MAPDIT_OFF_MP_SILU = 1, MAPDIT_OFF_MP_RESIDUAL = 2, MAPDIT_OFF_MP_POS_ENC = 4, MAPDIT_OFF_MP_EMBEDDING = 8,

@@ -161,6 +161,7 @@ int mapdit_dev_error_take_diffusion(hipStream_t st, int* out);
 int mapdit_dev_error_take_precise(hipStream_t st, int* out);
 int mapdit_dev_error_take_tsampler(hipStream_t st, int* out);
 int mapdit_dev_error_take_flow(hipStream_t st, int* out);
+int mapdit_dev_error_take_samplerng(hipStream_t st, int* out);
 
 // ---- entry points one translation unit offers another, outside the C ABI (per operand format: MD_SYM) -----------------------------
 // attention72.hip -> attention.hip (the head_dim-72 MFMA kernels behind mapdit_attn_cos_* / mapdit_attn_sdpa_fwd)

@@ -853,15 +853,16 @@ int linear_dw(mapdit_engine* e, int pidx, const bf16_t* dy, int ld_dy, const bf1
 }  // namespace
 
 extern "C" int mapdit_device_error_poll(void* stream) {
-    int a = 0, a2 = 0, b = 0, c = 0, d = 0, f = 0;
+    int a = 0, a2 = 0, b = 0, c = 0, d = 0, f = 0, g = 0;
     const int rc = mapdit_dev_error_take_embed((hipStream_t)stream, &a) | mapdit_dev_error_take_embed_f16((hipStream_t)stream, &a2) |
                    mapdit_dev_error_take_diffusion((hipStream_t)stream, &b) | mapdit_dev_error_take_precise((hipStream_t)stream, &c) |
-                   mapdit_dev_error_take_tsampler((hipStream_t)stream, &d) | mapdit_dev_error_take_flow((hipStream_t)stream, &f);
+                   mapdit_dev_error_take_tsampler((hipStream_t)stream, &d) | mapdit_dev_error_take_flow((hipStream_t)stream, &f) |
+                   mapdit_dev_error_take_samplerng((hipStream_t)stream, &g);
     if (rc) {
         mapdit_set_error("device_error_poll: reading the device error words failed");
         return MAPDIT_ERR_HIP;
     }
-    const int code = a | a2 | b | c | d | f;
+    const int code = a | a2 | b | c | d | f | g;
     if (code & MAPDIT_DEVERR_LABEL) {
         mapdit_set_error("index out of range: a class label outside [0, embedding rows) reached the label embedding (the kernels "
                          "clamped it; results of that call are invalid)");

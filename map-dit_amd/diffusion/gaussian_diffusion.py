@@ -466,6 +466,32 @@ class GaussianDiffusion:
                                  x.shape[0], x[0].numel(), L.cur_stream())
         return sample, xstart
 
+    def _counter_step(self, model_output, x, t, rng, index, clip_denoised, mode, eta=0.0):
+        """The unhooked stochastic step with its noise generated in the kernel from (rng.seed, index[j], t[j]): the default
+        objective's p_sample is mapdit_psample_step_counter, everything else mapdit_obj_step_counter -> (sample, pred_xstart)."""
+        x = self._prep(x)
+        mo = self._prep(model_output)
+        sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            if mode == _STEP_PSAMPLE and self._is_default():
+                L.lib().psample_step_counter(mo.data_ptr(), x.data_ptr(), rng.seed, index.data_ptr(), t.data_ptr(),
+                                             self._tables(x.device).data_ptr(), self.num_timesteps, int(bool(clip_denoised)),
+                                             sample.data_ptr(), xstart.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
+            else:
+                mean_type, var_type, _ = self._kinds()
+                L.lib().obj_step_counter(mo.data_ptr(), x.data_ptr(), rng.seed, index.data_ptr(), t.data_ptr(),
+                                         self._tables(x.device).data_ptr(), self._obj_tables(x.device).data_ptr(), self.num_timesteps,
+                                         mean_type, var_type, int(bool(clip_denoised)), mode, float(eta), sample.data_ptr(),
+                                         xstart.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
+        return sample, xstart
+
+    @staticmethod
+    def _rng_rows(rng, index, rows):
+        """The loops' rng= / index= pair, checked once, with the index laid out over the batch's rows (sample_rng.rows_index)."""
+        from ..sample_rng import pair, rows_index
+        rng, index = pair(rng, index)
+        return rng, (None if rng is None else rows_index(index, rows))
+
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """reference gaussian_diffusion.py:254-332 (mean = the p_sample kernel with zero noise)."""
         self._supported()
@@ -511,8 +537,14 @@ class GaussianDiffusion:
         return {"mean": mean, "variance": torch.exp(log_var), "log_variance": log_var, "pred_xstart": xstart, "extra": None,
                 "model_output": model_output}
 
-    def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None):
-        """reference gaussian_diffusion.py:376-417."""
+    def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, rng=None, index=None):
+        """reference gaussian_diffusion.py:376-417.  rng= (a SampleRNG) with index= (the sample index of every row): the step's noise is
+        the contract's noise[index[j]][t[j]] instead of a torch.randn_like draw - generated inside the step kernel, or materialised
+        for a hooked step."""
+        rng, index = self._rng_rows(rng, index, x.shape[0])
+        return self._p_sample(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, rng, index)
+
+    def _p_sample(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, rng, index):
         self._supported()
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
@@ -520,8 +552,11 @@ class GaussianDiffusion:
                         else self._model_output(model, x, t, model_kwargs))
         if denoised_fn is not None or cond_fn is not None:
             xin, grad = self._hooks(model_output, x, t, denoised_fn, cond_fn, model_kwargs)
-            noise = torch.randn_like(x)
+            noise = torch.randn_like(x) if rng is None else rng.noise_checked(index, t, x.shape)
             sample, xstart, _ = self._guided_step(model_output, x, t, noise, clip_denoised, _STEP_PSAMPLE, xstart_in=xin, cond_grad=grad)
+            return {"sample": sample, "pred_xstart": xstart}
+        if rng is not None:
+            sample, xstart = self._counter_step(model_output, x, t, rng, index, clip_denoised, _STEP_PSAMPLE)
             return {"sample": sample, "pred_xstart": xstart}
         noise = torch.randn_like(x)
         sample, xstart = self._step_math(model_output, x, t, noise, clip_denoised)
@@ -540,8 +575,13 @@ class GaussianDiffusion:
                               int(bool(reverse)), sample.data_ptr(), xstart.data_ptr(), x.shape[0], x[0].numel(), L.cur_stream())
         return sample, xstart
 
-    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
-        """reference gaussian_diffusion.py:513-567."""
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, rng=None,
+                    index=None):
+        """reference gaussian_diffusion.py:513-567.  rng= / index= as p_sample takes them: the same noise words, scaled by sigma(eta)."""
+        rng, index = self._rng_rows(rng, index, x.shape[0])
+        return self._ddim_sample(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, rng, index)
+
+    def _ddim_sample(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, rng, index):
         self._supported()
         x = self._prep(x)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
@@ -549,8 +589,11 @@ class GaussianDiffusion:
                         else self._model_output(model, x, t, model_kwargs))
         if denoised_fn is not None or cond_fn is not None:
             xin, grad = self._hooks(model_output, x, t, denoised_fn, cond_fn, model_kwargs)
-            noise = torch.randn_like(x)
+            noise = torch.randn_like(x) if rng is None else rng.noise_checked(index, t, x.shape)
             sample, xstart, _ = self._guided_step(model_output, x, t, noise, clip_denoised, _STEP_DDIM, eta, xstart_in=xin, cond_grad=grad)
+            return {"sample": sample, "pred_xstart": xstart}
+        if rng is not None:               # (eta = 0: sigma is 0 and the words drop out - the deterministic solver takes only its start)
+            sample, xstart = self._counter_step(model_output, x, t, rng, index, clip_denoised, _STEP_DDIM, eta)
             return {"sample": sample, "pred_xstart": xstart}
         noise = torch.randn_like(x)
         sample, xstart = self._ddim_math(model_output, x, t, noise, clip_denoised, eta, False)
@@ -628,22 +671,23 @@ class GaussianDiffusion:
         return {"total_bpd": total, "prior_bpd": prior, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                         device=None, progress=False, eta=0.0):
-        """reference gaussian_diffusion.py:607-636."""
+                         device=None, progress=False, eta=0.0, rng=None, index=None):
+        """reference gaussian_diffusion.py:607-636.  rng= / index=: as p_sample_loop."""
         final = None
         for sample in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                         denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs,
-                                                        device=device, progress=progress, eta=eta):
+                                                        device=device, progress=progress, eta=eta, rng=rng, index=index):
             final = sample
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                     model_kwargs=None, device=None, progress=False, eta=0.0):
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, rng=None, index=None):
         """reference gaussian_diffusion.py:638-680."""
+        rng, index = self._rng_rows(rng, index, shape[0])
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else torch.randn(*shape, device=device)
+        img = noise if noise is not None else self._start(shape, device, rng, index)
         indices = list(range(self.num_timesteps))[::-1]
         if progress:
             from tqdm.auto import tqdm
@@ -651,30 +695,43 @@ class GaussianDiffusion:
         for i in indices:
             t = torch.full((shape[0],), i, device=device, dtype=torch.int64)
             with torch.no_grad():
-                out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                       model_kwargs=model_kwargs, eta=eta)
+                if rng is None:
+                    out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                           model_kwargs=model_kwargs, eta=eta)
+                else:
+                    out = self._ddim_sample(model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, rng, index)
                 yield out
                 img = out["sample"]
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                      device=None, progress=False):
-        """reference gaussian_diffusion.py:419-462."""
+                      device=None, progress=False, rng=None, index=None):
+        """reference gaussian_diffusion.py:419-462.  rng= (a SampleRNG) and index= (one sample index per row, or per row of one half of
+        a classifier-free-guidance batch: the two halves then carry the same indices) go together: the initial latent (where noise is
+        None) and every step's noise are the contract's draws of those indices, whatever else the process has drawn."""
         final = None
         for sample in self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                      denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs,
-                                                     device=device, progress=progress):
+                                                     device=device, progress=progress, rng=rng, index=index):
             final = sample
         with torch.cuda.device(final["sample"].device):
             L.lib().device_error_poll(L.cur_stream())      # out-of-range label / timestep anywhere in the loop -> MapditError
         return final["sample"]
 
+    @staticmethod
+    def _start(shape, device, rng, index):
+        """The loops' initial latent where none is given: torch.randn, or the rng's latents of the rows' sample indices."""
+        if rng is None:
+            return torch.randn(*shape, device=device)
+        return rng.latents(index, tuple(shape[1:]))
+
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                  model_kwargs=None, device=None, progress=False):
+                                  model_kwargs=None, device=None, progress=False, rng=None, index=None):
         """reference gaussian_diffusion.py:464-511."""
+        rng, index = self._rng_rows(rng, index, shape[0])
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else torch.randn(*shape, device=device)
+        img = noise if noise is not None else self._start(shape, device, rng, index)
         indices = list(range(self.num_timesteps))[::-1]
         if progress:
             from tqdm.auto import tqdm
@@ -682,8 +739,11 @@ class GaussianDiffusion:
         for i in indices:
             t = torch.full((shape[0],), i, device=device, dtype=torch.int64)
             with torch.no_grad():
-                out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                    model_kwargs=model_kwargs)
+                if rng is None:
+                    out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                        model_kwargs=model_kwargs)
+                else:                      # (the pair was checked once, above: no host read per step)
+                    out = self._p_sample(model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, rng, index)
                 yield out
                 img = out["sample"]
 
@@ -702,35 +762,38 @@ class GaussianDiffusion:
         return sample, xstart
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                               device=None, progress=False, num_steps=20, order=2, spacing="logsnr", lower_order_final=True):
+                               device=None, progress=False, rng=None, index=None, num_steps=20, order=2, spacing="logsnr",
+                               lower_order_final=True):
         """Deterministic sampling with the multistep DPM-Solver++ (Lu et al. 2022; order 2 = "2M", order 1 = the DDIM eta = 0 update):
         at most ``num_steps`` model evaluations on timesteps of this diffusion chosen by ``spacing`` ("logsnr": nearest to equal steps
         of the log signal-to-noise ratio, duplicates dropped; "uniform": ``space_timesteps``).  Signature and hooks as
-        ``ddim_sample_loop``; the variance channels of a learned-range model are ignored."""
+        ``ddim_sample_loop``; the variance channels of a learned-range model are ignored.  rng= / index=: the start (where noise is None) is
+        the rng's latents of those sample indices; the solver draws nothing else."""
         final = None
         for sample in self.dpm_solver_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                               denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs,
                                                               device=device, progress=progress, num_steps=num_steps, order=order,
-                                                              spacing=spacing, lower_order_final=lower_order_final):
+                                                              spacing=spacing, lower_order_final=lower_order_final, rng=rng, index=index):
             final = sample
         with torch.cuda.device(final["sample"].device):
             L.lib().device_error_poll(L.cur_stream())      # out-of-range label / timestep / step index anywhere in the loop
         return final["sample"]
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                           model_kwargs=None, device=None, progress=False, num_steps=20, order=2, spacing="logsnr",
-                                           lower_order_final=True):
+                                           model_kwargs=None, device=None, progress=False, rng=None, index=None, num_steps=20, order=2,
+                                           spacing="logsnr", lower_order_final=True):
         """Yields {"sample", "pred_xstart"} per solver step.  After the model, an unhooked step is one mapdit_dpm_step launch.
         denoised_fn sees the raw x0 prediction (mapdit_obj_xstart) and its result is clipped inside the step; cond_fn goes through
         condition_score (mapdit_obj_step_guided without a sample: x0 moved by the gradient after the clip, not clipped again), and
         the conditioned x0 is what the solver uses and remembers."""
         self._supported()
+        rng, index = self._rng_rows(rng, index, shape[0])
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
         tabs = self._dpm_tables(torch.device(device), num_steps, order, spacing, lower_order_final)
         taus = tabs[2]
-        img = self._prep(noise if noise is not None else torch.randn(*shape, device=device))
+        img = self._prep(noise if noise is not None else self._start(shape, device, rng, index))
         hist = torch.zeros_like(img)          # c_1 = 0 on the first step, but 0 x NaN of an uninitialised buffer is NaN
         indices = list(range(len(taus)))[::-1]
         if progress:

@@ -243,28 +243,35 @@ class RectifiedFlow:
                               L.ptr(base_out), L.ptr(xstart), base.shape[0], base[0].numel(), groups, L.cur_stream())
         return sample, xstart
 
-    def sample_loop(self, model, shape, noise=None, model_kwargs=None, device=None, progress=False, num_steps=50, order=1):
+    def sample_loop(self, model, shape, noise=None, model_kwargs=None, device=None, progress=False, num_steps=50, order=1, rng=None,
+                    index=None):
         """Deterministic sampling along the flow ODE: order 1 Euler (one model evaluation per step), order 2 Heun (2 K' - 1 for K' steps),
         on at most ``num_steps`` steps of the timestep grid (``_schedule``).  ``model(x, t, **model_kwargs)`` returns the velocity on its
-        first C channels."""
+        first C channels.  rng= (a SampleRNG) with index= (the rows' sample indices): the start, where noise is None, is the rng's latents
+        of those indices; the solver draws nothing else."""
         final = None
         for sample in self.sample_loop_progressive(model, shape, noise=noise, model_kwargs=model_kwargs, device=device, progress=progress,
-                                                   num_steps=num_steps, order=order):
+                                                   num_steps=num_steps, order=order, rng=rng, index=index):
             final = sample
         with torch.cuda.device(final["sample"].device):
             L.lib().device_error_poll(L.cur_stream())      # out-of-range label / timestep / evaluation index anywhere in the loop
         return final["sample"]
 
-    def sample_loop_progressive(self, model, shape, noise=None, model_kwargs=None, device=None, progress=False, num_steps=50, order=1):
+    def sample_loop_progressive(self, model, shape, noise=None, model_kwargs=None, device=None, progress=False, num_steps=50, order=1,
+                                rng=None, index=None):
         """Yields {"sample", "pred_xstart", "committed"} per model evaluation; after the model an evaluation is one mapdit_flow_step
         launch.  "sample" is the next evaluation point: the solver's state where "committed" is true, Heun's Euler predictor where it
         is false.  "pred_xstart" = x - s v at the evaluation point."""
+        from ..sample_rng import pair, rows_index
+        rng, index = pair(rng, index)
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
         tabs = self._plan_tables(torch.device(device), num_steps, order)
         ts, kinds = tabs[3], tabs[4]
         J = len(ts)
+        if noise is None and rng is not None:
+            noise = rng.latents(rows_index(index, shape[0]), tuple(shape[1:]))
         img = self._prep(noise if noise is not None else torch.randn(*shape, device=device))
         assert tuple(img.shape) == tuple(shape), (tuple(img.shape), tuple(shape))
         base = img

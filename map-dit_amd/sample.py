@@ -50,14 +50,20 @@ def main(argv=None):
     vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
 
     n = 4                                                                  # sample.py:40
-    z = torch.randn(n, train_args["in_channels"], train_args["input_size"], train_args["input_size"], device=device)
+    rng = S.make_rng(args, device)                                        # --sample-rng counter: the image at grid position j is sample index j
+    index = None if rng is None else list(range(n))
+    if rng is None:
+        z = torch.randn(n, train_args["in_channels"], train_args["input_size"], train_args["input_size"], device=device)
+    else:
+        z = rng.latents(index, (train_args["in_channels"], train_args["input_size"], train_args["input_size"]))
     if not 0 <= args.class_label < int(train_args["num_classes"]):       # the reference fails inside F.embedding (IndexError)
         raise ValueError(f"--class-label {args.class_label} is outside the trained model's {train_args['num_classes']} classes")
     y = torch.tensor([args.class_label] * n, device=device)
     z = torch.cat([z, z], dim=0)                                          # CFG batch: conditional | null class
     y = torch.cat([y, torch.tensor([train_args["num_classes"]] * n, device=device)], dim=0)
     diffusion, solver = S.make_diffusion(args, train_args)
-    samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=not args.no_graph, progress=True, **solver)
+    samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=not args.no_graph, progress=True, rng=rng, index=index,
+                            **solver)
     samples, _ = samples.chunk(2, dim=0)
     samples = S.denormalize(samples, train_args)
     if vae is not None:

@@ -48,6 +48,9 @@ def main(argv=None):
     if not 0 <= args.class_label < int(train_args["num_classes"]):       # the reference fails inside F.embedding (IndexError)
         raise ValueError(f"--class-label {args.class_label} is outside the trained model's {train_args['num_classes']} classes")
     y = torch.cat([torch.tensor([args.class_label] * n), torch.tensor([train_args["num_classes"]] * n)]).to(device)
+    rng = S.make_rng(args, device)                                        # --sample-rng counter: row j is sample index j under every EMA width
+    index = None if rng is None else list(range(n))
+    ctr = {} if rng is None else dict(index=index)
     graphed = None
     res = []
     for std in EMA_STDS:
@@ -55,16 +58,16 @@ def main(argv=None):
             torch.manual_seed(args.seed)                                   # same noise for every profile
         sd = calculate_posthoc_ema(std, os.path.join(args.result_dir, "ema"), verbose=False)
         model.load_state_dict({k: v.float() for k, v in sd.items()})
-        z = torch.randn(n, *shape[1:], device=device)
+        z = torch.randn(n, *shape[1:], device=device) if rng is None else rng.latents(index, shape[1:])
         z = torch.cat([z, z], 0)
         if args.no_graph:
-            samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=False, progress=True, **solver)
+            samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale, use_graph=False, progress=True, rng=rng, index=index, **solver)
         else:
             if graphed is None:              # weights are re-imaged per replay set: the graph reads the cached bf16 images
-                graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale, **solver)
+                graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale, rng=rng, **solver)
             else:
                 graphed.refresh_weights()
-            samples = graphed.sample(z)
+            samples = graphed.sample(z, **ctr)
         samples, _ = samples.chunk(2, dim=0)
         res.append(samples)
     samples = torch.stack(res, dim=1)

@@ -7,7 +7,15 @@ them into pixels first (``arr_0``: [n, 8S, 8S, 3]).  ``--fid-ref REF.npz --incep
 FID of the samples against the reference statistics, accumulated batch by batch on the device (map-dit_amd/fid.py), printed, returned
 and written to ``fid_samples/<output-file>.fid.json``; the array is written as before.  ``--metrics fid,pr,kid`` (default ``fid``)
 adds precision / recall / density / coverage and KID (map-dit_amd/metrics.py) to that file (under its key ``metrics``) and to the output: ``--fid-ref`` must then
-be a file of ``python -m mapdit_amd.fid features`` (it holds ``pool_3``); the samples' features stay on the device."""
+be a file of ``python -m mapdit_amd.fid features`` (it holds ``pool_3``); the samples' features stay on the device.
+
+``--sample-rng counter``: sample i - its latent, its label, the noise of every step - is a function of (``--seed``, i) alone
+(map-dit_amd/sample_rng.py), batch b holds the sample indices [b n, (b + 1) n) (n = ``--batch-size``), and every finished batch is
+written as ``fid_samples/<output-file>.parts/<first>-<end>.npy`` beside a ``manifest.json`` of everything the bytes depend on.  Running
+the same command again skips the batches whose part exists (that is resuming); ``--shard R/W`` takes the batches with b % W == R, so W
+processes on W GPUs share a run; whichever process finds every part present assembles ``arr_0`` in index order and computes the
+metrics from the assembled bytes.  The finished file has the same bits whatever history produced it.  A manifest that differs in any
+key is refused before any model is built."""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +55,205 @@ def build_parser():
     p.add_argument("--inception-precision", choices=["f16", "bf16"], default="f16", help="16-bit operand format of the feature network")
     from .metrics import add_metric_flags
     add_metric_flags(p)                                                   # --metrics fid,pr,kid (default fid): pr and kid need pool_3 in --fid-ref
+    p.add_argument("--shard", type=str, default="0/1",
+                   help="R/W with --sample-rng counter: this process takes the batches b with b %% W == R (start W processes by hand or from a job script)")
     return p
+
+
+# ---- --sample-rng counter: the host logic of parts, shards and resuming (pure functions: no GPU, no model) -----------------------
+
+def parse_shard(text: str):
+    """"R/W" -> (R, W); W >= 1 and 0 <= R < W."""
+    try:
+        r, w = (int(v) for v in str(text).split("/"))
+    except ValueError:
+        raise ValueError(f"--shard {text}: expected R/W, two integers") from None
+    if w < 1 or not 0 <= r < w:
+        raise ValueError(f"--shard {text}: needs W >= 1 and 0 <= R < W")
+    return r, w
+
+
+def plan_batches(num_samples: int, batch_size: int, shard=(0, 1)):
+    """[(b, first, end)]: the batches b with b % W == R of a run of `num_samples` samples in batches of `batch_size`.  Batch b holds the
+    sample indices [first, end) = [b n, min((b + 1) n, num_samples)): the last one is cut where the array is cut."""
+    if num_samples < 1 or batch_size < 1:
+        raise ValueError(f"--num-samples {num_samples} and --batch-size {batch_size} must both be >= 1")
+    r, w = shard
+    return [(b, b * batch_size, min((b + 1) * batch_size, num_samples))
+            for b in range(-(-num_samples // batch_size)) if b % w == r]
+
+
+def check_shard_flags(args):
+    """Before anything is built: --shard is R/W with R < W, and means something under --sample-rng counter only -> (R, W)."""
+    shard = parse_shard(args.shard)
+    if args.sample_rng == "counter" and args.seed is None:
+        raise ValueError("--sample-rng counter needs a --seed: the seed is the generator's key")
+    if shard != (0, 1) and args.sample_rng != "counter":
+        raise ValueError(f"--shard {args.shard} needs --sample-rng counter: under the torch generator a sample depends on everything its "
+                         "process drew before it, so a run cannot be split")
+    return shard
+
+
+MANIFEST_KEYS = ("sample_rng", "seed", "num_samples", "batch_size", "sampler", "num_sampling_steps", "solver_order", "solver_spacing",
+                 "cfg_scale", "precision", "ema_std", "ckpt", "num_classes", "use_vae", "vae_weights", "vae_path", "vae_precision",
+                 "vae_norm_groups", "objective", "flow_shift", "graph")
+
+
+def make_manifest(args, train_args: dict) -> dict:
+    """Everything the bytes of a part depend on (the shard is not among them: a part is the same whoever makes it)."""
+    vae = bool(args.use_vae)
+    return {"sample_rng": "counter/1",                                     # the layout of mapdit.h, "Counter-based sampler draws"
+            "seed": args.seed, "num_samples": args.num_samples, "batch_size": args.batch_size, "sampler": args.sampler,
+            "num_sampling_steps": args.num_sampling_steps,
+            "solver_order": args.solver_order if args.sampler == "dpm++" else None,
+            "solver_spacing": args.solver_spacing if args.sampler == "dpm++" else None,
+            "cfg_scale": float(args.cfg_scale), "precision": args.precision,
+            "ema_std": float(args.ema_std) if args.ckpt is None else None, "ckpt": args.ckpt,
+            "num_classes": int(args.num_classes), "use_vae": vae,
+            "vae_weights": os.path.abspath(args.vae_weights) if vae and args.vae_weights else None,
+            "vae_path": args.vae_path if vae and not args.vae_weights else None,
+            "vae_precision": args.vae_precision if vae and args.vae_weights else None,
+            "vae_norm_groups": args.vae_norm_groups if vae and args.vae_weights else None,
+            "objective": (train_args or {}).get("objective", "diffusion"),
+            "flow_shift": float((train_args or {}).get("flow_shift", 1.0)) if args.sampler in S.FLOW_SAMPLERS else None,
+            "graph": not args.no_graph}
+
+
+def check_manifest(old: dict, new: dict):
+    """A parts directory holds the batches of ONE run: any key that differs (or is missing on one side) is refused, named with both
+    values."""
+    for k in sorted(set(old) | set(new)):
+        if k not in old or k not in new or old[k] != new[k]:
+            raise ValueError(f"the parts directory was written by a run with {k} = {old.get(k, '<absent>')!r}; this run has "
+                             f"{k} = {new.get(k, '<absent>')!r}.  Parts of two runs do not mix: use another --output-file, or remove the directory")
+
+
+def parts_dir(result_dir: str, output_file: str) -> str:
+    return os.path.join(result_dir, "fid_samples", output_file + ".parts")
+
+
+def part_path(pdir: str, first: int, end: int) -> str:
+    return os.path.join(pdir, f"{first}-{end}.npy")
+
+
+def _replace_into(path: str, write):
+    """Atomic write: `write(file)` into a temporary name beside `path`, then os.replace - a reader sees the old file or the whole new one,
+    and two processes writing the same bytes do no harm."""
+    tmp = f"{path}.tmp.{os.getpid()}"
+    with open(tmp, "wb") as f:
+        write(f)
+    os.replace(tmp, path)
+
+
+def part_done(path: str, rows: int, tail) -> bool:
+    """A finished part: a readable uint8 array of `rows` images of shape `tail`."""
+    if not os.path.isfile(path):
+        return False
+    try:
+        a = np.load(path, mmap_mode="r")
+    except (OSError, ValueError):
+        return False
+    return a.dtype == np.uint8 and a.shape == (rows, *tail)
+
+
+def open_manifest(pdir: str, manifest: dict):
+    """Compare with the directory's manifest.json, or write it (atomically: shards may start together)."""
+    import json
+    os.makedirs(pdir, exist_ok=True)
+    path = os.path.join(pdir, "manifest.json")
+    if os.path.isfile(path):
+        with open(path) as f:
+            check_manifest(json.load(f), manifest)
+    else:
+        _replace_into(path, lambda f: f.write(json.dumps(manifest, indent=1, sort_keys=True).encode()))
+
+
+def fid_record(args, path, out, device):
+    """--fid-ref under --sample-rng counter: the FID and --metrics in one pass over the assembled bytes, in batches of --batch-size from
+    index 0 - a function of the stored array alone -> the FID."""
+    import json
+
+    from . import fid as FID
+    ref_mu, ref_sigma = FID.load_stats(args.fid_ref)
+    if ref_mu.shape != (FID.FEATURE_DIM,):
+        raise ValueError(f"--fid-ref {args.fid_ref}: statistics of {ref_mu.shape[0]} dimensions, the pool features have {FID.FEATURE_DIM}")
+    fid_net = FID.InceptionFeatures.from_file(args.inception_weights, device, args.inception_precision)
+    fid_stats = FID.FeatureStats(FID.FEATURE_DIM, device)
+    metric_names = FID.parse_metrics(args.metrics)
+    keep_feats = metric_names != ("fid",)
+    feats = []
+    for i in range(0, len(out), args.batch_size):
+        feat = fid_net.features(torch.from_numpy(out[i:i + args.batch_size]).to(device))
+        fid_stats.update(feat)
+        if keep_feats:
+            feats.append(feat)
+    value = FID.frechet_distance(*fid_stats.mean_cov(), ref_mu, ref_sigma)
+    record = {"fid": value, "n": fid_stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}
+    extra = {}
+    if keep_feats:
+        ref_feat = torch.from_numpy(FID.load_features(args.fid_ref)).to(device)
+        extra = FID.extra_metrics(ref_feat, torch.cat(feats), metric_names, args)
+        record["metrics"] = extra
+    _replace_into(path + ".fid.json", lambda f: f.write(json.dumps(record).encode()))
+    print(f"fid: {value:.6f}")
+    for k, v in extra.items():
+        print(f"{k}: {v:.6f}")
+    return value
+
+
+def run_counter(args, train_args, device, want_fid, shard):
+    """main() under --sample-rng counter, from the manifest on.  Returns the parts directory while parts are missing, else what main()
+    returns: the FID with --fid-ref, the .npz path without."""
+    n = args.batch_size
+    pdir = parts_dir(args.result_dir, args.output_file)
+    open_manifest(pdir, make_manifest(args, train_args))                  # a differing run is refused here, before any model is built
+    size, chans = int(train_args["input_size"]), int(train_args["in_channels"])
+    tail = (8 * size, 8 * size, 3) if args.use_vae else (size, size, chans)
+    todo = [(b, first, end) for b, first, end in plan_batches(args.num_samples, n, shard)
+            if not part_done(part_path(pdir, first, end), end - first, tail)]
+    if todo:
+        rng = S.make_rng(args, device)
+        model = get_model(train_args).to(device)
+        S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=False)
+        model.gemm_precision = args.precision
+        vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
+        diffusion, solver = S.make_diffusion(args, train_args)
+        use_cfg = args.cfg_scale > 1.0
+        shape = (2 * n if use_cfg else n, chans, size, size)
+        null = torch.full((n,), args.num_classes, device=device, dtype=torch.int64)
+        graphed = None
+        for b, first, end in todo:
+            index = list(range(b * n, (b + 1) * n))                       # the whole batch: indices beyond --num-samples are drawn and dropped
+            z, y = rng.latents(index, shape[1:]), rng.labels(index, args.num_classes)
+            if use_cfg:
+                z, y = torch.cat([z, z], dim=0), torch.cat([y, null], dim=0)
+            if args.no_graph:
+                samples = S.run_sampler(model, diffusion, z, y, args.cfg_scale if use_cfg else None, use_graph=False, rng=rng, index=index,
+                                        **solver)
+            else:
+                if graphed is None:
+                    graphed = S.GraphedSampler(model, diffusion, shape, y, args.cfg_scale if use_cfg else None, rng=rng, **solver)
+                graphed.y.copy_(y)
+                samples = graphed.sample(z, index=index)
+            if use_cfg:
+                samples, _ = samples.chunk(2, dim=0)
+            samples = S.denormalize(samples, train_args)
+            if vae is not None:
+                samples = vae.decode(samples).sample
+            arr = np.ascontiguousarray(S.to_uint8_nhwc(samples)[: end - first])
+            assert arr.shape == (end - first, *tail), (arr.shape, tail)
+            _replace_into(part_path(pdir, first, end), lambda f: np.save(f, arr))
+    every = plan_batches(args.num_samples, n)
+    missing = [(first, end) for _, first, end in every if not part_done(part_path(pdir, first, end), end - first, tail)]
+    if missing:
+        print(f"{len(every) - len(missing)} of {len(every)} parts in {pdir}; missing sample ranges: " + ", ".join(f"{a}-{e}" for a, e in missing))
+        return pdir
+    out = np.concatenate([np.load(part_path(pdir, first, end)) for _, first, end in every], axis=0)
+    path = os.path.join(args.result_dir, "fid_samples", args.output_file)
+    if not path.endswith(".npz"):
+        path += ".npz"                                                     # (np.savez appends it to a name; a file object takes none)
+    _replace_into(path, lambda f: np.savez(f, arr_0=out))
+    return fid_record(args, path, out, device) if want_fid else path
 
 
 def check_fid_flags(args) -> bool:
@@ -83,6 +289,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     S.check_vae_flags(args)                                               # a missing --vae-weights file ends the run before any model is built
     want_fid = check_fid_flags(args)                                      # (so does half of the FID flag pair)
+    shard = check_shard_flags(args)                                       # (and a --shard that is no R/W with R < W, or has no counter rng)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     device = torch.device("cuda")
@@ -93,6 +300,8 @@ def main(argv=None):
     elif args.num_classes != int(train_args["num_classes"]):
         raise ValueError(f"--num-classes {args.num_classes} != the trained model's num_classes {train_args['num_classes']} "
                          "(config.yaml): labels and the null label would fall outside its embedding table")
+    if args.sample_rng == "counter":
+        return run_counter(args, train_args, device, want_fid, shard)
     model = get_model(train_args).to(device)
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=False)
     model.gemm_precision = args.precision

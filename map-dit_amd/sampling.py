@@ -30,10 +30,15 @@ class GraphedSampler:
     sampler: "ancestral" (p_sample, one replay per timestep of the diffusion) or "dpm++" (DPM-Solver++ with num_steps / order / spacing /
     lower_order_final as ``diffusion.dpm_solver_sample_loop`` takes them; one replay per solver step, ``self.num_replays`` of them), or
     "flow": `diffusion` is a ``flow.RectifiedFlow`` and num_steps / order (1 Euler, 2 Heun) are ``flow.sample_loop``'s; one replay per
-    model evaluation.  A RectifiedFlow with another sampler, or "flow" with a GaussianDiffusion, is refused; clip_denoised does not apply."""
+    model evaluation.  A RectifiedFlow with another sampler, or "flow" with a GaussianDiffusion, is refused; clip_denoised does not apply.
+
+    rng: a ``sample_rng.SampleRNG``.  The sampler then owns an int64 ``index`` buffer (one sample index per row) and the captured
+    ancestral step is ``mapdit_psample_step_counter`` / ``mapdit_obj_step_counter``, in place: the noise of row j at step t is the
+    contract's ``noise[index[j]][t]``, generated in the kernel - no generator launch, no copy.  ``sample(index=...)`` copies the indices
+    in (a guidance batch takes n of them and both halves carry them) and draws the start from them: the same graph, another aim."""
 
     def __init__(self, model, diffusion, shape, y, cfg_scale=None, clip_denoised=False, sampler="ancestral", num_steps=20, order=2,
-                 spacing="logsnr", lower_order_final=True):
+                 spacing="logsnr", lower_order_final=True, rng=None):
         assert not model.training, "sampling runs the model in eval mode"
         if sampler not in ("ancestral", "dpm++", "flow"):
             raise ValueError(f'sampler must be "ancestral", "dpm++" or "flow"; got {sampler!r}')
@@ -42,6 +47,9 @@ class GraphedSampler:
             raise ValueError(f'sampler="flow" runs a flow.RectifiedFlow and "ancestral" / "dpm++" a GaussianDiffusion; got sampler={sampler!r} '
                              f"with a {type(diffusion).__name__}")
         self.flow = None
+        self.rng = rng
+        # (index 0 in every row is a valid aim for the warm-up and the capture)
+        self.index = None if rng is None else torch.zeros(shape[0], device=next(model.parameters()).device, dtype=torch.int64)
         if sampler == "flow":
             return self._init_flow(model, diffusion, shape, y, cfg_scale, num_steps, order)
         diffusion._supported()
@@ -133,6 +141,18 @@ class GraphedSampler:
             out = self.model.forward(self.img, mapped, self.y)
         else:
             out = self.model.forward_with_cfg(self.img, mapped, self.y, self.cfg_scale)
+        if self.rng is not None:          # in place: the counter kernels' sample may alias x
+            if self.otab is None:
+                L.lib().psample_step_counter(out.data_ptr(), self.img.data_ptr(), self.rng.seed, self.index.data_ptr(), self.t.data_ptr(),
+                                             self.tab.data_ptr(), d.num_timesteps, int(self.clip), self.img.data_ptr(), None,
+                                             self.img.shape[0], self.img[0].numel(), L.cur_stream())
+            else:
+                mean_type, var_type, _ = d._kinds()
+                L.lib().obj_step_counter(out.data_ptr(), self.img.data_ptr(), self.rng.seed, self.index.data_ptr(), self.t.data_ptr(),
+                                         self.tab.data_ptr(), self.otab.data_ptr(), d.num_timesteps, mean_type, var_type, int(self.clip),
+                                         0, 0.0, self.img.data_ptr(), None, self.img.shape[0], self.img[0].numel(), L.cur_stream())
+            self.t.sub_(1)
+            return
         noise = torch.randn_like(self.img)
         nxt = torch.empty_like(self.img)
         if self.otab is None:
@@ -171,8 +191,18 @@ class GraphedSampler:
         rt.weights_key = self.model._weights_key()
 
     @torch.no_grad()
-    def sample(self, noise=None, steps=None):
-        """Run the reverse chain from ``noise`` (or fresh N(0,1)); ``steps`` bounds the prefix (default: all)."""
+    def sample(self, noise=None, steps=None, index=None):
+        """Run the reverse chain from ``noise`` (or fresh N(0,1)); ``steps`` bounds the prefix (default: all).  A sampler built with an
+        rng needs ``index`` (one sample index per row, or per row of one half of a guidance batch) and draws the start from it unless
+        ``noise`` is given; without an rng an index is refused."""
+        if (index is None) != (self.rng is None):
+            raise ValueError("sample(index=...) needs a GraphedSampler built with rng=, and one built with rng= needs index=: "
+                             f"got index={'None' if index is None else 'given'}, rng={'None' if self.rng is None else 'given'}")
+        if self.rng is not None:                                          # checked here, outside the capture: the kernels read the low 32 bits
+            from .sample_rng import rows_index
+            self.index.copy_(rows_index(self.rng.check_index(index), self.img.shape[0]))
+            if noise is None:
+                noise = self.rng.latents(self.index, tuple(self.img.shape[1:]))
         n = self.num_replays
         if self.dpm is not None:
             self.hist.zero_()
@@ -317,7 +347,21 @@ def add_sampler_flags(parser):
                              "flow-heun: the ODE sampler of a run trained with --objective flow")
     parser.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="dpm++ only: 1 (DDIM) or 2 (2M)")
     parser.add_argument("--solver-spacing", choices=["logsnr", "uniform"], default="logsnr", help="dpm++ only: how its steps are chosen")
+    parser.add_argument("--sample-rng", choices=["torch", "counter"], default="torch",
+                        help="torch: every draw from the global torch generator, as the reference; counter: sample i's latent, label and "
+                             "step noise are a function of (--seed, i) alone (sample_rng.SampleRNG) - what sample_fid.py's parts, "
+                             "shards and resuming rest on")
     return parser
+
+
+def make_rng(args, device):
+    """The SampleRNG of ``--sample-rng counter`` (keyed by ``--seed``), or None."""
+    if getattr(args, "sample_rng", "torch") != "counter":
+        return None
+    if args.seed is None:
+        raise ValueError("--sample-rng counter needs a --seed: the seed is the generator's key")
+    from .sample_rng import SampleRNG
+    return SampleRNG(args.seed, device)
 
 
 def check_objective(sampler: str, train_args: dict | None):
@@ -348,33 +392,40 @@ def make_diffusion(args, train_args: dict | None = None):
 
 
 def run_sampler(model, diffusion, z, y, cfg_scale, use_graph: bool = True, progress: bool = False, sampler: str = "ancestral",
-                num_steps: int = 20, order: int = 2, spacing: str = "logsnr"):
+                num_steps: int = 20, order: int = 2, spacing: str = "logsnr", rng=None, index=None):
     """``diffusion.p_sample_loop(model.forward[_with_cfg], z.shape, z, clip_denoised=False, ...)`` - through the captured
     hipGraph (default) or the eager loop; with ``sampler="dpm++"``, ``diffusion.dpm_solver_sample_loop`` (num_steps, order,
     spacing) the same two ways; with ``sampler="flow"`` (or the CLI names "flow-euler" / "flow-heun", which fix the order), `diffusion`
-    is a RectifiedFlow and the loop is its ``sample_loop(num_steps=, order=1 | 2)``."""
+    is a RectifiedFlow and the loop is its ``sample_loop(num_steps=, order=1 | 2)``.  rng= / index= (together): the step noise is the
+    SampleRNG's for those sample indices; z stays the start."""
+    from .sample_rng import pair
+    pair(rng, index)
+    ctr = {} if rng is None else dict(rng=rng, index=index)
+    idx = {} if rng is None else dict(index=index)
     if sampler not in SAMPLERS + ("flow",):
         raise ValueError(f"sampler must be one of {SAMPLERS + ('flow',)}; got {sampler!r}")
     if sampler == "flow" or sampler in FLOW_SAMPLERS:
         order = FLOW_SAMPLERS.get(sampler, order)
         if use_graph:
-            return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, sampler="flow", num_steps=num_steps, order=order).sample(z)
+            return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, sampler="flow", num_steps=num_steps, order=order,
+                                  rng=rng).sample(z, **idx)
         from .flow import RectifiedFlow
         if not isinstance(diffusion, RectifiedFlow):
             raise ValueError(f'sampler="flow" runs a flow.RectifiedFlow and "ancestral" / "dpm++" a GaussianDiffusion; got sampler={sampler!r} '
                              f"with a {type(diffusion).__name__}")
         kw = dict(y=y) if cfg_scale is None else dict(y=y, cfg_scale=cfg_scale)
         fn = model.forward if cfg_scale is None else model.forward_with_cfg
-        return diffusion.sample_loop(fn, z.shape, z, model_kwargs=kw, progress=progress, device=z.device, num_steps=num_steps, order=order)
+        return diffusion.sample_loop(fn, z.shape, z, model_kwargs=kw, progress=progress, device=z.device, num_steps=num_steps, order=order,
+                                     **ctr)
     solver = dict(num_steps=num_steps, order=order, spacing=spacing) if sampler == "dpm++" else {}
     if use_graph:
-        return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, clip_denoised=False, sampler=sampler, **solver).sample(z)
+        return GraphedSampler(model, diffusion, z.shape, y, cfg_scale, clip_denoised=False, sampler=sampler, rng=rng, **solver).sample(z, **idx)
     kw = dict(y=y) if cfg_scale is None else dict(y=y, cfg_scale=cfg_scale)
     fn = model.forward if cfg_scale is None else model.forward_with_cfg
     if sampler == "dpm++":
         return diffusion.dpm_solver_sample_loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=progress, device=z.device,
-                                                **solver)
-    return diffusion.p_sample_loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=progress, device=z.device)
+                                                **solver, **ctr)
+    return diffusion.p_sample_loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=progress, device=z.device, **ctr)
 
 
 def save_image_grid(samples: torch.Tensor, path: str, nrow: int, value_range=(-1.0, 1.0), padding: int = 2):
