@@ -1084,6 +1084,16 @@ size_t mapdit_inc_workspace_bytes(const mapdit_inc_config_t* cfg, int N);
  * feat fp32 [N, 2048].  Every launch goes to `stream`; no allocation, no synchronisation, no host read-back. */
 int mapdit_inc_features(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
                         int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
+/* The spatial features of sFID (ADM's `mixed_6/conv:0[..., :7]`, taken to be the Mixed_6d.branch1x1 unit's output after BatchNorm and
+ * ReLU, in the port's channel order): the first MAPDIT_INC_SPATIAL_CHANNELS channels of that unit, widened from the 16-bit
+ * activation to fp32 [N, hs * ws * channels] in (h, w, c) order.  mapdit_inc_spatial_shape (host only) gives hs, ws and channels of
+ * a configuration: 17, 17, 7 at 299 (2023 numbers per image), 3, 3, 7 at 75.
+ * mapdit_inc_features_tap is mapdit_inc_features' walk with one copy kernel after Mixed_6d: `spatial` NULL skips the copy, and feat
+ * has mapdit_inc_features' bits either way.  Same workspace (the tap goes to the caller's buffer), same refusals. */
+#define MAPDIT_INC_SPATIAL_CHANNELS 7
+int mapdit_inc_spatial_shape(const mapdit_inc_config_t* cfg, int* hs, int* ws, int* channels);
+int mapdit_inc_features_tap(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                            int W, float* feat, float* spatial, void* workspace, size_t ws_bytes, void* stream);
 /* sum[d] += sum_n feat[n][d] and outer[i][j] += sum_n feat[n][i] * feat[n][j] in fp64 (feat fp32 [N, D]; sum [D], outer [D, D], zeroed
  * by the caller before the first batch).  Each output element adds its samples in index order to the value it read: no atomics, no
  * partial sums, so the sums do not depend on how the samples were cut into batches. */
@@ -1121,6 +1131,17 @@ int mapdit_ball_count(const float* Q, int Nq, const float* R, int Nr, int D, con
 size_t mapdit_poly_kernel_sum_workspace_bytes(int Na, int Nb, int D, int chunks);
 int mapdit_poly_kernel_sum(const float* A, int Na, const float* B, int Nb, int D, double gamma, double coef0, int degree, int skip_diag,
                            double* out, int chunks, void* workspace, size_t ws_bytes, void* stream);
+/* The two sums of the Inception Score over N samples and C classes (metrics.inception_score finishes them on the host):
+ *   ent[0] = sum_n sum_c p_nc log p_nc  and  marg[c] = sum_n p_nc,  p_n = softmax_c(l_n), l_nc = g(x_n, w_c) + bias[c].
+ * X fp32 [N, D] samples, W fp32 [C, D] class rows, bias fp32 [C] or NULL; ent [1] and marg [C] fp64 on the device, overwritten.
+ * fp32 only inside the Gram chain: g is converted to fp64, the bias is added and every exp / log runs in fp64.  Two passes over the
+ * same tile kernel.  Samples as queries: per (sample, class tile) an online (m, s, u) = (max l, sum exp(l - m), sum exp(l - m) l),
+ * merged in tile order into lse_n = m + log s and sum_c p log p = u / s - lse_n.  Classes as queries: sum_n exp(l_nc - lse_n), one
+ * fp64 partial per (class, sample tile) and wave, added in index order; g(i, j) == g(j, i) bit for bit, so both passes see the
+ * same logits.  Every partial belongs to a tile, none to a slice: no output depends on chunks, bit for bit. */
+size_t mapdit_softmax_score_workspace_bytes(int N, int C, int D, int chunks);
+int mapdit_softmax_score(const float* X, int N, const float* W, int C, int D, const float* bias, double* ent, double* marg, int chunks,
+                         void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
@@ -1202,6 +1223,8 @@ int mapdit_inc_pool_f16(const void* in, int in_kind, void* out, int out_kind, in
 int mapdit_inc_global_avg_f16(const void* in, int in_kind, float* out, int N, int HW, int C, void* stream);
 int mapdit_inc_features_f16(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
                             int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
+int mapdit_inc_features_tap_f16(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N,
+                                int H, int W, float* feat, float* spatial, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

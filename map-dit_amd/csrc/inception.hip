@@ -2,6 +2,8 @@
 // convolutions) and the fp64 feature statistics (mapdit.h, "Inception / FID").  Built once per 16-bit operand format (csrc/Makefile).
 // Activations are 16-bit NHWC between the layers (a convolution rounds its input to the operand format anyway; max pooling commutes
 // with that rounding, the average pool rounds once more); the image at 299 x 299 and the last block's output are fp32.
+// mapdit_inc_features_tap is the same walk with one copy kernel after Mixed_6d: sFID's spatial features, the first 7 channels of
+// that block's branch1x1 unit, widened to fp32 into the caller's buffer (no workspace of its own).
 //
 // Convolution: conv.hip's kernels (common.h, md_conv_t) with kh x kw taps, stride, pad_h / pad_w, ReLU and a store into a channel
 // slice.  Cin is a multiple of 16 and of nothing larger (48, 80, 288 ...) and Cout a multiple of 16, not of 64: the 16-channel K
@@ -55,6 +57,13 @@ __global__ __launch_bounds__(256) void inc_global_avg_kernel(const void* __restr
     float a = 0.f;
     for (int i = 0; i < HW; ++i) a += inc_load(in, in_f32, ((size_t)n * HW + i) * C + c);
     out[idx] = a / (float)HW;
+}
+
+// The spatial tap: channels [0, ct) of a 16-bit [pixels, C] activation -> fp32 [pixels, ct], one thread per output element
+__global__ __launch_bounds__(256) void inc_tap_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, long total, int C, int ct) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    out[idx] = up16(in[(size_t)(idx / ct) * C + (int)(idx % ct)]);
 }
 
 #if MAPDIT_DT == 0
@@ -238,6 +247,8 @@ struct IncWalk {
     const void* const* wt;
     uint16_t *X, *Y, *T1, *T2;
     float *IMG, *FIN;
+    float* TAP;                  // the spatial tap's destination [N, tapH * tapW * MAPDIT_INC_SPATIAL_CHANNELS], or null: no tap
+    int tapH, tapW;
     int li;                      // the next convolution's number in execution order
     size_t maxE, finE;
     IncLayer layers[MAPDIT_INC_NUM_CONV];
@@ -278,6 +289,16 @@ struct IncWalk {
         uint16_t* t = X;
         X = Y;
         Y = t;
+    }
+    // after Mixed_6d: X is the block's concatenated [N, H, W, 768] output, channels [0, 192) of it the branch1x1 unit
+    int tap(int H, int W) {
+        tapH = H;
+        tapW = W;
+        if (dry || !TAP) return MAPDIT_OK;
+        const long total = (long)N * H * W * MAPDIT_INC_SPATIAL_CHANNELS;
+        inc_tap_kernel<<<cdiv(total, 256), 256, 0, (hipStream_t)stream>>>((const bf16_t*)X, TAP, total, 768, MAPDIT_INC_SPATIAL_CHANNELS);
+        MD_LAUNCH_CHECK();
+        return MAPDIT_OK;
     }
 
     // Mixed_5b / 5c / 5d
@@ -383,6 +404,7 @@ struct IncWalk {
         MD_TRY(block_c(H, W, 128));
         MD_TRY(block_c(H, W, 160));
         MD_TRY(block_c(H, W, 160));
+        MD_TRY(tap(H, W));                                                                                            // Mixed_6d
         MD_TRY(block_c(H, W, 192));
         MD_TRY(block_d(&H, &W));
         MD_TRY(block_e(H, W, 1280, MAPDIT_INC_POOL_AVG, false));
@@ -443,25 +465,39 @@ extern "C" int mapdit_inc_layer_shape(int index, int* cin, int* cout, int* kh, i
     *stride = l.st;
     return MAPDIT_OK;
 }
+
+extern "C" int mapdit_inc_spatial_shape(const mapdit_inc_config_t* cfg, int* hs, int* ws, int* channels) {
+    MD_CHECK(hs && ws && channels, "inc_spatial_shape: null argument");
+    IncWalk wk;
+    IncPlan pl;
+    MD_TRY(inc_plan(cfg, 1, &wk, &pl));
+    *hs = wk.tapH;
+    *ws = wk.tapW;
+    *channels = MAPDIT_INC_SPATIAL_CHANNELS;
+    return MAPDIT_OK;
+}
 #endif
 
-extern "C" int MD_SYM(inc_features)(const mapdit_inc_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
-                                    float* feat, void* workspace, size_t ws_bytes, void* stream) {
+// the one run: `spatial` null is mapdit_inc_features (no tap kernel, the same launches as ever)
+static int inc_features_run(const char* who, const mapdit_inc_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H,
+                            int W, float* feat, float* spatial, void* workspace, size_t ws_bytes, void* stream) {
     IncWalk wk;
     IncPlan pl;
     MD_TRY(inc_plan(cfg, N, &wk, &pl));
-    MD_CHECK(wt && images && feat && workspace, "inc_features: null argument");
-    MD_CHECK(img_kind == MAPDIT_INC_IMG_U8_NHWC || img_kind == MAPDIT_INC_IMG_F32_NCHW, "inc_features: bad img_kind %d", img_kind);
-    MD_CHECK(H >= 8 && W >= 8, "inc_features: images of %d x %d (8 x 8 at the least)", H, W);
-    MD_CHECK(ws_bytes >= pl.total, "inc_features: workspace of %zu bytes, %zu needed (mapdit_inc_workspace_bytes)", ws_bytes, pl.total);
-    MD_CHECK(!((uintptr_t)workspace & 255), "inc_features: the workspace must be 256-byte aligned");
-    for (int i = 0; i < 2 * MAPDIT_INC_NUM_CONV; ++i) MD_CHECK(wt[i], "inc_features: weight slot %d is null", i);
+    MD_CHECK(wt && images && feat && workspace, "%s: null argument", who);
+    MD_CHECK(img_kind == MAPDIT_INC_IMG_U8_NHWC || img_kind == MAPDIT_INC_IMG_F32_NCHW, "%s: bad img_kind %d", who, img_kind);
+    MD_CHECK(H >= 8 && W >= 8, "%s: images of %d x %d (8 x 8 at the least)", who, H, W);
+    MD_CHECK(ws_bytes >= pl.total, "%s: workspace of %zu bytes, %zu needed (mapdit_inc_workspace_bytes)", who, ws_bytes, pl.total);
+    MD_CHECK(!((uintptr_t)workspace & 255), "%s: the workspace must be 256-byte aligned", who);
+    MD_CHECK(!((uintptr_t)spatial & 3), "%s: spatial is not 4-byte aligned", who);
+    for (int i = 0; i < 2 * MAPDIT_INC_NUM_CONV; ++i) MD_CHECK(wt[i], "%s: weight slot %d is null", who, i);
     char* ws = (char*)workspace;
     wk = IncWalk{};
     wk.dry = false;
     wk.N = N;
     wk.stream = stream;
     wk.wt = wt;
+    wk.TAP = spatial;
     wk.IMG = (float*)(ws + pl.off_img);
     wk.FIN = (float*)(ws + pl.off_fin);
     wk.X = (uint16_t*)(ws + pl.off_x);
@@ -474,4 +510,14 @@ extern "C" int MD_SYM(inc_features)(const mapdit_inc_config_t* cfg, const void* 
     int Hf = 0, Wf = 0;
     MD_TRY(wk.run(S, &Hf, &Wf));
     return MD_SYM(inc_global_avg)(wk.FIN, MAPDIT_INC_IN_F32, feat, N, Hf * Wf, 2048, stream);
+}
+
+extern "C" int MD_SYM(inc_features)(const mapdit_inc_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
+                                    float* feat, void* workspace, size_t ws_bytes, void* stream) {
+    return inc_features_run("inc_features", cfg, wt, images, img_kind, N, H, W, feat, nullptr, workspace, ws_bytes, stream);
+}
+
+extern "C" int MD_SYM(inc_features_tap)(const mapdit_inc_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H,
+                                        int W, float* feat, float* spatial, void* workspace, size_t ws_bytes, void* stream) {
+    return inc_features_run("inc_features_tap", cfg, wt, images, img_kind, N, H, W, feat, spatial, workspace, ws_bytes, stream);
 }

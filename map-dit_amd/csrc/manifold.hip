@@ -1,8 +1,11 @@
 // Sample-quality metrics on feature sets (metrics.py: precision / recall, density / coverage, KID): the Gram matrix G = R Q^T of two
 // row-major fp32 sets [rows, D], computed tile by tile on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: exact fp32 products, one rounding
 // per step of the chain) and never stored.  Every 128 x 128 tile is reduced in the epilogue to what the metric needs - the 8 smallest
-// squared distances per query, a count of references whose ball holds the query, or an fp64 sum of polynomial-kernel values.  One
-// kernel, three epilogues (the template argument).  fp32 only: built once, not per 16-bit operand format.
+// squared distances per query, a count of references whose ball holds the query, an fp64 sum of polynomial-kernel values, or the
+// softmax statistics of the Inception Score (mapdit_softmax_score: the Gram values are logits; per sample an online (max, sum exp,
+// sum exp * logit) over the classes, then with the roles swapped per class the sum of exp(logit - lse) over the samples - fp32 ends
+// at the Gram value, the bias, exp and log are fp64).  One kernel, five epilogues (the template argument).  fp32 only: built once,
+// not per 16-bit operand format.
 //
 // Tile: 128 references (the MFMA's A side, the rows of C) x 128 queries (B side, the columns of C) x 32 of K, 4 waves, each 2 x 2 tiles
 // of 32 x 32.  In the 32 x 32 C layout a lane owns ONE column and 16 rows, so with the queries on the columns a lane reduces over
@@ -13,6 +16,8 @@
 //
 // Grid: query tiles x `chunks` slices of the reference tiles.  Partial results go to the workspace and a small second kernel merges
 // them: a k-smallest set, an integer count and a sum over per-tile partials in a fixed order do not depend on the slicing.  No atomics.
+// The softmax epilogues keep that promise the way MF_POLY does: one (m, s, u) per (sample, class tile) and one fp64 sum per (class,
+// sample tile, wave), merged in tile order - every output of mapdit_softmax_score is independent of `chunks` bit for bit.
 #include <type_traits>
 
 #include "common.h"
@@ -22,7 +27,7 @@ namespace {
 constexpr int MF_TILE = 128, MF_BK = 32, MF_LD = 36, MF_THREADS = 256, MF_KMAX = 8;
 constexpr int MF_MAX_ROWS = 1 << 30;        // row indices, tile counts and rows + 127 stay in int; row offsets are 64-bit
 constexpr int MF_MAX_D = 65536, MF_MAX_CHUNKS = 65535;
-enum { MF_KNN = 0, MF_COUNT = 1, MF_POLY = 2 };
+enum { MF_KNN = 0, MF_COUNT = 1, MF_POLY = 2, MF_LSE = 3, MF_MARGINAL = 4 };
 
 struct mf_args_t {
     const float* Q;           // [Nq, D] queries: the columns of a tile
@@ -38,7 +43,21 @@ struct mf_args_t {
     float* knn_part;          // [chunks][Nq][8] ascending
     uint32_t* cnt_part;       // [chunks][Nq]
     double* sum_part;         // [qtiles][rtiles][4 waves]
+    const float* bias;        // LSE: [Nr] (the classes are the references), MARGINAL: [Nq]; or null
+    const double* lse;        // MARGINAL: [Nr], each sample's log-sum-exp
+    double* lse_part;         // LSE: [rtiles][Nq][3] = (m, s, u) of a sample over one class tile
+    double* marg_part;        // MARGINAL: [rtiles][Nq][2 waves]
 };
+
+// (m, s, u) = (max l, sum exp(l - m), sum exp(l - m) l) of two disjoint sets of logits; (-inf, 0, 0) is the empty set
+__device__ __forceinline__ void mf_lse_merge(double& m, double& s, double& u, double m2, double s2, double u2) {
+    const double mn = fmax(m, m2);
+    if (mn == -__builtin_inf()) return;
+    const double a = exp(m - mn), b = exp(m2 - mn);
+    s = s * a + s2 * b;
+    u = u * a + u2 * b;
+    m = mn;
+}
 
 // the 8 smallest of a stream, ascending: one compare-exchange per slot
 __device__ __forceinline__ void mf_insert(float (&lst)[MF_KMAX], float d) {
@@ -55,6 +74,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void gram_tile_kernel(mf_args_t p) {
     __shared__ __attribute__((aligned(16))) float sR[MF_TILE * MF_LD];
     __shared__ __attribute__((aligned(16))) float sQ[MF_TILE * MF_LD];
     __shared__ float sNr[MF_TILE], sRad[MF_TILE];
+    __shared__ double sLse[MF_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1, l31 = lane & 31, half = lane >> 5;
     const int qtile = blockIdx.x, chunk = blockIdx.y;
@@ -69,14 +89,15 @@ __global__ __launch_bounds__(MF_THREADS, 2) void gram_tile_kernel(mf_args_t p) {
     for (int i = 0; i < 4; ++i) qsrc[i] = p.Q + (size_t)min(q0 + ld_row + 32 * i, p.Nq - 1) * p.D + ld_col;
 
     int qidx[2];
-    float nqv[2], radq[2];
+    float nqv[2], radq[2], biasq[2];
     float lst[2][MF_KMAX];
     uint32_t cnt[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         qidx[n] = q0 + wn * 64 + n * 32 + l31;
         const bool in = qidx[n] < p.Nq;
-        nqv[n] = (EPI != MF_POLY && in) ? p.nq[qidx[n]] : 0.f;
+        nqv[n] = ((EPI == MF_KNN || EPI == MF_COUNT) && in) ? p.nq[qidx[n]] : 0.f;
+        biasq[n] = (EPI == MF_MARGINAL && p.bias && in) ? p.bias[qidx[n]] : 0.f;
         radq[n] = (EPI == MF_COUNT && p.mode == MAPDIT_BALL_QUERY_RADIUS && in) ? p.rad[qidx[n]] : 0.f;
         cnt[n] = 0;
 #pragma unroll
@@ -114,7 +135,12 @@ __global__ __launch_bounds__(MF_THREADS, 2) void gram_tile_kernel(mf_args_t p) {
                 *reinterpret_cast<float4*>(&sR[(ld_row + 32 * i) * MF_LD + ld_col]) = gr[i];
                 *reinterpret_cast<float4*>(&sQ[(ld_row + 32 * i) * MF_LD + ld_col]) = gq[i];
             }
-            if (EPI != MF_POLY && kt == 0 && tid < MF_TILE) {
+            if ((EPI == MF_LSE || EPI == MF_MARGINAL) && kt == 0 && tid < MF_TILE) {
+                const bool in = r0 + tid < p.Nr;
+                if (EPI == MF_LSE) sNr[tid] = (in && p.bias) ? p.bias[r0 + tid] : 0.f;
+                else sLse[tid] = in ? p.lse[r0 + tid] : 0.0;
+            }
+            if ((EPI == MF_KNN || EPI == MF_COUNT) && kt == 0 && tid < MF_TILE) {
                 const bool in = r0 + tid < p.Nr;
                 sNr[tid] = in ? p.nr[r0 + tid] : 0.f;
                 if (EPI == MF_COUNT) sRad[tid] = (in && p.mode == MAPDIT_BALL_REF_RADIUS) ? p.rad[r0 + tid] : 0.f;
@@ -171,7 +197,75 @@ __global__ __launch_bounds__(MF_THREADS, 2) void gram_tile_kernel(mf_args_t p) {
                         }
                     }
         };
-        if (EPI != MF_POLY || p.degree == 1) reduce_tile(std::integral_constant<int, 1>{});
+        if constexpr (EPI == MF_LSE) {
+            // fp32 ends at g: the logit l = g + bias and everything after it is fp64.  A lane's 32 classes of the tile per query in
+            // two blocks of 16 (one accumulator each: 16 logits are live at a time, not 64), merged in block order; then the four
+            // lanes that hold the same query (slot = 2 wm + half) meet in LDS and merge in slot order: one partial per (sample, class
+            // tile), whatever the slicing
+            double pm[2], ps[2], pu[2];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                pm[n] = -__builtin_inf();
+                ps[n] = pu[n] = 0.0;
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    double l[16], mx = -__builtin_inf();
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int lr = wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                        l[r] = (r0 + lr < p.Nr) ? (double)acc[m][n][r] + (double)sNr[lr] : -__builtin_inf();
+                        mx = fmax(mx, l[r]);
+                    }
+                    double s = 0.0, u = 0.0;
+                    if (mx != -__builtin_inf()) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const bool in = l[r] != -__builtin_inf();          // (rows past the end: exp(-inf) = 0, but 0 * -inf is no 0)
+                            const double e = in ? exp(l[r] - mx) : 0.0;
+                            s += e;
+                            u += in ? e * l[r] : 0.0;
+                        }
+                    }
+                    mf_lse_merge(pm[n], ps[n], pu[n], mx, s, u);
+                    __builtin_amdgcn_sched_barrier(0);         // block by block: the next block's logits are not formed ahead of time
+                }
+            }
+            __syncthreads();                                   // every wave is done with sR: it becomes [128 queries][4 slots][3] doubles, 12 KB
+            double* mb = reinterpret_cast<double*>(sR);
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                double* d = mb + ((wn * 64 + n * 32 + l31) * 4 + 2 * wm + half) * 3;
+                d[0] = pm[n];
+                d[1] = ps[n];
+                d[2] = pu[n];
+            }
+            __syncthreads();
+            if (tid < MF_TILE && q0 + tid < p.Nq) {
+                double m = mb[tid * 12], s = mb[tid * 12 + 1], u = mb[tid * 12 + 2];
+                for (int t = 1; t < 4; ++t) mf_lse_merge(m, s, u, mb[tid * 12 + 3 * t], mb[tid * 12 + 3 * t + 1], mb[tid * 12 + 3 * t + 2]);
+                double* dst = p.lse_part + ((size_t)rt * p.Nq + q0 + tid) * 3;
+                dst[0] = m;
+                dst[1] = s;
+                dst[2] = u;
+            }                                                  // (the next tile's first barrier comes before sR is written again)
+        } else if constexpr (EPI == MF_MARGINAL) {
+            // the same logit bits with the roles swapped (g is symmetric): exp(l - lse) of a lane's 32 samples per class, the two lane
+            // halves by one exchange (a + b == b + a), one partial per (class, sample tile) and wave
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                double s = 0.0;
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int lr = wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                        const double l = (double)acc[m][n][r] + (double)biasq[n];
+                        s += (r0 + lr < p.Nr) ? exp(l - sLse[lr]) : 0.0;
+                    }
+                s += __shfl_xor(s, 32, 64);
+                if (half == 0 && qidx[n] < p.Nq) p.marg_part[((size_t)rt * p.Nq + qidx[n]) * 2 + wm] = s;
+            }
+        } else if (EPI != MF_POLY || p.degree == 1) reduce_tile(std::integral_constant<int, 1>{});
         else if (p.degree == 2) reduce_tile(std::integral_constant<int, 2>{});
         else if (p.degree == 3) reduce_tile(std::integral_constant<int, 3>{});
         else reduce_tile(std::integral_constant<int, 4>{});
@@ -183,7 +277,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void gram_tile_kernel(mf_args_t p) {
         }
     }
 
-    if (EPI == MF_POLY) return;
+    if (EPI == MF_POLY || EPI == MF_LSE || EPI == MF_MARGINAL) return;
     // the two lane halves and the two waves (wm) that hold the same query meet here: slot = 2 wm + half
     __syncthreads();
     const int ql = wn * 64 + l31, slot = 2 * wm + half;
@@ -252,6 +346,33 @@ __global__ __launch_bounds__(256) void sum_merge_kernel(const double* __restrict
         __syncthreads();
     }
     if (threadIdx.x == 0) *out = s[0];
+}
+
+// one thread per sample: the class tiles' (m, s, u) in tile order -> lse = m + log s and sum_c p log p = u / s - lse
+__global__ __launch_bounds__(256) void lse_merge_kernel(const double* __restrict__ part, int N, int rtiles, double* __restrict__ lse,
+                                                        double* __restrict__ plogp) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= N) return;
+    double m = -__builtin_inf(), s = 0.0, u = 0.0;
+    for (int rt = 0; rt < rtiles; ++rt) {
+        const double* src = part + ((size_t)rt * N + q) * 3;
+        mf_lse_merge(m, s, u, src[0], src[1], src[2]);
+    }
+    const double l = m + log(s);
+    lse[q] = l;
+    plogp[q] = u / s - l;
+}
+
+// one thread per class: the (sample tile, wave) partials in index order
+__global__ __launch_bounds__(256) void marg_merge_kernel(const double* __restrict__ part, int C, int rtiles, double* __restrict__ marg) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double v = 0.0;
+    for (int rt = 0; rt < rtiles; ++rt) {
+        v += part[((size_t)rt * C + c) * 2];
+        v += part[((size_t)rt * C + c) * 2 + 1];
+    }
+    marg[c] = v;
 }
 
 // one wave per row: lane l adds the float4s l, l + 64, ... of the row in fp64, then the butterfly; one rounding to fp32 at the end
@@ -425,6 +546,76 @@ extern "C" int mapdit_poly_kernel_sum(const float* A, int Na, const float* B, in
     a.sum_part = (double*)workspace;
     MD_TRY(mf_launch<MF_POLY>(a, stream));
     hipLaunchKernelGGL(sum_merge_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a.sum_part, (size_t)mf_tiles(Na) * a.rtiles * 4, out);
+    MD_LAUNCH_CHECK();
+    return MAPDIT_OK;
+}
+
+namespace {
+struct mf_score_plan_t {
+    size_t off_lse_part, off_lse, off_plogp, off_marg_part, total;
+};
+
+// does not depend on chunks: every partial belongs to a tile
+mf_score_plan_t mf_score_plan(int N, int C) {
+    mf_score_plan_t pl;
+    size_t o = 0;
+    pl.off_lse_part = o; o += md_up256((size_t)mf_tiles(C) * N * 3 * sizeof(double));
+    pl.off_lse = o; o += md_up256((size_t)N * sizeof(double));
+    pl.off_plogp = o; o += md_up256((size_t)N * sizeof(double));
+    pl.off_marg_part = o; o += md_up256((size_t)mf_tiles(N) * C * 2 * sizeof(double));
+    pl.total = o;
+    return pl;
+}
+}  // namespace
+
+extern "C" size_t mapdit_softmax_score_workspace_bytes(int N, int C, int D, int chunks) {
+    if (mf_check_shape("softmax_score", N, C, D, chunks) != MAPDIT_OK) return 0;
+    return mf_score_plan(N, C).total;
+}
+
+extern "C" int mapdit_softmax_score(const float* X, int N, const float* W, int C, int D, const float* bias, double* ent, double* marg, int chunks,
+                                    void* workspace, size_t ws_bytes, void* stream) {
+    MD_TRY(mf_check_shape("softmax_score", N, C, D, chunks));
+    MD_TRY(mf_check_ptr("softmax_score", "X", X));
+    MD_TRY(mf_check_ptr("softmax_score", "W", W));
+    MD_CHECK(!bias || mf_aligned(bias, 4), "softmax_score: bias is unaligned");
+    MD_CHECK(mf_aligned(ent, 8) && mf_aligned(marg, 8), "softmax_score: ent or marg is null or unaligned");
+    const mf_score_plan_t pl = mf_score_plan(N, C);
+    MD_CHECK(mf_aligned(workspace, 256) && ws_bytes >= pl.total, "softmax_score: workspace of %zu bytes at %p (%zu needed, 256-byte aligned)", ws_bytes,
+             workspace, pl.total);
+    char* ws = (char*)workspace;
+    double* lse = (double*)(ws + pl.off_lse);
+    double* plogp = (double*)(ws + pl.off_plogp);
+    // samples as queries, classes as references: lse and sum_c p log p per sample
+    mf_args_t a = {};
+    a.Q = X;
+    a.R = W;
+    a.Nq = N;
+    a.Nr = C;
+    a.D = D;
+    a.bias = bias;
+    a.rtiles = mf_tiles(C);
+    a.chunks = mf_chunks(mf_tiles(N), a.rtiles, chunks);
+    a.lse_part = (double*)(ws + pl.off_lse_part);
+    MD_TRY(mf_launch<MF_LSE>(a, stream));
+    hipLaunchKernelGGL(lse_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a.lse_part, N, a.rtiles, lse, plogp);
+    MD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sum_merge_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, plogp, (size_t)N, ent);
+    MD_LAUNCH_CHECK();
+    // classes as queries, samples as references: the class marginal
+    mf_args_t b = {};
+    b.Q = W;
+    b.R = X;
+    b.Nq = C;
+    b.Nr = N;
+    b.D = D;
+    b.bias = bias;
+    b.lse = lse;
+    b.rtiles = mf_tiles(N);
+    b.chunks = mf_chunks(mf_tiles(C), b.rtiles, chunks);
+    b.marg_part = (double*)(ws + pl.off_marg_part);
+    MD_TRY(mf_launch<MF_MARGINAL>(b, stream));
+    hipLaunchKernelGGL(marg_merge_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, b.marg_part, C, b.rtiles, marg);
     MD_LAUNCH_CHECK();
     return MAPDIT_OK;
 }

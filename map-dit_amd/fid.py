@@ -4,15 +4,23 @@
 
     python -m mapdit_amd.fid stats --images A.npz --inception-weights FILE --output ref.npz
     python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz
-    python -m mapdit_amd.fid compare a.npz b.npz [--inception-weights FILE] [--metrics fid,pr,kid]
+    python -m mapdit_amd.fid compare a.npz b.npz [--inception-weights FILE] [--metrics fid,fid_s,isc,pr,kid]
 
 ``features`` writes the ``pool_3`` features [N, 2048] fp32 beside ``mu`` and ``sigma``, so the file still loads as a statistics file.
 ``--metrics``: ``pr`` (precision, recall, density, coverage) and ``kid`` (metrics.py) need the features of both sides - an image
 array with the weights, or a file that holds ``pool_3``; ``a`` is the reference (real) side, ``b`` the samples.
+``fid_s`` (sFID): the same Fréchet distance on the spatial features, the first 7 channels of the ``Mixed_6d.branch1x1`` unit
+(17 x 17 x 7 = 2023 numbers per image; ``mapdit_inc_features_tap``).  ``stats --spatial`` / ``features --spatial`` add their
+statistics as ``mu_s``, ``sigma_s`` (the keys of ADM's reference batches); ``compare`` needs them, or images, on both sides.
+``isc`` (Inception Score, ``metrics.inception_score``): of side ``b``, from its ``pool_3`` and the classifier head (``fc.weight``) of
+``--inception-weights``; printed as ``isc: mean ± std`` over splits of 5000.
 
 Parity with the hub weights is unpinned: the network is restated from its public description and checked against an independent
 fp64 restatement on random weights (tests/inception_reference.py), not against ``pytorch-fid``.  The first FID quoted from this
-code needs one cross-check against ``pytorch-fid`` on a machine that has the weight file.
+code needs one cross-check against ``pytorch-fid`` on a machine that has the weight file.  The same holds for ``fid_s`` and ``isc``
+against ADM's ``evaluator.py``: ``mixed_6/conv:0`` is TAKEN to be the ``Mixed_6d.branch1x1`` unit's output after BatchNorm and ReLU,
+and its channel order to be the port's (a permutation of the 2023 coordinates would not change the distance, another choice of 7
+channels would); neither is checked here.
 """
 from __future__ import annotations
 
@@ -125,6 +133,20 @@ def fold_state_dict(sd) -> dict:
     return out
 
 
+NUM_LOGITS = 1008
+
+
+def classifier_head(sd):
+    """(W fp32 [1008, 2048], b fp32 [1008]) of the raw state dict: the ``fc`` layer on ``pool_3`` that ``fold_state_dict`` leaves out,
+    for ``metrics.inception_score``.  A missing key is a KeyError naming it, a wrong shape a ValueError."""
+    for k, shape in (("fc.weight", (NUM_LOGITS, FEATURE_DIM)), ("fc.bias", (NUM_LOGITS,))):
+        if k not in sd:
+            raise KeyError(f"Inception state dict: missing key {k!r} (the classifier head; the Inception Score needs it)")
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"Inception state dict: {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
+    return sd["fc.weight"].detach().to(torch.float32).contiguous(), sd["fc.bias"].detach().to(torch.float32).contiguous()
+
+
 def pack_conv_weight(w, dtype):
     """[Cout, Cin, kh, kw] -> 16-bit [Cout][kh][kw][Cin], the B operand of mapdit_inc_conv."""
     return w.permute(0, 2, 3, 1).contiguous().to(torch.float32).to(dtype)
@@ -183,8 +205,15 @@ class InceptionFeatures:
             raise ValueError(f"Inception features refused: {lib.last_error().decode()}")
         return need
 
+    @property
+    def spatial_dim(self) -> int:
+        """The length of a spatial feature row: 17 * 17 * 7 = 2023 at 299 (``mapdit_inc_spatial_shape``, host only)."""
+        return spatial_dim(self._cfg.image_size)
+
     @torch.no_grad()
-    def features(self, x):
+    def features(self, x, spatial=False):
+        """``spatial=True`` -> (feat, fp32 [N, spatial_dim]): sFID's features, the first 7 channels of Mixed_6d.branch1x1 in (h, w, c)
+        order, from the same pass; ``feat`` has the same bits either way."""
         if not isinstance(x, torch.Tensor) or not x.is_cuda or self.device.type != "cuda":
             raise NotImplementedError("InceptionFeatures.features runs on the GPU only (HIP kernels, no CPU path): pass a CUDA tensor to a network on the device")
         u8 = x.dtype == torch.uint8
@@ -195,8 +224,10 @@ class InceptionFeatures:
         if H < 8 or W < 8:
             raise ValueError(f"Inception features: images of {H} x {W} (8 x 8 at the least)")
         feat = torch.empty(N, FEATURE_DIM, dtype=torch.float32, device=self.device)
+        sdim = self.spatial_dim if spatial else 0
+        spat = torch.empty(N, sdim, dtype=torch.float32, device=self.device) if spatial else None
         if N == 0:
-            return feat
+            return (feat, spat) if spatial else feat
         chunk = min(N, self.max_batch)
         need = self.workspace_bytes(chunk)
         lib = L.lib()
@@ -205,15 +236,15 @@ class InceptionFeatures:
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        fn = lib.inc_features_f16 if self.precision == "f16" else lib.inc_features
+        fn = lib.inc_features_tap_f16 if self.precision == "f16" else lib.inc_features_tap       # (a null tap is mapdit_inc_features)
         kind = L.INC_IMG_U8_NHWC if u8 else L.INC_IMG_F32_NCHW
         with torch.cuda.device(self.device):
             stream = L.cur_stream()
             for i in range(0, N, chunk):
                 n = min(chunk, N - i)
-                fn(C.byref(self._cfg), self._table, x[i:i + n].data_ptr(), kind, n, H, W, feat[i:i + n].data_ptr(), self._ws.data_ptr(),
-                   self._ws.numel(), stream)
-        return feat
+                fn(C.byref(self._cfg), self._table, x[i:i + n].data_ptr(), kind, n, H, W, feat[i:i + n].data_ptr(),
+                   L.ptr(spat[i:i + n] if spatial else None), self._ws.data_ptr(), self._ws.numel(), stream)
+        return (feat, spat) if spatial else feat
 
 
 class FeatureStats:
@@ -253,22 +284,51 @@ class FeatureStats:
         save_stats(path, mu, sigma)
 
 
-def save_stats(path, mu, sigma):
+SPATIAL_KEYS = ("mu_s", "sigma_s")                             # the keys of ADM's reference batches
+
+
+def _spatial_arrays(mu_s, sigma_s) -> dict:
+    if (mu_s is None) != (sigma_s is None):
+        raise ValueError("mu_s and sigma_s go together")
+    return {} if mu_s is None else {"mu_s": np.asarray(mu_s, np.float64), "sigma_s": np.asarray(sigma_s, np.float64)}
+
+
+def save_stats(path, mu, sigma, mu_s=None, sigma_s=None):
+    """``mu``, ``sigma`` and, when given, the spatial statistics ``mu_s``, ``sigma_s`` (sFID) as fp64."""
     with open(path, "wb") as f:                                # (an open file: np.savez appends no second ".npz" to the name)
-        np.savez(f, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64))
+        np.savez(f, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64), **_spatial_arrays(mu_s, sigma_s))
 
 
-def load_stats(path):
+def load_stats(path, spatial=False):
     """``mu`` [D] and ``sigma`` [D, D] of any ``.npz`` that holds them (``pytorch-fid`` statistics, ADM's ``VIRTUAL_*`` reference
-    batches); other keys are ignored."""
+    batches); other keys are ignored.  ``spatial=True`` -> (mu, sigma, mu_s, sigma_s): the spatial statistics too, under the keys
+    ADM's reference batches carry."""
+    keys = ("mu", "sigma") + (SPATIAL_KEYS if spatial else ())
     with np.load(path) as z:
-        for k in ("mu", "sigma"):
-            if k not in z.files:
-                raise KeyError(f"{path}: no {k!r} in the file (it holds {sorted(z.files)}); statistics need 'mu' and 'sigma'")
-        mu, sigma = np.asarray(z["mu"], np.float64), np.asarray(z["sigma"], np.float64)
-    if mu.ndim != 1 or sigma.shape != (mu.shape[0], mu.shape[0]):
-        raise ValueError(f"{path}: mu of shape {mu.shape} and sigma of shape {sigma.shape} are no [D] and [D, D]")
-    return mu, sigma
+        for k in keys:
+            if k in z.files:
+                continue
+            if k in SPATIAL_KEYS:
+                raise KeyError(f"{path}: no {k!r} in the file (it holds {sorted(z.files)}); the spatial statistics are written by "
+                               "`python -m mapdit_amd.fid stats --spatial --images A.npz --inception-weights FILE --output ref.npz`")
+            raise KeyError(f"{path}: no {k!r} in the file (it holds {sorted(z.files)}); statistics need 'mu' and 'sigma'")
+        out = [np.asarray(z[k], np.float64) for k in keys]
+    for km, ks, mu, sigma in zip(keys[0::2], keys[1::2], out[0::2], out[1::2]):
+        if mu.ndim != 1 or sigma.shape != (mu.shape[0], mu.shape[0]):
+            raise ValueError(f"{path}: {km} of shape {mu.shape} and {ks} of shape {sigma.shape} are no [D] and [D, D]")
+    return tuple(out)
+
+
+def has_spatial(path) -> bool:
+    """Whether an ``.npz`` carries ``mu_s`` and ``sigma_s`` (the member names alone are read)."""
+    import zipfile
+    if not str(path).endswith(".npz"):
+        return False
+    try:
+        with zipfile.ZipFile(path) as z:
+            return all(k + ".npy" in z.namelist() for k in SPATIAL_KEYS)
+    except zipfile.BadZipFile:                                 # (no archive: it carries nothing; the caller's refusal names the command)
+        return False
 
 
 FeatureStats.load = staticmethod(load_stats)
@@ -276,10 +336,12 @@ FeatureStats.load = staticmethod(load_stats)
 FEATURES_KEY = "pool_3"
 
 
-def save_features(path, feat, mu, sigma):
-    """``pool_3`` fp32 [N, D] beside ``mu`` and ``sigma``: a statistics file that also carries what precision / recall and KID need."""
+def save_features(path, feat, mu, sigma, mu_s=None, sigma_s=None):
+    """``pool_3`` fp32 [N, D] beside ``mu`` and ``sigma`` (and ``mu_s``, ``sigma_s`` when given): a statistics file that also carries
+    what precision / recall, KID and the Inception Score need."""
     with open(path, "wb") as f:
-        np.savez(f, **{FEATURES_KEY: np.asarray(feat, np.float32)}, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64))
+        np.savez(f, **{FEATURES_KEY: np.asarray(feat, np.float32)}, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64),
+                 **_spatial_arrays(mu_s, sigma_s))
 
 
 def features_rows(path):
@@ -315,9 +377,27 @@ def load_features(path):
 
 
 # ---- metrics beside the FID ---------------------------------------------------------------------------------------------------------
-def extra_metrics(real, fake, names, args) -> dict:
-    """The values of ``pr`` and ``kid`` (those in ``names``) of two fp32 CUDA feature tensors, in printing order."""
+FEATURE_METRICS = ("isc", "pr", "kid")                        # the names that need pool_3 itself, not its statistics
+
+
+def load_head(path):
+    """``classifier_head`` of a weight file: what ``isc`` reads of it."""
+    return classifier_head(load_state_dict_file(path))
+
+
+def spatial_dim(image_size=IMAGE_SIZE) -> int:
+    """The length of a spatial feature row at an image size, from the library's plan (host only): 2023 at 299."""
+    v = [C.c_int() for _ in range(3)]
+    L.lib().inc_spatial_shape(C.byref(L.IncConfig(image_size=int(image_size))), *[C.byref(x) for x in v])
+    return v[0].value * v[1].value * v[2].value
+
+
+def extra_metrics(real, fake, names, args, head=None) -> dict:
+    """The values of ``isc``, ``pr`` and ``kid`` (those in ``names``) of two fp32 CUDA feature tensors, in printing order.  ``isc`` is
+    the score of ``fake`` alone (``real`` may be None) on ``head``'s weight: the unbiased logits, as in ADM's evaluator."""
     out = {}
+    if "isc" in names:
+        out["isc"], out["isc_std"] = M.inception_score(fake, head[0].to(fake.device))
     if "pr" in names:
         out.update(M.precision_recall(real, fake))
     if "kid" in names:
@@ -355,20 +435,54 @@ def load_images(path):
     return a
 
 
-def stats_of_images(images, net, batch_size=64, device="cuda") -> FeatureStats:
-    st = FeatureStats(FEATURE_DIM, device)
-    for i in range(0, len(images), batch_size):
-        st.update(net.features(torch.from_numpy(np.ascontiguousarray(images[i:i + batch_size])).to(device)))
-    return st
+def print_metrics(values):
+    """One line per metric; the Inception Score with its standard deviation over the splits."""
+    for k, v in values.items():
+        if k == "isc":
+            print(f"isc: {v:.6f} ± {values['isc_std']:.6f}")
+        elif k != "isc_std":
+            print(f"{k}: {v:.6f}")
 
 
-def features_of_images(images, net, batch_size=64, device="cuda"):
-    """(fp32 [N, 2048] on the device, FeatureStats): stats_of_images that keeps the features."""
-    st, feats = FeatureStats(FEATURE_DIM, device), []
-    for i in range(0, len(images), batch_size):
-        feats.append(net.features(torch.from_numpy(np.ascontiguousarray(images[i:i + batch_size])).to(device)))
-        st.update(feats[-1])
-    return torch.cat(feats), st
+class FeaturePass:
+    """One pass of the network over batches of uint8 images: the FeatureStats of ``pool_3``, with ``spatial`` those of the spatial
+    features from the same walk, and with ``keep`` the ``pool_3`` rows themselves (on the device)."""
+
+    def __init__(self, net, device="cuda", spatial=False, keep=False):
+        self.net, self.device = net, device
+        self.stats = FeatureStats(FEATURE_DIM, device)
+        self.stats_s = FeatureStats(net.spatial_dim, device) if spatial else None
+        self.feats = [] if keep else None
+
+    def update(self, images):
+        x = torch.from_numpy(np.ascontiguousarray(images)).to(self.device)
+        if self.stats_s is None:
+            feat = self.net.features(x)
+        else:
+            feat, spat = self.net.features(x, spatial=True)
+            self.stats_s.update(spat)
+        self.stats.update(feat)
+        if self.feats is not None:
+            self.feats.append(feat)
+        return self
+
+    def over(self, images, batch_size):
+        for i in range(0, len(images), batch_size):
+            self.update(images[i:i + batch_size])
+        return self
+
+
+def stats_of_images(images, net, batch_size=64, device="cuda", spatial=False):
+    """The FeatureStats of the pool features; ``spatial=True`` -> (that, the FeatureStats of the spatial features) from one pass."""
+    p = FeaturePass(net, device, spatial).over(images, batch_size)
+    return (p.stats, p.stats_s) if spatial else p.stats
+
+
+def features_of_images(images, net, batch_size=64, device="cuda", spatial=False):
+    """(fp32 [N, 2048] on the device, FeatureStats): stats_of_images that keeps the features.  ``spatial=True`` adds the FeatureStats
+    of the spatial features, accumulated in the same pass, as a third value."""
+    p = FeaturePass(net, device, spatial, keep=True).over(images, batch_size)
+    return (torch.cat(p.feats), p.stats, p.stats_s) if spatial else (torch.cat(p.feats), p.stats)
 
 
 def _is_stats(path) -> bool:
@@ -387,7 +501,10 @@ def build_parser():
     f = sub.add_parser("features", help="pool_3 features of an image array, with their mu and sigma")
     f.add_argument("--images", required=True, help=".npz / .npy of uint8 [N, H, W, 3]")
     f.add_argument("--output", required=True)
-    c = sub.add_parser("compare", help="FID (and with --metrics precision / recall, KID) of two statistics or feature files or image arrays")
+    for q in (s, f):
+        q.add_argument("--spatial", action="store_true", help="add mu_s, sigma_s: the statistics of the spatial features (sFID, --metrics fid_s)")
+    c = sub.add_parser("compare", help="FID (and with --metrics sFID, Inception Score, precision / recall, KID) of two statistics or feature "
+                                       "files or image arrays")
     c.add_argument("a", help="the reference (real) side")
     c.add_argument("b", help="the samples")
     add_metric_flags(c)
@@ -412,12 +529,22 @@ def main(argv=None):
 
     if args.cmd == "stats":
         images = load_images(args.images)                      # (a bad array ends the run before the weights are read)
+        if args.spatial:
+            st, st_s = stats_of_images(images, network(), args.batch_size, spatial=True)
+            save_stats(args.output, *st.mean_cov(), *st_s.mean_cov())
+            print(f"{args.output}: mu, sigma, mu_s, sigma_s of {st.n} images")
+            return args.output
         st = stats_of_images(images, network(), args.batch_size)
         st.save(args.output)
         print(f"{args.output}: mu, sigma of {st.n} images")
         return args.output
     if args.cmd == "features":
         images = load_images(args.images)
+        if args.spatial:
+            feat, st, st_s = features_of_images(images, network(), args.batch_size, spatial=True)
+            save_features(args.output, feat.cpu().numpy(), *st.mean_cov(), *st_s.mean_cov())
+            print(f"{args.output}: {FEATURES_KEY}, mu, sigma, mu_s, sigma_s of {st.n} images")
+            return args.output
         feat, st = features_of_images(images, network(), args.batch_size)
         save_features(args.output, feat.cpu().numpy(), *st.mean_cov())
         print(f"{args.output}: {FEATURES_KEY}, mu, sigma of {st.n} images")
@@ -429,27 +556,39 @@ def main(argv=None):
         print(f"fid: {fid:.6f}")
         return fid
     kinds = ["features" if has_features(f) else "stats" if _is_stats(f) else "images" for f in (args.a, args.b)]
-    for f, kind in zip((args.a, args.b), kinds):               # refused before the network is built or a kernel runs
-        if kind == "stats":
-            raise ValueError(f"{f} holds statistics only: --metrics {args.metrics} needs the features of both sides; write them with "
-                             "`python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz`")
+    both = "pr" in names or "kid" in names                     # pool_3 of both sides; isc: of the samples (b) alone
+    need_feat = (both, both or "isc" in names)
+    for f, kind, need in zip((args.a, args.b), kinds, need_feat):          # refused before the network is built or a kernel runs
+        if kind == "stats" and need:
+            raise ValueError(f"{f} holds statistics only: --metrics {args.metrics} needs the features of " + ("both sides" if both else "the samples") +
+                             "; write them with `python -m mapdit_amd.fid features --images A.npz --inception-weights FILE --output feats.npz`")
         if kind == "images" and args.inception_weights is None:
             raise ValueError(f"{f} is an image array: it needs --inception-weights")
-    feats, pairs = [], []
-    for f, kind in zip((args.a, args.b), kinds):
-        if kind == "features":
-            feats.append(torch.from_numpy(load_features(f)).to("cuda"))
-            pairs.append(load_stats(f) if "fid" in names else None)
-        else:
-            feat, st = features_of_images(load_images(f), network(), args.batch_size)
+        if "fid_s" in names and kind != "images" and not has_spatial(f):
+            raise ValueError(f"{f} holds no 'mu_s' / 'sigma_s': fid_s compares the spatial statistics, which " +
+                             ("pool_3 does not give; " if kind == "features" else "the file lacks; ") +
+                             "write them with `python -m mapdit_amd.fid stats --spatial --images A.npz --inception-weights FILE --output ref.npz`")
+    if "isc" in names and args.inception_weights is None:
+        raise ValueError("--metrics isc needs --inception-weights: the Inception Score reads the classifier head (fc.weight) of the file")
+    head = load_head(args.inception_weights) if "isc" in names else None   # (the head alone: no network for two feature files)
+    feats, pairs, pairs_s = [], [], []
+    for f, kind, need in zip((args.a, args.b), kinds, need_feat):
+        if kind == "images":
+            feat, st, *st_s = features_of_images(load_images(f), network(), args.batch_size, spatial="fid_s" in names)
             feats.append(feat)
             pairs.append(st.mean_cov() if "fid" in names else None)
+            pairs_s.append(st_s[0].mean_cov() if st_s else None)
+        else:
+            feats.append(torch.from_numpy(load_features(f)).to("cuda") if need else None)
+            pairs.append(load_stats(f) if "fid" in names else None)
+            pairs_s.append(load_stats(f, spatial=True)[2:] if "fid_s" in names else None)
     values = {}
     if "fid" in names:
         values["fid"] = frechet_distance(*pairs[0], *pairs[1])
-    values.update(extra_metrics(feats[0], feats[1], names, args))
-    for k, v in values.items():
-        print(f"{k}: {v:.6f}")
+    if "fid_s" in names:
+        values["fid_s"] = frechet_distance(*pairs_s[0], *pairs_s[1])
+    values.update(extra_metrics(feats[0], feats[1], names, args, head))
+    print_metrics(values)
     return values
 
 

@@ -6,6 +6,8 @@
     knn_radii(x, k=3)                       fp32 [N]: the k-th smallest squared distance to another row
     precision_recall(real, fake, k=3)       {"precision", "recall", "density", "coverage"}
     kid(real, fake, subsets=100, subset_size=1000, seed=0)     (mean, std) of the unbiased MMD^2 estimate, kernel (x.y / D + 1)^3
+    inception_score(feat, fc_weight, fc_bias=None, split_size=5000)    (mean, std) over the splits of exp(mean KL(p_n || p_bar)):
+                                            the softmax over feat . fc_weight^T is reduced on the Gram tile, never stored
 
 ``chunks`` (0: chosen by the library) only cuts the work differently; no result depends on it.
 """
@@ -131,12 +133,64 @@ def kid(real, fake, subsets=100, subset_size=1000, seed=0, chunks=0):
     return float(est.mean()), float(est.std())
 
 
+# ---- Inception Score ----------------------------------------------------------------------------------------------------------------
+def softmax_score(x, weight, bias=None, chunks=0):
+    """(ent fp64 0-dim, marg fp64 [C]) on the device: sum_n sum_c p log p and sum_n p_nc of p_n = softmax(x_n . w_c + bias_c), one
+    ``mapdit_softmax_score`` call (fp32 only inside the dot products; bias, exp and log in fp64)."""
+    x, weight = _features(x, "x"), _features(weight, "weight")
+    if x.shape[1] != weight.shape[1]:
+        raise ValueError(f"metrics: x has {x.shape[1]} dimensions, weight {weight.shape[1]}")
+    N, D, C = x.shape[0], x.shape[1], weight.shape[0]
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or not bias.is_cuda:
+            raise NotImplementedError("metrics: bias must be a CUDA tensor (HIP kernels, no CPU path)")
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (C,):
+            raise ValueError(f"metrics: bias has shape {tuple(bias.shape)} and dtype {bias.dtype}, expected fp32 [{C}]")
+        bias = bias.detach().contiguous()
+    lib = L.lib()
+    ent = torch.empty((), dtype=torch.float64, device=x.device)
+    marg = torch.empty(C, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = _workspace(lib.softmax_score_workspace_bytes(N, C, D, chunks), x.device, "softmax_score")
+        lib.softmax_score(x.data_ptr(), N, weight.data_ptr(), C, D, L.ptr(bias), ent.data_ptr(), marg.data_ptr(), chunks, ws.data_ptr(), ws.numel(),
+                          L.cur_stream())
+    return ent, marg
+
+
+def inception_score_from_sums(ent, marg, n) -> float:
+    """exp(KL) of one split of n samples from its two sums, in fp64 on the host: with P_c = marg[c] (the class marginal times n),
+    KL = (ent - sum_c P_c log(P_c / n)) / n, the mean over the samples of KL(p_n || p_bar).  A class with P_c = 0 adds 0."""
+    p = np.asarray(marg, np.float64)
+    nz = p > 0
+    cross = float(np.sum(p[nz] * np.log(p[nz] / n)))
+    return float(np.exp((float(ent) - cross) / n))
+
+
+def inception_score(feat, fc_weight, fc_bias=None, split_size=5000, chunks=0):
+    """(mean, std) over the splits of exp(mean_n KL(p_n || p_bar)): ADM's ``compute_inception_score`` - rows [i, i + split_size) per
+    split, the last one may be short, ``np.std`` (N) over the splits.  ``feat`` fp32 [N, 2048] ``pool_3``, ``fc_weight`` fp32
+    [1008, 2048] (``fid.classifier_head``), both CUDA tensors.  ``fc_bias=None``: the unbiased logits, as in ADM's evaluator and
+    torch-fidelity's ``logits_unbiased``.  One ``mapdit_softmax_score`` call per split; the host finishes each in fp64."""
+    feat, fc_weight = _features(feat, "feat"), _features(fc_weight, "fc_weight")
+    if split_size < 1:
+        raise ValueError(f"inception_score: split_size={split_size} (at least 1)")
+    if feat.shape[0] < 1:
+        raise ValueError("inception_score: no samples")
+    sums = []
+    for i in range(0, feat.shape[0], int(split_size)):
+        rows = feat[i:i + int(split_size)]
+        ent, marg = softmax_score(rows, fc_weight, fc_bias, chunks)
+        sums.append((ent, marg, rows.shape[0]))
+    scores = np.array([inception_score_from_sums(float(ent.cpu()), marg.cpu().numpy(), n) for ent, marg, n in sums], np.float64)
+    return float(scores.mean()), float(scores.std())
+
+
 # ---- the --metrics flags of fid.py and sample_fid.py --------------------------------------------------------------------------------
-METRICS = ("fid", "pr", "kid")
+METRICS = ("fid", "fid_s", "isc", "pr", "kid")
 
 
 def parse_metrics(text) -> tuple:
-    """"fid,pr,kid" -> the names in METRICS order; None or "" is the default, ("fid",)."""
+    """"fid,fid_s,isc,pr,kid" -> the names in METRICS order; None or "" is the default, ("fid",)."""
     names = [m.strip() for m in (text or "fid").split(",") if m.strip()]
     bad = [m for m in names if m not in METRICS]
     if bad or not names:
@@ -145,6 +199,7 @@ def parse_metrics(text) -> tuple:
 
 
 def add_metric_flags(p):
-    p.add_argument("--metrics", default=None, help="comma-separated: fid (default), pr (precision, recall, density, coverage), kid")
+    p.add_argument("--metrics", default=None, help="comma-separated: fid (default), fid_s (sFID: the Fréchet distance of the spatial features), "
+                                                   "isc (Inception Score), pr (precision, recall, density, coverage), kid")
     p.add_argument("--kid-subsets", type=int, default=100)
     p.add_argument("--kid-subset-size", type=int, default=1000, help="at most the smaller set's size")

@@ -7,7 +7,9 @@ them into pixels first (``arr_0``: [n, 8S, 8S, 3]).  ``--fid-ref REF.npz --incep
 FID of the samples against the reference statistics, accumulated batch by batch on the device (map-dit_amd/fid.py), printed, returned
 and written to ``fid_samples/<output-file>.fid.json``; the array is written as before.  ``--metrics fid,pr,kid`` (default ``fid``)
 adds precision / recall / density / coverage and KID (map-dit_amd/metrics.py) to that file (under its key ``metrics``) and to the output: ``--fid-ref`` must then
-be a file of ``python -m mapdit_amd.fid features`` (it holds ``pool_3``); the samples' features stay on the device.
+be a file of ``python -m mapdit_amd.fid features`` (it holds ``pool_3``); the samples' features stay on the device.  ``fid_s`` (sFID)
+needs ``mu_s`` / ``sigma_s`` in ``--fid-ref`` (``fid stats --spatial``) and accumulates the spatial statistics in the same pass of the
+network; ``isc`` (the samples' Inception Score, stored as ``isc`` and ``isc_std``) reads the classifier head of ``--inception-weights``.
 
 ``--sample-rng counter``: sample i - its latent, its label, the noise of every step - is a function of (``--seed``, i) alone
 (map-dit_amd/sample_rng.py), batch b holds the sample indices [b n, (b + 1) n) (n = ``--batch-size``), and every finished batch is
@@ -168,37 +170,71 @@ def open_manifest(pdir: str, manifest: dict):
         _replace_into(path, lambda f: f.write(json.dumps(manifest, indent=1, sort_keys=True).encode()))
 
 
+class FidPass:
+    """--fid-ref: the one pass of the feature network over the samples (fid.FeaturePass) - the pool statistics, with ``fid_s`` the
+    spatial statistics from the same walk, and the ``pool_3`` rows themselves where a metric needs them (isc, pr, kid) - and the
+    record made of it.  With the default --metrics it reads, computes and keeps what the FID alone needs.  What can be refused
+    (the reference's dimensions, a weight file without the classifier head) was refused by check_fid_flags, before any model."""
+
+    def __init__(self, args, device):
+        from . import fid as FID
+        from .vae import load_state_dict_file
+        self.FID, self.args, self.device = FID, args, device
+        self.names = FID.parse_metrics(args.metrics)
+        self.spatial = "fid_s" in self.names
+        self.ref = FID.load_stats(args.fid_ref, spatial=self.spatial)
+        if self.ref[0].shape != (FID.FEATURE_DIM,):
+            raise ValueError(f"--fid-ref {args.fid_ref}: statistics of {self.ref[0].shape[0]} dimensions, the pool features have {FID.FEATURE_DIM}")
+        sd = getattr(args, "inception_sd", None)                          # (check_fid_flags read it for isc: the file is read once)
+        if sd is None and "isc" in self.names:
+            sd = load_state_dict_file(args.inception_weights)
+        if sd is None:
+            net = FID.InceptionFeatures.from_file(args.inception_weights, device, args.inception_precision)
+        else:
+            net = FID.InceptionFeatures.from_state_dict(sd, device, args.inception_precision)
+        self.head = FID.classifier_head(sd) if "isc" in self.names else None
+        keep = any(m in self.names for m in FID.FEATURE_METRICS)           # their features stay on the device
+        self.run = FID.FeaturePass(net, device, self.spatial, keep)
+
+    @property
+    def n(self):
+        return self.run.stats.n
+
+    def update(self, images):
+        """uint8 [n, H, W, 3] (numpy): the stored bytes."""
+        self.run.update(images)
+
+    def record(self, path) -> dict:
+        FID, args = self.FID, self.args
+        value = FID.frechet_distance(*self.run.stats.mean_cov(), *self.ref[:2])
+        record = {"fid": value, "n": self.run.stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}
+        if self.names != ("fid",):
+            extra = {}
+            if self.spatial:
+                extra["fid_s"] = FID.frechet_distance(*self.run.stats_s.mean_cov(), *self.ref[2:])
+            if self.run.feats is not None:
+                both = "pr" in self.names or "kid" in self.names
+                ref_feat = torch.from_numpy(FID.load_features(args.fid_ref)).to(self.device) if both else None
+                extra.update(FID.extra_metrics(ref_feat, torch.cat(self.run.feats), self.names, args, self.head))
+            record["metrics"] = extra                                      # (its "precision" is not the record's: that is the operand format)
+        return record
+
+    def report(self, record):
+        print(f"fid: {record['fid']:.6f}")
+        self.FID.print_metrics(record.get("metrics", {}))
+        return record["fid"]
+
+
 def fid_record(args, path, out, device):
     """--fid-ref under --sample-rng counter: the FID and --metrics in one pass over the assembled bytes, in batches of --batch-size from
     index 0 - a function of the stored array alone -> the FID."""
     import json
-
-    from . import fid as FID
-    ref_mu, ref_sigma = FID.load_stats(args.fid_ref)
-    if ref_mu.shape != (FID.FEATURE_DIM,):
-        raise ValueError(f"--fid-ref {args.fid_ref}: statistics of {ref_mu.shape[0]} dimensions, the pool features have {FID.FEATURE_DIM}")
-    fid_net = FID.InceptionFeatures.from_file(args.inception_weights, device, args.inception_precision)
-    fid_stats = FID.FeatureStats(FID.FEATURE_DIM, device)
-    metric_names = FID.parse_metrics(args.metrics)
-    keep_feats = metric_names != ("fid",)
-    feats = []
+    fid_pass = FidPass(args, device)
     for i in range(0, len(out), args.batch_size):
-        feat = fid_net.features(torch.from_numpy(out[i:i + args.batch_size]).to(device))
-        fid_stats.update(feat)
-        if keep_feats:
-            feats.append(feat)
-    value = FID.frechet_distance(*fid_stats.mean_cov(), ref_mu, ref_sigma)
-    record = {"fid": value, "n": fid_stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}
-    extra = {}
-    if keep_feats:
-        ref_feat = torch.from_numpy(FID.load_features(args.fid_ref)).to(device)
-        extra = FID.extra_metrics(ref_feat, torch.cat(feats), metric_names, args)
-        record["metrics"] = extra
+        fid_pass.update(out[i:i + args.batch_size])
+    record = fid_pass.record(path)
     _replace_into(path + ".fid.json", lambda f: f.write(json.dumps(record).encode()))
-    print(f"fid: {value:.6f}")
-    for k, v in extra.items():
-        print(f"{k}: {v:.6f}")
-    return value
+    return fid_pass.report(record)
 
 
 def run_counter(args, train_args, device, want_fid, shard):
@@ -272,7 +308,13 @@ def check_fid_flags(args) -> bool:
             raise FileNotFoundError(f"{flag} {path}: no such file")
     if not args.use_vae:
         raise ValueError("--fid-ref needs pixels: the feature network reads 3-channel images, --use-vae false writes latents")
-    if names != ("fid",):
+    if "fid_s" in names:
+        from .fid import has_spatial
+        if not has_spatial(args.fid_ref):
+            raise ValueError(f"--metrics {metrics}: fid_s needs the reference's spatial statistics: --fid-ref {args.fid_ref} holds no 'mu_s' / "
+                             "'sigma_s'; write them with `python -m mapdit_amd.fid stats --spatial --images A.npz --inception-weights FILE "
+                             "--output ref.npz`")
+    if "pr" in names or "kid" in names:                                   # (isc is the samples' own: it reads the head of --inception-weights)
         from .fid import features_rows
         rows = features_rows(args.fid_ref)
         if rows is None:
@@ -281,6 +323,18 @@ def check_fid_flags(args) -> bool:
         if "kid" in names and args.kid_subset_size > min(rows, args.num_samples):
             raise ValueError(f"--metrics {metrics}: --kid-subset-size {args.kid_subset_size} exceeds the smaller set (--num-samples "
                              f"{args.num_samples}, {rows} reference features)")
+    if "fid_s" in names:
+        from .fid import spatial_dim
+        with np.load(args.fid_ref) as z:
+            got = z["mu_s"].shape
+        if got != (spatial_dim(),):
+            raise ValueError(f"--metrics {metrics}: --fid-ref {args.fid_ref} holds spatial statistics of shape {got}, the spatial features have "
+                             f"{spatial_dim()} dimensions")
+    if "isc" in names:                                                    # a file without fc.weight is a KeyError here, not after the sampling
+        from .fid import classifier_head
+        from .vae import load_state_dict_file
+        args.inception_sd = load_state_dict_file(args.inception_weights)
+        classifier_head(args.inception_sd)
     return True
 
 
@@ -307,16 +361,7 @@ def main(argv=None):
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
     diffusion, solver = S.make_diffusion(args, train_args)
-    if want_fid:
-        from . import fid as FID
-        ref_mu, ref_sigma = FID.load_stats(args.fid_ref)
-        if ref_mu.shape != (FID.FEATURE_DIM,):
-            raise ValueError(f"--fid-ref {args.fid_ref}: statistics of {ref_mu.shape[0]} dimensions, the pool features have {FID.FEATURE_DIM}")
-        fid_net = FID.InceptionFeatures.from_file(args.inception_weights, device, args.inception_precision)
-        fid_stats = FID.FeatureStats(FID.FEATURE_DIM, device)
-        metric_names = FID.parse_metrics(args.metrics)
-        keep_feats = metric_names != ("fid",)                             # pr / kid: the samples' features stay on the device
-        feats = []
+    fid_pass = FidPass(args, device) if want_fid else None
 
     n = args.batch_size
     use_cfg = args.cfg_scale > 1.0
@@ -343,31 +388,19 @@ def main(argv=None):
             samples = vae.decode(samples).sample
         gathered.append(S.to_uint8_nhwc(samples))
         if want_fid:                                                      # the stored bytes, cut where the array is cut
-            keep = min(len(gathered[-1]), args.num_samples - fid_stats.n)
+            keep = min(len(gathered[-1]), args.num_samples - fid_pass.n)
             if keep > 0:
-                feat = fid_net.features(torch.from_numpy(gathered[-1][:keep]).to(device))
-                fid_stats.update(feat)
-                if keep_feats:
-                    feats.append(feat)
+                fid_pass.update(gathered[-1][:keep])
     out = np.concatenate(gathered, axis=0)[: args.num_samples]
     os.makedirs(os.path.join(args.result_dir, "fid_samples"), exist_ok=True)
     path = os.path.join(args.result_dir, "fid_samples", args.output_file)
     np.savez(path, arr_0=out)
     if want_fid:
         import json
-        value = FID.frechet_distance(*fid_stats.mean_cov(), ref_mu, ref_sigma)
-        record = {"fid": value, "n": fid_stats.n, "ref": args.fid_ref, "precision": args.inception_precision, "samples": path}
-        extra = {}
-        if keep_feats:
-            ref_feat = torch.from_numpy(FID.load_features(args.fid_ref)).to(device)
-            extra = FID.extra_metrics(ref_feat, torch.cat(feats), metric_names, args)
-            record["metrics"] = extra                                      # (its "precision" is not the record's: that is the operand format)
+        record = fid_pass.record(path)
         with open(path + ".fid.json", "w") as f:
             json.dump(record, f)
-        print(f"fid: {value:.6f}")
-        for k, v in extra.items():
-            print(f"{k}: {v:.6f}")
-        return value
+        return fid_pass.report(record)
     return path
 
 
