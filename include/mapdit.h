@@ -1144,6 +1144,79 @@ int mapdit_softmax_score(const float* X, int N, const float* W, int C, int D, co
                          void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * DINOv2 ViT / FD-DINOv2 (additive within abi 5; csrc/vit.hip, dinov2.py): the CLS feature after the final LayerNorm of the public
+ * dinov2_vit{s,b,l}14 networks - a plain pre-norm ViT: LayerNorm (eps 1e-6), biased linears, softmax attention with head_dim 64,
+ * exact (erf) GELU, LayerScale, patch 14 - whose Frechet distance (fid.FeatureStats(D), fid.frechet_distance) is the FD-DINOv2 of
+ * Stein et al. 2023 and of EDM2 (ViT-L/14: D = 1024).  Activations between the kernels are 16-bit (bf16; _f16 twins below),
+ * accumulation is fp32 and THE RESIDUAL STREAM IS FP32 (the residual carries outliers of a few hundred).  No registers, no SwiGLU.
+ * Every entry point sends its launches to `stream`, allocates nothing, synchronises nothing and reads nothing back; every tensor is
+ * 16-byte aligned.  PARITY WITH THE HUB WEIGHTS AND WITH EDM2'S calculate_metrics.py UNPINNED: the network is restated from its public
+ * description (tests/dinov2_reference.py); the resize is pinned to the installed torch's F.interpolate.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define MAPDIT_VIT_PATCH 14
+#define MAPDIT_VIT_PATCH_K 592   /* a patch row: 3 * 14 * 14 = 588 values in (c, py, px) order, padded with zeros to a multiple of 16 */
+#define MAPDIT_VIT_MAX_DEPTH 64
+enum { MAPDIT_VIT_IMG_U8_NHWC = 0, MAPDIT_VIT_IMG_F32_NCHW = 1 };
+enum { MAPDIT_VIT_OUT_F32 = 0, MAPDIT_VIT_OUT_16 = 1 };
+/* images: uint8 [N, H, W, 3] or fp32 [N, 3, H, W] in [-1, 1], H, W >= 8 -> rows 16-bit [N * P, MAPDIT_VIT_PATCH_K], P = (size / 14)^2, row
+ * (n, gy, gx) = the pixels of that patch in (c, py, px) order, the tail [588, 592) zero.  One kernel: the bicubic resize to size x size
+ * WITH ANTIALIASING in F.interpolate's map (mode="bicubic", antialias=True, align_corners=False: Keys cubic with a = -0.5, the support
+ * widened by the scale when downsampling, the weights normalised per output pixel, the horizontal pass first, no clamping of the
+ * result) on pixel values in 0 .. 255 (the fp32 form maps (v + 1) * 127.5 first), then / 255, - mean (0.485, 0.456, 0.406), / std (0.229,
+ * 0.224, 0.225): EDM2's DINOv2Detector(resize_mode="torch").  The tap range and each weight's argument are formed in exact integer
+ * arithmetic (one fp32 division per weight); size == H == W reduces to the identity taps: the values are (v / 255 - mean) / std. */
+int mapdit_vit_prepare(const void* images, int img_kind, uint16_t* rows, int N, int H, int W, int size, void* stream);
+/* out[m][co] = bias[co] + sum_c in[m][c] * w[co][c]: in 16-bit [M, Cin], w 16-bit [Cout, Cin], bias fp32, out fp32 or 16-bit (fp16
+ * saturated) [M, Cout]; Cin and Cout multiples of 16.  mapdit_inc_conv's implicit GEMM as a 1 x 1 convolution over M pixels (the
+ * 128-wide tile where Cout % 128 == 0, the 64-wide one else; the same bits): a row's bits do not depend on M. */
+int mapdit_vit_linear(const uint16_t* in, const uint16_t* w, const float* bias, void* out, int out_kind, long M, int Cin, int Cout, void* stream);
+/* tokens fp32 [N, T, D], T = 1 + P: row 0 = cls + pos[0], row 1 + p = patch[n * P + p] + pos[1 + p].  patch fp32 [N * P, D] (the
+ * patch-embed linear's output), cls fp32 [D], pos fp32 [T, D], interpolated to this T by the caller.  D a multiple of 4. */
+int mapdit_vit_embed(const float* patch, const float* cls, const float* pos, float* tokens, int N, int T, int D, void* stream);
+/* out[m] = (x[m] - mean) / sqrt(var + eps) * w + b over rows of D fp32 values ldx apart (ldx >= D; the final norm reads the CLS rows
+ * alone with ldx = T * D); out dense [M, D], 16-bit or fp32.  Two passes in fp32 (the mean, then the biased variance of the
+ * deviations), one wave per row in a fixed order: a row's bits do not depend on M.  D and ldx multiples of 4. */
+int mapdit_vit_layernorm(const float* x, long ldx, const float* w, const float* b, float eps, void* out, int out_kind, long M, int D,
+                         void* stream);
+/* Softmax attention, head_dim 64 ONLY (every DINOv2 size; another head_dim is refused), scale 1 / 8, any T >= 2: q, k, v of head h are
+ * columns [64 h, 64 h + 64) of the three D-wide thirds of the packed 16-bit rows qkv [N * T, 3 D], D = 64 * heads; out 16-bit [N * T, D].
+ * Both products on the MFMA; keys are streamed in tiles of 64 with an online softmax (running maximum and sum in fp32, exp in
+ * fp32, the probabilities rounded to the operand format for the second product).  Query rows and key columns past T are masked and
+ * never loaded: a sample's bits do not depend on its neighbours or on N. */
+int mapdit_vit_attention(const uint16_t* qkv, uint16_t* out, int N, int T, int heads, int head_dim, void* stream);
+/* out[i] = 0.5 x (1 + erf(x / sqrt 2)), x = in[i] (the exact GELU; evaluated as 0.5 x erfc(-x / sqrt 2), which has no cancellation for
+ * negative x): 16-bit in and out (fp16 saturated at +-65504), the math in fp32; n a multiple of 8; in may be out. */
+int mapdit_vit_gelu(const uint16_t* in, uint16_t* out, long n, void* stream);
+/* x[m][d] += gamma[d] * y[m][d] (LayerScale and the residual, one fma): x fp32 [M, D], y fp32 (MAPDIT_VIT_OUT_F32) or 16-bit, gamma fp32 [D]. */
+int mapdit_vit_residual(float* x, const void* y, int y_kind, const float* gamma, long M, int D, void* stream);
+/* The network.  Weight table (host array of device pointers): the MAPDIT_VIT_W_* slots, then per block MAPDIT_VIT_W_BLOCK slots in
+ * MAPDIT_VIT_B_* order.  Linear weights 16-bit [out, in] (PATCH: [dim, MAPDIT_VIT_PATCH_K], the convolution weight flattened (c, py,
+ * px), its tail zero); biases, LayerNorm weights, LayerScale gammas, cls [dim] and pos [T, dim] fp32. */
+enum { MAPDIT_VIT_W_PATCH = 0, MAPDIT_VIT_W_PATCH_BIAS, MAPDIT_VIT_W_CLS, MAPDIT_VIT_W_POS, MAPDIT_VIT_W_NORM, MAPDIT_VIT_W_NORM_BIAS,
+       MAPDIT_VIT_W_GLOBAL };
+enum { MAPDIT_VIT_B_LN1 = 0, MAPDIT_VIT_B_LN1_BIAS, MAPDIT_VIT_B_QKV, MAPDIT_VIT_B_QKV_BIAS, MAPDIT_VIT_B_PROJ, MAPDIT_VIT_B_PROJ_BIAS,
+       MAPDIT_VIT_B_LS1, MAPDIT_VIT_B_LN2, MAPDIT_VIT_B_LN2_BIAS, MAPDIT_VIT_B_FC1, MAPDIT_VIT_B_FC1_BIAS, MAPDIT_VIT_B_FC2,
+       MAPDIT_VIT_B_FC2_BIAS, MAPDIT_VIT_B_LS2, MAPDIT_VIT_W_BLOCK };
+typedef struct {
+    int image_size;           /* the square every image is resized to: 224 for FD-DINOv2 (a multiple of patch; T = 1 + (image_size / patch)^2) */
+    int patch;                /* 14 (the packing constant MAPDIT_VIT_PATCH; anything else is refused) */
+    int dim;                  /* 384 / 768 / 1024 for ViT-S / B / L; a multiple of 16 */
+    int depth;
+    int heads;                /* dim / 64 */
+    int mlp_dim;              /* 4 * dim in the public networks; a multiple of 16 */
+    float ln_eps;             /* 1e-6 */
+} mapdit_vit_config_t;
+/* Bytes mapdit_vit_features needs for N images: the patch rows, the fp32 token stream and one fp32 branch output, two 16-bit [M, dim]
+ * activations, the qkv rows and the [M, mlp_dim] MLP activation, M = N * T.  0 with a message in mapdit_last_error() when refused:
+ * dim != 64 * heads, dim or mlp_dim no multiple of 16, image_size no multiple of patch, patch != 14, depth outside 1 .. 64, N < 1. */
+size_t mapdit_vit_workspace_bytes(const mapdit_vit_config_t* cfg, int N);
+/* prepare -> patch embed -> embed -> depth x { LN, qkv, attention, proj, x += ls1 * y;  LN, fc1, GELU, fc2, x += ls2 * y } -> the final
+ * LayerNorm on row 0 of every sample -> feat fp32 [N, dim].  images as for mapdit_vit_prepare (H, W >= 8).  An image alone and in a
+ * batch gives the same bits.  Refusals as above, plus a workspace that is too small or not 256-byte aligned and a null weight slot. */
+int mapdit_vit_features(const mapdit_vit_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                        int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
  * holds fp16 bits instead of bf16 bits.  (mapdit_weightnorm_fwd*_f16: w_bf16 receives fp16; the w_split3 image stays a bf16
  * split - the fp32-accurate conditioning GEMMs run on bf16 terms in every engine.)
@@ -1225,6 +1298,16 @@ int mapdit_inc_features_f16(const mapdit_inc_config_t* cfg, const void* const* w
                             int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
 int mapdit_inc_features_tap_f16(const mapdit_inc_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N,
                                 int H, int W, float* feat, float* spatial, void* workspace, size_t ws_bytes, void* stream);
+int mapdit_vit_prepare_f16(const void* images, int img_kind, uint16_t* rows, int N, int H, int W, int size, void* stream);
+int mapdit_vit_linear_f16(const uint16_t* in, const uint16_t* w, const float* bias, void* out, int out_kind, long M, int Cin, int Cout,
+                          void* stream);
+int mapdit_vit_layernorm_f16(const float* x, long ldx, const float* w, const float* b, float eps, void* out, int out_kind, long M, int D,
+                             void* stream);
+int mapdit_vit_attention_f16(const uint16_t* qkv, uint16_t* out, int N, int T, int heads, int head_dim, void* stream);
+int mapdit_vit_gelu_f16(const uint16_t* in, uint16_t* out, long n, void* stream);
+int mapdit_vit_residual_f16(float* x, const void* y, int y_kind, const float* gamma, long M, int D, void* stream);
+int mapdit_vit_features_f16(const mapdit_vit_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                            int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,12 @@ written as ``fid_samples/<output-file>.parts/<first>-<end>.npy`` beside a ``mani
 the same command again skips the batches whose part exists (that is resuming); ``--shard R/W`` takes the batches with b % W == R, so W
 processes on W GPUs share a run; whichever process finds every part present assembles ``arr_0`` in index order and computes the
 metrics from the assembled bytes.  The finished file has the same bits whatever history produced it.  A manifest that differs in any
-key is refused before any model is built."""
+key is refused before any model is built.
+
+``--dinov2-ref REF.npz --dinov2-weights FILE`` (together, and with pixels): FD-DINOv2, the Fréchet distance on the CLS features of the
+DINOv2 ViT (map-dit_amd/dinov2.py) against the reference's ``mu_dinov2`` / ``sigma_dinov2`` - one more pass over the same uint8 bytes
+the FID pass reads (under ``--sample-rng counter``: over the assembled array), printed as ``fd_dinov2:`` and written to
+``fid_samples/<output-file>.fd_dinov2.json``.  The flags have no bearing on the array, the manifest or ``.fid.json``."""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +62,10 @@ def build_parser():
     p.add_argument("--inception-precision", choices=["f16", "bf16"], default="f16", help="16-bit operand format of the feature network")
     from .metrics import add_metric_flags
     add_metric_flags(p)                                                   # --metrics fid,pr,kid (default fid): pr and kid need pool_3 in --fid-ref
+    p.add_argument("--dinov2-ref", type=str, default=None, help="reference statistics (.npz with mu_dinov2 and sigma_dinov2): compute FD-DINOv2")
+    p.add_argument("--dinov2-weights", type=str, default=None,
+                   help="dinov2_vitl14_pretrain weights (.safetensors, or a torch state dict) for --dinov2-ref")
+    p.add_argument("--dinov2-precision", choices=["f16", "bf16"], default="f16", help="16-bit operand format of the DINOv2 network")
     p.add_argument("--shard", type=str, default="0/1",
                    help="R/W with --sample-rng counter: this process takes the batches b with b %% W == R (start W processes by hand or from a job script)")
     return p
@@ -237,7 +246,66 @@ def fid_record(args, path, out, device):
     return fid_pass.report(record)
 
 
-def run_counter(args, train_args, device, want_fid, shard):
+class DinoPass:
+    """--dinov2-ref: one pass of the DINOv2 network over the samples' bytes and the record made of it.  What can be refused (half
+    of the flag pair, latents, a reference of another dimension) was refused by check_dinov2_flags, before any model."""
+
+    def __init__(self, args, device):
+        from . import dinov2 as DINO
+        self.DINO, self.args = DINO, args
+        self.ref = DINO.load_stats(args.dinov2_ref)
+        net = DINO.DinoV2Features.from_state_dict(args.dinov2_sd, device, args.dinov2_precision)
+        args.dinov2_sd = None                                              # (the host copy of the weights is not needed again)
+        self.run = DINO.FeaturePass(net, device)
+
+    @property
+    def n(self):
+        return self.run.stats.n
+
+    def update(self, images):
+        self.run.update(images)
+
+    def finish(self, path) -> float:
+        """Writes ``<samples>.fd_dinov2.json`` and prints ``fd_dinov2:`` -> the value."""
+        import json
+        value = self.DINO.fd_dinov2(*self.run.stats.mean_cov(), *self.ref)
+        record = {"fd_dinov2": value, "n": self.run.stats.n, "ref": self.args.dinov2_ref, "precision": self.args.dinov2_precision, "samples": path}
+        _replace_into(path + ".fd_dinov2.json", lambda f: f.write(json.dumps(record).encode()))
+        print(f"fd_dinov2: {value:.6f}")
+        return value
+
+
+def dinov2_record(args, path, out, device):
+    """--dinov2-ref under --sample-rng counter: FD-DINOv2 of the assembled bytes, in batches of --batch-size from index 0."""
+    dino_pass = DinoPass(args, device)
+    for i in range(0, len(out), args.batch_size):
+        dino_pass.update(out[i:i + args.batch_size])
+    return dino_pass.finish(path)
+
+
+def check_dinov2_flags(args) -> bool:
+    """Before anything is built: --dinov2-ref and --dinov2-weights go together, name files, need pixels, and agree on the dimension."""
+    if args.dinov2_ref is None and args.dinov2_weights is None:
+        return False
+    if args.dinov2_ref is None or args.dinov2_weights is None:
+        raise ValueError("--dinov2-ref and --dinov2-weights go together: FD-DINOv2 needs the reference statistics and the feature network")
+    for flag, path in (("--dinov2-ref", args.dinov2_ref), ("--dinov2-weights", args.dinov2_weights)):
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{flag} {path}: no such file")
+    if not args.use_vae:
+        raise ValueError("--dinov2-ref needs pixels: the feature network reads 3-channel images, --use-vae false writes latents")
+    from . import dinov2 as DINO
+    from .vae import load_state_dict_file
+    mu, _ = DINO.load_stats(args.dinov2_ref)
+    args.dinov2_sd = load_state_dict_file(args.dinov2_weights)             # (read once: DinoPass builds the network from it)
+    dim = DINO.feature_dim(args.dinov2_sd)
+    if mu.shape[0] != dim:
+        raise ValueError(f"--dinov2-ref {args.dinov2_ref}: statistics of {mu.shape[0]} dimensions, --dinov2-weights {args.dinov2_weights} is a "
+                         f"network of dim {dim}")
+    return True
+
+
+def run_counter(args, train_args, device, want_fid, shard, want_dino=False):
     """main() under --sample-rng counter, from the manifest on.  Returns the parts directory while parts are missing, else what main()
     returns: the FID with --fid-ref, the .npz path without."""
     n = args.batch_size
@@ -289,7 +357,10 @@ def run_counter(args, train_args, device, want_fid, shard):
     if not path.endswith(".npz"):
         path += ".npz"                                                     # (np.savez appends it to a name; a file object takes none)
     _replace_into(path, lambda f: np.savez(f, arr_0=out))
-    return fid_record(args, path, out, device) if want_fid else path
+    result = fid_record(args, path, out, device) if want_fid else path
+    if want_dino:
+        dinov2_record(args, path, out, device)
+    return result
 
 
 def check_fid_flags(args) -> bool:
@@ -343,6 +414,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     S.check_vae_flags(args)                                               # a missing --vae-weights file ends the run before any model is built
     want_fid = check_fid_flags(args)                                      # (so does half of the FID flag pair)
+    want_dino = check_dinov2_flags(args)                                  # (and half of the FD-DINOv2 pair, or a reference of another dimension)
     shard = check_shard_flags(args)                                       # (and a --shard that is no R/W with R < W, or has no counter rng)
     if args.seed is not None:
         torch.manual_seed(args.seed)
@@ -355,13 +427,14 @@ def main(argv=None):
         raise ValueError(f"--num-classes {args.num_classes} != the trained model's num_classes {train_args['num_classes']} "
                          "(config.yaml): labels and the null label would fall outside its embedding table")
     if args.sample_rng == "counter":
-        return run_counter(args, train_args, device, want_fid, shard)
+        return run_counter(args, train_args, device, want_fid, shard, want_dino)
     model = get_model(train_args).to(device)
     S.load_weights(model, args.result_dir, args.ema_std, args.ckpt, verbose=False)
     model.gemm_precision = args.precision
     vae = S.load_vae(args.vae_path, device, args.vae_weights, args.vae_precision, args.vae_norm_groups) if args.use_vae else None
     diffusion, solver = S.make_diffusion(args, train_args)
     fid_pass = FidPass(args, device) if want_fid else None
+    dino_pass = DinoPass(args, device) if want_dino else None
 
     n = args.batch_size
     use_cfg = args.cfg_scale > 1.0
@@ -391,10 +464,16 @@ def main(argv=None):
             keep = min(len(gathered[-1]), args.num_samples - fid_pass.n)
             if keep > 0:
                 fid_pass.update(gathered[-1][:keep])
+        if want_dino:                                                     # one more pass over the same bytes
+            keep = min(len(gathered[-1]), args.num_samples - dino_pass.n)
+            if keep > 0:
+                dino_pass.update(gathered[-1][:keep])
     out = np.concatenate(gathered, axis=0)[: args.num_samples]
     os.makedirs(os.path.join(args.result_dir, "fid_samples"), exist_ok=True)
     path = os.path.join(args.result_dir, "fid_samples", args.output_file)
     np.savez(path, arr_0=out)
+    if want_dino:
+        dino_pass.finish(path)
     if want_fid:
         import json
         record = fid_pass.record(path)
