@@ -868,6 +868,19 @@ int mapdit_engine_set_input_grad(mapdit_engine_t* e, float* dx, int input_only);
  * forward; keep each micro-batch's loss such a mean and fold 1 / k into the optimiser's gradient scale instead of dividing the loss, or
  * set the loss scale k times higher. */
 int mapdit_engine_set_grad_accumulate(mapdit_engine_t* e, int on);
+/* Hidden-state gradient (additive within abi 5; REPA, repa.py).  The fp32 residual stream after block `block` is the saved checkpoint
+ * mapdit_engine_peek(MAPDIT_PEEK_B_XOUT, block) returns, at every recompute level.  One-shot, like the input-gradient request: the next
+ * backward treats dh fp32 [N * T, D] - the true, unscaled gradient of the loss with respect to that block's output - as a second source
+ * of gradient at that point, in the stage of block `block` + 1 (mapdit_engine_backward and mapdit_engine_backward_stages alike; dh is
+ * read there and must stay alive until then).  A forward drops an unconsumed request; dh = NULL clears it.  How: the pass whose x' is
+ * that checkpoint is the attention-branch residual / modulate backward of block `block` + 1, which forms dx' = ca * dxo + (modulate
+ * backward) and derives the gradients of block `block`'s MLP branch from dx' in the same kernel; adding dh to dx' equals adding
+ * dh * loss_scale / ca to dxo before the pass runs, and dxo is the buffer block `block` + 1's MLP-branch pass has just written
+ * (mapdit_repa_stream_add on the 16-bit gradient stream: one more rounding of that stream; the fp32 form on an fp32 stream).
+ * Refused, with a mapdit_last_error() naming "hidden": an inference engine, MAPDIT_PREC_BF16X3, the LayerNorm form
+ * (MAPDIT_OFF_NO_LAYERNORM), block outside 0 .. depth - 2 (the last block's output feeds the final layer, whose pass has no dxo), a staged
+ * backward in progress, and - by the backward itself - an input-only backward. */
+int mapdit_engine_set_hidden_grad(mapdit_engine_t* e, int block, const float* dh);
 
 /* Measurement hook: bracket every launch of one kernel family with HIP events on the launch stream.
  * MAPDIT_PROF_FC1_FWD = the block-MLP fc1 GEMM (gemm NT + SILU2 epilogue, [N*T, 4D] = [N*T, D] x [4D, D]^T). */
@@ -1215,6 +1228,48 @@ size_t mapdit_vit_workspace_bytes(const mapdit_vit_config_t* cfg, int N);
  * batch gives the same bits.  Refusals as above, plus a workspace that is too small or not 256-byte aligned and a null weight slot. */
 int mapdit_vit_features(const mapdit_vit_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
                         int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
+/* The same walk with the final LayerNorm on every row (additive within abi 5): tokens [N, T, dim], T = 1 + (image_size / 14)^2, fp32
+ * (MAPDIT_VIT_OUT_F32) or 16-bit (MAPDIT_VIT_OUT_16).  Row 0 of a sample is its CLS token - with an fp32 output the bits of
+ * mapdit_vit_features - and row 1 + p patch p in row-major grid order (gy * g + gx: the order of the DiT's patchify).  Workspace,
+ * refusals and the alone-or-in-a-batch property as for mapdit_vit_features. */
+int mapdit_vit_tokens(const mapdit_vit_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                      int W, void* tokens, int out_kind, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * REPA, representation alignment (Yu et al. 2024; additive within abi 5; csrc/repa.hip, repa.py): a three-layer MLP
+ * z = W3 silu(W2 silu(W1 h + b1) + b2) + b3 projects the hidden state h after an early block, and each projected token is pulled
+ * toward the DINOv2 patch token f of the clean image by a negative cosine similarity.  The products are mapdit_gemm_* (16-bit operands,
+ * fp32 accumulation, fp32 results); these are the pointwise passes between them.  Every tensor is 16-byte aligned; nothing is
+ * allocated, synchronised or read back.  No reference counterpart: the reference trains without it.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define MAPDIT_REPA_PART_ROWS 128   /* rows per partial of the bias gradient's column sum */
+enum { MAPDIT_REPA_F_F32 = 0, MAPDIT_REPA_F_F16 = 1 };
+/* pre fp32 [M, C] (a GEMM's result) += bias[C], in place: the pre-activation the backward reads; act 16-bit [M, C] =
+ * round(silu(pre)) (fp16 saturated), or NULL for a layer without activation (the bias alone).  C a multiple of 8. */
+int mapdit_repa_bias_silu_fwd(float* pre, const float* bias, uint16_t* act, long M, int C, void* stream);
+/* dpre = alpha * dact * silu'(pre), silu'(x) = s (1 + x (1 - s)), s = sigmoid(x); pre = NULL: dpre = alpha * dact (the layer without
+ * activation).  dact, pre fp32 [M, C]; dpre16 16-bit [M, C] = round(dpre), or NULL.  The bias gradient dbias[C] = (accumulate ?
+ * dbias : 0) + bias_scale * sum_m dpre[m][c] is taken from the fp32 dpre as a deterministic column sum: part fp32 [ceil(M /
+ * MAPDIT_REPA_PART_ROWS), C] (scratch) receives the sum over each run of MAPDIT_REPA_PART_ROWS rows - four interleaved row walks in
+ * row order, added in a fixed order - and mapdit_repa_colsum_finish adds the partials in index order.  No atomics: two runs give the
+ * same bits.  alpha carries an fp16 loss scale in, bias_scale takes it out.  C a multiple of 8, M <= 128 * 65,535. */
+int mapdit_repa_bias_silu_bwd(const float* dact, const float* pre, uint16_t* dpre16, float* dbias, float* part, float alpha, float bias_scale,
+                              int accumulate, long M, int C, void* stream);
+int mapdit_repa_colsum_finish(const float* part, int nparts, float* out, float scale, int accumulate, int C, void* stream);
+/* loss[n] = -(1 / T) sum_t <z_t / max(|z_t|, 1e-12), f_t / max(|f_t|, 1e-12)> over the T rows of sample n, and dz [R, P] = g_n *
+ * d loss[n] / d z with g_n = scale * gscale[n] (gscale = NULL: scale alone; a device vector of R / T values: the gradient autograd
+ * hands the loss).  z fp32 [R, P]; f [R, P] fp32 (MAPDIT_REPA_F_F32) or IEEE fp16 (MAPDIT_REPA_F_F16, the features file's format in
+ * either engine precision); loss or dz may be NULL.  One launch, fp32 arithmetic: a workgroup per sample, a wave per row (each lane
+ * walks its columns in order, the 64 partial sums meet in a fixed butterfly), each wave adds its rows' cosines in row order, the four
+ * wave sums are added in order.  Below 1e-12 the normalisation is the constant 1e12 (F.normalize's): an all-zero row of z or f adds 0
+ * to the loss and its dz is finite.  R a multiple of T, any T >= 1; P a multiple of 8. */
+int mapdit_repa_cos_loss(const float* z, const void* f, int f_kind, const float* gscale, float scale, float* loss, float* dz, long R, int T,
+                         int P, void* stream);
+/* out[i] = round(out[i] + alpha * dh[i]): out 16-bit (a gradient stream), dh fp32.  The sum is formed in fp64 (the product of two fp32
+ * values is exact there) and rounded ONCE to the 16-bit format, to nearest even: exact where the sum is representable.  n a multiple of
+ * 8.  _f32: out fp32, one fma per element; n a multiple of 4.  Behind mapdit_engine_set_hidden_grad. */
+int mapdit_repa_stream_add(uint16_t* out, const float* dh, float alpha, long n, void* stream);
+int mapdit_repa_stream_add_f32(float* out, const float* dh, float alpha, long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * IEEE fp16 operand forms (see "16-bit operand format" at the top): identical signatures and semantics, every uint16_t tensor
@@ -1308,6 +1363,12 @@ int mapdit_vit_gelu_f16(const uint16_t* in, uint16_t* out, long n, void* stream)
 int mapdit_vit_residual_f16(float* x, const void* y, int y_kind, const float* gamma, long M, int D, void* stream);
 int mapdit_vit_features_f16(const mapdit_vit_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
                             int W, float* feat, void* workspace, size_t ws_bytes, void* stream);
+int mapdit_vit_tokens_f16(const mapdit_vit_config_t* cfg, const void* const* weights_host, const void* images, int img_kind, int N, int H,
+                          int W, void* tokens, int out_kind, void* workspace, size_t ws_bytes, void* stream);
+int mapdit_repa_bias_silu_fwd_f16(float* pre, const float* bias, uint16_t* act, long M, int C, void* stream);
+int mapdit_repa_bias_silu_bwd_f16(const float* dact, const float* pre, uint16_t* dpre16, float* dbias, float* part, float alpha, float bias_scale,
+                                  int accumulate, long M, int C, void* stream);
+int mapdit_repa_stream_add_f16(uint16_t* out, const float* dh, float alpha, long n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,10 @@ struct mapdit_engine {
     // and MPScale-reference sums the fused kernels cannot skip land in the first floats of dcd, which an input-only backward does not use)
     float* ig_dx = nullptr;
     bool ig_only = false;
+    // mapdit_engine_set_hidden_grad, one-shot: the backward adds hg_dh (d loss / d X[2 hg_block + 2], unscaled) to the gradient stream
+    // between the two passes of block hg_block + 1 (mapdit.h)
+    const float* hg_dh = nullptr;
+    int hg_block = -1;
     bool have_saved = false;
     // mapdit_engine_set_grad_accumulate, one-shot: every parameter gradient the next backward writes is g <- g + new, `new` being the fp32
     // value a fresh backward stores (the accumulate forms of the writers: same arithmetic, one more fp32 addition; fixed order, no atomics).
@@ -1121,6 +1125,29 @@ extern "C" int mapdit_engine_set_input_grad(mapdit_engine_t* e, float* dx, int i
     return MAPDIT_OK;
 }
 
+// One-shot (consumed in the stage of block `block` + 1 of the next backward, dropped by the next forward): dh = d loss / d (block's output),
+// injected into the gradient stream there (mapdit.h).  Cannot change between the stages of a staged backward.
+extern "C" int mapdit_engine_set_hidden_grad(mapdit_engine_t* e, int block, const float* dh) {
+    MD_CHECK(e, "engine_set_hidden_grad: null argument");
+    MD_CHECK(e->train, "engine_set_hidden_grad: a hidden-state gradient needs a training engine (the inference engine keeps no activations)");
+    MD_CHECK(e->next_stage == 0, "engine_set_hidden_grad: the hidden-state gradient cannot change while a staged backward is in progress");
+    if (!dh) {
+        e->hg_dh = nullptr;
+        e->hg_block = -1;
+        return MAPDIT_OK;
+    }
+    MD_CHECK(e->cfg.precision != MAPDIT_PREC_BF16X3, "engine_set_hidden_grad: the hidden-state gradient is not built for the bf16x3 engine");
+    MD_CHECK(!e->ln, "engine_set_hidden_grad: the hidden-state gradient is not built for the LayerNorm form (no-layernorm off)");
+    MD_CHECK(block >= 0 && block <= e->cfg.depth - 2,
+             "engine_set_hidden_grad: hidden block %d outside 0 .. depth - 2 = %d (the last block's output feeds the final layer alone)", block,
+             e->cfg.depth - 2);
+    MD_CHECK(!e->ig_only, "engine_set_hidden_grad: a hidden-state gradient cannot enter an input-only backward");
+    MD_CHECK(!((uintptr_t)dh & 15), "engine_set_hidden_grad: the hidden-state gradient must be 16-byte aligned");
+    e->hg_dh = dh;
+    e->hg_block = block;
+    return MAPDIT_OK;
+}
+
 // One-shot (consumed by the backward that reaches stage L+1, dropped by the next forward): that backward ADDS every parameter gradient to
 // what the bound gradient buffers hold (mapdit.h).  Like the input-gradient request it cannot change between the stages of a staged backward.
 // Not built where the gradient buffers do not hold finished gradients when a backward returns (sharded weight passes: raw sums that wait
@@ -1260,6 +1287,8 @@ static int forward_precise(mapdit_engine* e, const float* x, const int64_t* t, c
     e->have_saved = save != 0;
     e->ig_dx = nullptr;                   // an unconsumed input-gradient request belonged to the previous forward's backward
     e->ig_only = false;
+    e->hg_dh = nullptr;                   // (so did a hidden-state gradient)
+    e->hg_block = -1;
     return MAPDIT_OK;
 }
 
@@ -1600,6 +1629,8 @@ extern "C" int mapdit_engine_forward(mapdit_engine_t* e, const float* x, const i
     e->have_saved = save != 0;
     e->ig_dx = nullptr;                   // an unconsumed input-gradient request belonged to the previous forward's backward
     e->ig_only = false;
+    e->hg_dh = nullptr;                   // (so did a hidden-state gradient)
+    e->hg_block = -1;
     e->gacc = false;                      // (so did an unconsumed accumulate request)
     return MAPDIT_OK;
 }
@@ -1689,6 +1720,7 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
         return e->dcd + (idx == MAPDIT_P_MS_REF ? 0 : idx == MAPDIT_P_SS_REF ? NSCALE : 2 * NSCALE);
     };
     const int acc = grad_acc(e);          // accumulation (mapdit_engine_set_grad_accumulate): every writer of a bound gradient adds
+    MD_CHECK(!(io && e->hg_dh), "engine_backward: a hidden-state gradient (mapdit_engine_set_hidden_grad) cannot enter an input-only backward");
     MD_CHECK(!acc || e->shard_world <= 1, "engine_backward: gradient accumulate is not built for sharded weight passes");
     if (stage_from == 0) {
     e->dw_pending.clear();
@@ -1773,6 +1805,16 @@ extern "C" int mapdit_engine_backward_stages(mapdit_engine_t* e, const float* do
             const RotBwd rb{mod + e->o_shm, mod + e->o_scm, dmod + e->o_shm, dmod + e->o_scm, e->params[pidx_block(i, MAPDIT_B_GAIN_MLP)]};
             TRY(dx_resid_mod_bwd(e, M, Hm, e->dh, Hm, W(pidx_block(i, MAPDIT_B_FC1)), a, G(pidx_block(i, MAPDIT_B_GAIN_MLP)), st,
                                  e->rot ? &rb : nullptr));
+        }
+        // mapdit_engine_set_hidden_grad: d loss / d X[2i] enters here.  The attention-branch pass below forms dx' = ca * dxo + (modulate
+        // backward) at x' = X[2i] and derives block i-1's MLP-branch gradients from dx' in the same kernel: dx' + dh = ca * (dxo + dh / ca)
+        // + ..., and dxo = DXb is what the MLP-branch pass above has just written (on the loss-scaled stream: dh * lscale / ca).
+        if (e->hg_dh && i == e->hg_block + 1) {
+            const float alpha = e->lscale / e->ca;
+            if (e->dx16) TRY(DT_FN(e, mapdit_repa_stream_add)(e->DXb16, e->hg_dh, alpha, (long)M * D, st));
+            else TRY(mapdit_repa_stream_add_f32(e->DXb, e->hg_dh, alpha, (long)M * D, st));
+            e->hg_dh = nullptr;           // one-shot: consumed
+            e->hg_block = -1;
         }
         // attention branch: dy2 holds the grad of the attention branch output y_i (its own buffer: dy may still wait for the grouped launch)
         TRY(gemm16(e, MAPDIT_NN, M, D, D, e->dy2, D, W(pidx_block(i, MAPDIT_B_PROJ)), D, epi_bf16(e->dO, D), st));

@@ -447,18 +447,19 @@ extern "C" size_t mapdit_vit_workspace_bytes(const mapdit_vit_config_t* cfg, int
 }
 #endif
 
-extern "C" int MD_SYM(vit_features)(const mapdit_vit_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
-                                    float* feat, void* workspace, size_t ws_bytes, void* stream) {
-    VitPlan pl;
+// The walk both outputs share: everything up to the residual stream x fp32 [N * T, dim] in front of the final LayerNorm (*xout).
+static int MD_TU(vit_walk)(const char* who, const mapdit_vit_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
+                           const void* out, void* workspace, size_t ws_bytes, void* stream, VitPlan* plan, float** xout) {
+    VitPlan& pl = *plan;
     MD_TRY(vit_plan(cfg, N, &pl));
-    MD_CHECK(wt && images && feat && workspace, "vit_features: null argument");
-    MD_CHECK(img_kind == MAPDIT_VIT_IMG_U8_NHWC || img_kind == MAPDIT_VIT_IMG_F32_NCHW, "vit_features: bad img_kind %d", img_kind);
-    MD_CHECK(H >= 8 && W >= 8, "vit_features: images of %d x %d (8 x 8 at the least)", H, W);
-    MD_CHECK(ws_bytes >= pl.total, "vit_features: workspace of %zu bytes, %zu needed (mapdit_vit_workspace_bytes)", ws_bytes, pl.total);
-    MD_CHECK(!((uintptr_t)workspace & 255), "vit_features: the workspace must be 256-byte aligned");
-    MD_CHECK(VIT_ALIGNED16(feat), "vit_features: feat must be 16-byte aligned");
+    MD_CHECK(wt && images && out && workspace, "%s: null argument", who);
+    MD_CHECK(img_kind == MAPDIT_VIT_IMG_U8_NHWC || img_kind == MAPDIT_VIT_IMG_F32_NCHW, "%s: bad img_kind %d", who, img_kind);
+    MD_CHECK(H >= 8 && W >= 8, "%s: images of %d x %d (8 x 8 at the least)", who, H, W);
+    MD_CHECK(ws_bytes >= pl.total, "%s: workspace of %zu bytes, %zu needed (mapdit_vit_workspace_bytes)", who, ws_bytes, pl.total);
+    MD_CHECK(!((uintptr_t)workspace & 255), "%s: the workspace must be 256-byte aligned", who);
+    MD_CHECK(VIT_ALIGNED16(out), "%s: the output must be 16-byte aligned", who);
     const int nw = MAPDIT_VIT_W_GLOBAL + cfg->depth * MAPDIT_VIT_W_BLOCK;
-    for (int i = 0; i < nw; ++i) MD_CHECK(wt[i] && VIT_ALIGNED16(wt[i]), "vit_features: weight slot %d is null or not 16-byte aligned", i);
+    for (int i = 0; i < nw; ++i) MD_CHECK(wt[i] && VIT_ALIGNED16(wt[i]), "%s: weight slot %d is null or not 16-byte aligned", who, i);
     char* ws = (char*)workspace;
     uint16_t* rows = (uint16_t*)(ws + pl.off_rows);
     float* x = (float*)(ws + pl.off_x);
@@ -488,7 +489,28 @@ extern "C" int MD_SYM(vit_features)(const mapdit_vit_config_t* cfg, const void* 
         MD_TRY(MD_SYM(vit_linear)(fb, (const uint16_t*)w[MAPDIT_VIT_B_FC2], (const float*)w[MAPDIT_VIT_B_FC2_BIAS], y, k32, M, F, D, stream));
         MD_TRY(MD_SYM(vit_residual)(x, y, k32, (const float*)w[MAPDIT_VIT_B_LS2], M, D, stream));
     }
+    *xout = x;
+    return MAPDIT_OK;
+}
+
+extern "C" int MD_SYM(vit_features)(const mapdit_vit_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
+                                    float* feat, void* workspace, size_t ws_bytes, void* stream) {
+    VitPlan pl;
+    float* x = nullptr;
+    MD_TRY(MD_TU(vit_walk)("vit_features", cfg, wt, images, img_kind, N, H, W, feat, workspace, ws_bytes, stream, &pl, &x));
     // the final LayerNorm on the CLS rows alone (LayerNorm is per row): row n * T of x -> feat[n]
-    return MD_SYM(vit_layernorm)(x, (long)T * D, (const float*)wt[MAPDIT_VIT_W_NORM], (const float*)wt[MAPDIT_VIT_W_NORM_BIAS], cfg->ln_eps, feat, k32, N, D,
-                                 stream);
+    return MD_SYM(vit_layernorm)(x, (long)pl.T * cfg->dim, (const float*)wt[MAPDIT_VIT_W_NORM], (const float*)wt[MAPDIT_VIT_W_NORM_BIAS], cfg->ln_eps, feat,
+                                 MAPDIT_VIT_OUT_F32, N, cfg->dim, stream);
+}
+
+// The same walk with the final LayerNorm on EVERY row: tokens [N, T, dim], row 0 of a sample its CLS token (the bits of vit_features
+// with an fp32 output: the LayerNorm is one wave per row and knows nothing of the other rows), rows 1 + p the patches in grid order.
+extern "C" int MD_SYM(vit_tokens)(const mapdit_vit_config_t* cfg, const void* const* wt, const void* images, int img_kind, int N, int H, int W,
+                                  void* tokens, int out_kind, void* workspace, size_t ws_bytes, void* stream) {
+    MD_CHECK(out_kind == MAPDIT_VIT_OUT_F32 || out_kind == MAPDIT_VIT_OUT_16, "vit_tokens: bad out_kind %d", out_kind);
+    VitPlan pl;
+    float* x = nullptr;
+    MD_TRY(MD_TU(vit_walk)("vit_tokens", cfg, wt, images, img_kind, N, H, W, tokens, workspace, ws_bytes, stream, &pl, &x));
+    return MD_SYM(vit_layernorm)(x, cfg->dim, (const float*)wt[MAPDIT_VIT_W_NORM], (const float*)wt[MAPDIT_VIT_W_NORM_BIAS], cfg->ln_eps, tokens, out_kind,
+                                 pl.M, cfg->dim, stream);
 }

@@ -201,20 +201,24 @@ class DinoV2Features:
             raise ValueError(f"DINOv2 features refused: {lib.last_error().decode()}")
         return need
 
-    @torch.no_grad()
-    def features(self, x):
+    def _run(self, x, what, out16=False):
+        """The walk over chunks of max_batch images: ``what`` = "features" (CLS rows, fp32 [N, D]) or "tokens" ([N, T, D])."""
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise NotImplementedError("DinoV2Features.features runs on the GPU only (HIP kernels, no CPU path): pass a CUDA tensor")
+            raise NotImplementedError(f"DinoV2Features.{what} runs on the GPU only (HIP kernels, no CPU path): pass a CUDA tensor")
         u8 = x.dtype == torch.uint8
         if x.dim() != 4 or x.shape[3 if u8 else 1] != 3:
-            raise ValueError(f"DINOv2 features: x has shape {tuple(x.shape)} ({x.dtype}), expected uint8 [N, H, W, 3] or float [N, 3, H, W]")
+            raise ValueError(f"DINOv2 {what}: x has shape {tuple(x.shape)} ({x.dtype}), expected uint8 [N, H, W, 3] or float [N, 3, H, W]")
         x = x.detach().to(self.device).contiguous() if u8 else x.detach().to(self.device, torch.float32).contiguous()
         N, H, W = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
         if H < 8 or W < 8:
-            raise ValueError(f"DINOv2 features: images of {H} x {W} (8 x 8 at the least)")
-        feat = torch.empty(N, self.dim, dtype=torch.float32, device=self.device)
+            raise ValueError(f"DINOv2 {what}: images of {H} x {W} (8 x 8 at the least)")
+        if what == "tokens":
+            T = 1 + (self.image_size // PATCH) ** 2
+            out = torch.empty(N, T, self.dim, dtype=PRECISIONS[self.precision] if out16 else torch.float32, device=self.device)
+        else:
+            out = torch.empty(N, self.dim, dtype=torch.float32, device=self.device)
         if N == 0:
-            return feat
+            return out
         chunk = min(N, self.max_batch)
         need = self.workspace_bytes(chunk)
         lib = L.lib()
@@ -223,15 +227,26 @@ class DinoV2Features:
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        fn = lib.vit_features_f16 if self.precision == "f16" else lib.vit_features
+        fn = getattr(lib, "vit_" + what + ("_f16" if self.precision == "f16" else ""))
+        extra = (L.VIT_OUT_16 if out16 else L.VIT_OUT_F32,) if what == "tokens" else ()
         kind = L.VIT_IMG_U8_NHWC if u8 else L.VIT_IMG_F32_NCHW
         with torch.cuda.device(self.device):
             stream = L.cur_stream()
             for i in range(0, N, chunk):
                 n = min(chunk, N - i)
-                fn(C.byref(self._cfg), self._table, x[i:i + n].data_ptr(), kind, n, H, W, feat[i:i + n].data_ptr(), self._ws.data_ptr(),
+                fn(C.byref(self._cfg), self._table, x[i:i + n].data_ptr(), kind, n, H, W, out[i:i + n].data_ptr(), *extra, self._ws.data_ptr(),
                    self._ws.numel(), stream)
-        return feat
+        return out
+
+    @torch.no_grad()
+    def features(self, x):
+        return self._run(x, "features")
+
+    @torch.no_grad()
+    def tokens(self, x, out16=False):
+        """Every token after the final LayerNorm (``mapdit_vit_tokens``): [N, 1 + g * g, D], g = image_size / 14; row 0 the CLS token (fp32:
+        the bits of ``features``), rows 1 + p the patches in row-major grid order.  ``out16``: in the network's 16-bit format."""
+        return self._run(x, "tokens", out16)
 
 
 # ---- files --------------------------------------------------------------------------------------------------------------------------
@@ -327,6 +342,43 @@ def fd_dinov2(mu1, sigma1, mu2, sigma2) -> float:
     return FID.frechet_distance(mu1, sigma1, mu2, sigma2)
 
 
+def tokens_flip_flags(num, flip_seed):
+    """Which images the ``tokens`` subcommand mirrors: none, or those ``encode_data --flip --seed S`` mirrored."""
+    if flip_seed is None:
+        return np.zeros(num, dtype=bool)
+    from .encode_data import flip_flags
+    return flip_flags(num, flip_seed).numpy().astype(bool)
+
+
+def write_tokens(args):
+    """``tokens``: fp16 [num, G * G, dim] through a memory map, a batch at a time (ImageNet at G = 16, ViT-B: 503 GB)."""
+    if args.grid < 1 or args.grid > 128:
+        raise ValueError(f"--grid {args.grid}: the token grid must lie in 1 .. 128")
+    if args.batch_size < 1:
+        raise ValueError(f"--batch-size {args.batch_size} must be at least 1")
+    if not str(args.output).endswith(".npy"):
+        raise ValueError(f"--output {args.output!r}: the tokens are written as one .npy (train.py --repa-features memory-maps it)")
+    if args.dinov2_weights is None:
+        raise ValueError("tokens needs --dinov2-weights")
+    images = FID.load_images(args.images)                      # (a bad array ends the run before the weights are read)
+    num = len(images)
+    flips = tokens_flip_flags(num, args.flip_seed)
+    net = DinoV2Features.from_file(args.dinov2_weights, "cuda", args.precision, min(args.batch_size, 32), image_size=PATCH * args.grid)
+    out = np.lib.format.open_memmap(args.output, mode="w+", dtype=np.float16, shape=(num, args.grid * args.grid, net.dim))
+    for i in range(0, num, args.batch_size):
+        batch = np.ascontiguousarray(images[i:i + args.batch_size])
+        fl = flips[i:i + args.batch_size]
+        if fl.any():
+            batch = batch.copy()
+            batch[fl] = batch[fl][:, :, ::-1]
+        tok = net.tokens(torch.from_numpy(batch).to("cuda"))
+        out[i:i + len(batch)] = tok[:, 1:].to(torch.float16).cpu().numpy()
+    out.flush()
+    del out
+    print(f"{args.output}: fp16 [{num}, {args.grid * args.grid}, {net.dim}] patch tokens" + (f", flips of seed {args.flip_seed}" if args.flip_seed is not None else ""))
+    return args.output
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m mapdit_amd.dinov2")
@@ -336,10 +388,15 @@ def build_parser():
     for q in (s, f):
         q.add_argument("--images", required=True, help=".npz / .npy of uint8 [N, H, W, 3]")
         q.add_argument("--output", required=True, help="an existing .npz keeps its other arrays (FID's mu, sigma, pool_3)")
+    t = sub.add_parser("tokens", help="the patch tokens of an image array as an fp16 .npy [num, G * G, dim]: REPA's targets (train.py --repa-features)")
+    t.add_argument("--images", required=True, help=".npz / .npy of uint8 [N, H, W, 3]")
+    t.add_argument("--output", required=True, help="the .npy to write (fp16 [num, G * G, dim], CLS dropped)")
+    t.add_argument("--grid", type=int, required=True, help="G: the images are resized to 14 G pixels; G * G must equal the DiT's token count")
+    t.add_argument("--flip-seed", type=int, default=None, help="mirror image i iff encode_data.flip_flags(num, S)[i] (the latents of encode_data --flip --seed S)")
     c = sub.add_parser("compare", help="FD-DINOv2 of two statistics or features files or image arrays")
     c.add_argument("a", help="the reference (real) side")
     c.add_argument("b", help="the samples")
-    for q in (s, f, c):
+    for q in (s, f, c, t):
         q.add_argument("--dinov2-weights", default=None, help="dinov2_vitl14_pretrain weights (.safetensors, or a torch state dict)")
         q.add_argument("--batch-size", type=int, default=64)
         q.add_argument("--precision", choices=sorted(PRECISIONS), default="f16")
@@ -358,6 +415,8 @@ def main(argv=None):
             net = DinoV2Features.from_file(args.dinov2_weights, "cuda", args.precision, min(args.batch_size, 32))
         return net
 
+    if args.cmd == "tokens":
+        return write_tokens(args)
     if args.cmd == "stats":
         images = FID.load_images(args.images)                  # (a bad array ends the run before the weights are read)
         st = stats_of_images(images, network(), args.batch_size)

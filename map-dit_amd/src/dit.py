@@ -251,18 +251,32 @@ class _DiTFunction(torch.autograd.Function):
         ctx.model, ctx.rt, ctx.generation = model, rt, rt.generation
         ctx.x_shape = x.shape
         ctx.params_need_grad = rt.params_need_grad
-        return out
+        ctx.tap = model.hidden_tap
+        if ctx.tap is None:
+            return out
+        # second output: a copy of the fp32 residual stream after block `tap` (the engine's saved checkpoint).  A gradient autograd leaves
+        # None for it (the output went unused) means no request: that backward issues the launches of a backward without a tap.
+        ctx.set_materialize_grads(False)
+        hidden = model._peek("xout", ctx.tap).view(x.shape[0], -1, model.hidden_size)
+        return out, hidden
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, dh=None):
         model, rt = ctx.model, ctx.rt
         # The engine holds the activations of exactly one forward.  forward(A); forward(B); lossA.backward() would silently
         # differentiate A's loss through B's activations: refuse it (so does a runtime rebuilt for a larger batch in between).
         if ctx.generation != rt.generation or not any(r is rt for r in model._rt.values()):
             raise L.MapditError("backward through a stale forward: the engine keeps the saved activations of the most recent "
                                 "training forward only (one outstanding forward per model; run backward before the next forward)")
+        if dout is None:                  # (a tapped forward whose logits went unused: the loss reads the hidden state alone)
+            dout = torch.zeros(ctx.x_shape[0], 2 * model.in_channels, model.input_size, model.input_size, device=dh.device)
         dout = dout.contiguous().float()
         dx = torch.empty(ctx.x_shape, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        if dh is not None:
+            if dx is not None and not ctx.params_need_grad:
+                raise L.MapditError("a gradient at the hidden tap (model.hidden_tap) cannot enter an input-only backward (every parameter is "
+                                    "frozen): the hidden-state gradient is built for the training backward")
+            dh = dh.contiguous().float()
         if dx is not None and not ctx.params_need_grad:
             # input-only: frozen weights, dL/dx alone - no parameter gradient is computed, p.grad and the flat buffer stay as they are
             rt.lib.engine_set_input_grad(rt.handle, dx.data_ptr(), 1)      # one-shot; a request left behind by a failed backward dies with the next forward
@@ -281,6 +295,8 @@ class _DiTFunction(torch.autograd.Function):
             rt.lib.engine_set_input_grad(rt.handle, dx.data_ptr(), 0)       # one-shot: consumed by the last stage below
         if in_engine:
             rt.lib.engine_set_grad_accumulate(rt.handle, 1)                 # one-shot too: consumed by the last stage, dropped by a forward
+        if dh is not None:
+            rt.lib.engine_set_hidden_grad(rt.handle, ctx.tap, dh.data_ptr())   # one-shot: read in the stage of block tap + 1 (dh lives until then)
         hook = getattr(model, "_stage_hook", None)
         if hook is None:
             rt.lib.engine_backward(rt.handle, dout.data_ptr(), L.cur_stream())
@@ -392,6 +408,11 @@ class DiT(nn.Module):
         # row and block and re-runs the block's fc1 GEMM / the block's forward at the start of its backward stage (mapdit_config_t.recompute);
         # gradients are bit-identical to "none".  Inference runtimes are not affected.
         self._activation_recompute = "none"
+        # Opt-in (not part of the state dict): k = a training forward also leaves model.tapped_hidden, an fp32 [N, T, D] copy of block k's
+        # output, and a gradient with respect to it joins the backward (mapdit_engine_set_hidden_grad; repa.py).  None (the default): not
+        # one launch differs.
+        self._hidden_tap = None
+        self.tapped_hidden = None
         self._pflat = None            # flat fp32 storage behind every parameter (views)
         self._gflat = None            # flat gradient buffer, p.grad are views of it
         self._gviews = None
@@ -536,6 +557,28 @@ class DiT(nn.Module):
             raise ValueError(f"activation_recompute must be one of {list(L.RECOMPUTE)}, got {value!r}")
         self._activation_recompute = value
 
+    # The hidden tap: None, or the block (0 .. depth - 2) whose output a training forward exposes as model.tapped_hidden.
+    @property
+    def hidden_tap(self):
+        return self.__dict__.get("_hidden_tap", None)          # (objects pickled before the attribute existed)
+
+    @hidden_tap.setter
+    def hidden_tap(self, value):
+        if value is not None:
+            if isinstance(value, bool) or not isinstance(value, int):
+                raise ValueError(f"hidden_tap must be None or a block index, got {value!r}")
+            if not 0 <= value <= self.depth - 2:
+                raise ValueError(f"hidden_tap={value} outside 0 .. depth - 2 = {self.depth - 2}: the last block's output feeds the final layer "
+                                 "alone (the engine injects a hidden-state gradient in front of the next block)")
+        self._hidden_tap = value
+
+    def _check_hidden_tap(self):
+        """The engine's refusals (mapdit_engine_set_hidden_grad), before any device work."""
+        if getattr(self, "gemm_precision", "f16") == "bf16x3":
+            raise ValueError("hidden_tap is not built for gemm_precision 'bf16x3' (the parity engine has a backward of its own)")
+        if not self.no_layernorm:
+            raise ValueError("hidden_tap is not built for the LayerNorm form (no_layernorm=False)")
+
     def effective_loss_scale(self) -> float:
         """The loss scale the most recent fp16 backward ran with (the automatic choice resolved); 1.0 before any backward."""
         rt = self._rt.get(("f16", True))
@@ -612,6 +655,9 @@ class DiT(nn.Module):
         if not need_grad and getattr(self, "_shard_stale", False):
             raise L.MapditError("sharded weight passes (--grad-comm zero1w): this rank holds stale master rows of the other ranks after an "
                                 "optimiser step - call reducer.gather_state() before an inference forward, a checkpoint or an EMA snapshot")
+        self.tapped_hidden = None
+        if need_grad and self.hidden_tap is not None:
+            self._check_hidden_tap()
         rt = self._runtime(x.shape[0], train=need_grad)
         with torch.cuda.device(x.device):
             if self.training:
@@ -630,7 +676,10 @@ class DiT(nn.Module):
                     rt.weights_key = key
             if need_grad:
                 rt.params_need_grad = params_need_grad       # (False: x alone requires grad - the backward will be input-only)
-                return _DiTFunction.apply(self, rt, x, t, y, self._anchor())
+                if self.hidden_tap is None:
+                    return _DiTFunction.apply(self, rt, x, t, y, self._anchor())
+                out, self.tapped_hidden = _DiTFunction.apply(self, rt, x, t, y, self._anchor())
+                return out
             out = torch.empty(x.shape[0], 2 * self.in_channels, self.input_size, self.input_size, device=x.device)
             rt.lib.engine_forward(rt.handle, x.data_ptr(), t.data_ptr(), y.data_ptr(), x.shape[0], 0, out.data_ptr(),
                                   L.cur_stream())
@@ -676,11 +725,12 @@ class DiT(nn.Module):
         new.gemm_precision, new._loss_scale = self.gemm_precision, self.loss_scale
         new.input_gradients = getattr(self, "input_gradients", False)
         new.activation_recompute = self.activation_recompute
+        new.hidden_tap = self.hidden_tap
         return new
 
     def __getstate__(self):
         st = super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__.copy()
         st = dict(st)
-        for k in ("_rt", "_gflat", "_gviews", "_anchor_t", "_buffer_grad_scratch"):
+        for k in ("_rt", "_gflat", "_gviews", "_anchor_t", "_buffer_grad_scratch", "tapped_hidden"):
             st[k] = {} if k == "_rt" else None
         return st

@@ -21,7 +21,10 @@ label drops and --synthetic batch come from one launch of a counter-based genera
 bits for any world size and --grad-accum-steps, and --resume PATH: continue a --step-rng counter run from one of its checkpoints, which
 hold the keys "ema" (the fp32 EMA copies) and "train_state" (step, log accumulators, fp16 guard) besides the reference's; with the
 device loader or --synthetic the continued run ends with the bits of the run that was never stopped.  A default (--step-rng torch) run
-writes the reference's checkpoint, key for key, and cannot be continued: its generators' states are in no checkpoint.
+writes the reference's checkpoint, key for key, and cannot be continued: its generators' states are in no checkpoint, and
+--repa-features FILE | synthetic:P: representation alignment (REPA, repa.py) - a projector on the hidden state after --repa-depth blocks is
+pulled toward the DINOv2 patch tokens of the clean images (`python -m mapdit_amd.dinov2 tokens`); the loss gains --repa-coeff times the
+alignment term, the log line `, repa: ...`, the checkpoints "repa_head" and "repa_opt".  Single process, host loader or --synthetic.
 """
 import argparse
 import contextlib
@@ -40,6 +43,7 @@ from .diffusion.timestep_sampler import create_named_schedule_sampler
 from .flow import create_flow
 from ._lib import MapditError
 from .optim import FusedAdamEMA, create_lr_lambda
+from .repa import RepaHead
 from .src.models import DIT_MODELS
 from .step_rng import StepRNG, first_slot
 
@@ -94,6 +98,87 @@ class LatentDataset(torch.utils.data.Dataset):
     def __getitem__(self, i):
         f = self.means[i] + torch.randn_like(self.means[i]) * self.stds[i]
         return (f - self.m) / self.s, self.labels[i]
+
+
+class RepaLatentDataset(LatentDataset):
+    """--repa-features FILE with --data-path: a sample is (x, y, f), f fp16 [tokens, P] row i of the memory-mapped file (the row order of
+    the latents: `dinov2 tokens` over the images `encode_data` read, with --flip-seed where that ran with --flip)."""
+
+    def __init__(self, path, features_path):
+        super().__init__(path)
+        self.features_path, self._feats = features_path, None
+
+    def __getitem__(self, i):
+        import numpy as np
+        if self._feats is None:                  # opened in the process that reads it (a loader worker)
+            self._feats = np.load(self.features_path, mmap_mode="r")
+        x, y = super().__getitem__(i)
+        return x, y, torch.from_numpy(np.array(self._feats[i]))
+
+
+def parse_repa_features(spec):
+    """--repa-features: "synthetic:P" -> ("synthetic", P), anything else -> ("file", path).  A bad P is a ValueError naming the flag."""
+    if spec.startswith("synthetic:"):
+        try:
+            P = int(spec[len("synthetic:"):])
+        except ValueError:
+            P = 0
+        if P < 8 or P % 8:
+            raise ValueError(f"--repa-features {spec}: the feature width after 'synthetic:' must be a positive multiple of 8")
+        return "synthetic", P
+    return "file", spec
+
+
+def check_repa_features_file(path, num_rows, tokens):
+    """The features file against the data set, from its header alone (the file is memory-mapped): fp16 [num_rows, tokens, P], P a
+    multiple of 8.  Returns P; a misfit is a ValueError naming --repa-features and what does not fit."""
+    import numpy as np
+    if not os.path.isfile(path):
+        raise ValueError(f"--repa-features {path}: no such file (write one with `python -m mapdit_amd.dinov2 tokens`, or pass synthetic:P with --synthetic)")
+    try:
+        a = np.load(path, mmap_mode="r")
+    except Exception as e:
+        raise ValueError(f"--repa-features {path}: not a .npy array ({e})") from None
+    if a.dtype != np.float16:
+        raise ValueError(f"--repa-features {path}: dtype {a.dtype}, expected float16 (what `dinov2 tokens` writes)")
+    if a.ndim != 3:
+        raise ValueError(f"--repa-features {path}: shape {tuple(a.shape)}, expected [samples, tokens, feature width]")
+    if a.shape[0] != num_rows:
+        raise ValueError(f"--repa-features {path}: {a.shape[0]} rows, the data set has {num_rows} samples (one row per latent, in the latents' order)")
+    if a.shape[1] != tokens:
+        raise ValueError(f"--repa-features {path}: {a.shape[1]} tokens per sample, the model has (input_size / patch)^2 = {tokens} "
+                         f"(`dinov2 tokens --grid {math.isqrt(tokens)}`)")
+    if a.shape[2] < 8 or a.shape[2] % 8:
+        raise ValueError(f"--repa-features {path}: feature width {a.shape[2]} must be a positive multiple of 8")
+    return int(a.shape[2])
+
+
+def check_repa_args(args, world):
+    """The refusals of --repa-features that need no device: each a ValueError naming the flag that does not fit."""
+    if args.repa_features is None:
+        return None
+    kind, what = parse_repa_features(args.repa_features)
+    if args.data_loader == "device":
+        raise ValueError("--repa-features is not built for --data-loader device (the device-resident loader gathers latents alone); use the host loader")
+    if world > 1:
+        raise ValueError(f"--repa-features is single-process: a world size of {world} needs an all-reduce of the head's gradients, which is not built")
+    if args.precision == "bf16x3":
+        raise ValueError("--repa-features is not built for --precision bf16x3 (the hidden-state gradient is a bf16 / f16 engine feature)")
+    if not args.use_no_layernorm:
+        raise ValueError("--repa-features is not built for --no-use-no-layernorm (the LayerNorm form)")
+    if kind == "synthetic" and not args.synthetic:
+        raise ValueError(f"--repa-features {args.repa_features} draws N(0,1) features for --synthetic; a data set needs a features file")
+    if kind == "file" and args.synthetic:
+        raise ValueError(f"--repa-features {args.repa_features}: --synthetic has no images to have features of; pass synthetic:P")
+    if not args.repa_coeff >= 0 or not math.isfinite(args.repa_coeff):
+        raise ValueError(f"--repa-coeff {args.repa_coeff} must be finite and >= 0")
+    if args.repa_hidden < 8 or args.repa_hidden % 8:
+        raise ValueError(f"--repa-hidden {args.repa_hidden} must be a positive multiple of 8")
+    if not args.repa_lr > 0:
+        raise ValueError(f"--repa-lr {args.repa_lr} must be positive")
+    if args.repa_depth is not None and args.repa_depth < 1:
+        raise ValueError(f"--repa-depth {args.repa_depth} must be at least 1")
+    return kind, what
 
 
 def build_parser():
@@ -169,6 +254,14 @@ def build_parser():
                         "--grad-accum-steps, nothing to carry over a --resume.  With --data-loader device or --synthetic the whole step "
                         "is then a function of (--seed, step); with --data-loader host the loader's order is not.  Checkpoints of a "
                         "counter run gain the keys --resume needs; a torch run writes the reference's two)")
+    p.add_argument("--repa-features", type=str, default=None, metavar="FILE | synthetic:P",
+                   help="representation alignment (REPA): FILE = fp16 [samples, tokens, P] .npy of DINOv2 patch tokens in the latents' order "
+                        "(`python -m mapdit_amd.dinov2 tokens`), memory-mapped; synthetic:P = N(0,1) features for --synthetic.  Single "
+                        "process, host loader, f16 / bf16")
+    p.add_argument("--repa-coeff", type=float, default=0.5, help="weight of the alignment term in the loss")
+    p.add_argument("--repa-depth", type=int, default=None, help="align the hidden state after this many blocks (default: 8 for depth >= 24, else 4)")
+    p.add_argument("--repa-hidden", type=int, default=2048, help="width of the projector's two inner layers")
+    p.add_argument("--repa-lr", type=float, default=1e-4, help="learning rate of the projector's Adam (the run's warm-up and decay apply)")
     p.add_argument("--resume", type=str, default=None, metavar="PATH",
                    help="continue a --step-rng counter run: PATH is one of its checkpoints/NNNNNNN.pt or its experiment directory (the "
                         "latest checkpoint).  "
@@ -291,6 +384,11 @@ def main(argv=None):
         raise NotImplementedError("--no-use-no-layernorm (the LayerNorm form) is built for the AdaLN modulation, not with --use-rotation-modulation")
     if args.data_loader == "device" and args.synthetic:
         raise ValueError("--data-loader device draws from the data set under --data-path; --synthetic has none")
+    repa = check_repa_args(args, int(os.environ.get("WORLD_SIZE", "1")))      # (None without --repa-features: nothing below changes)
+    if repa is not None and resume is not None:
+        for key in ("repa_head", "repa_opt"):
+            if key not in resume:
+                raise ValueError(f"--resume {resume_path}: the checkpoint has no {key!r} key, the run trains with --repa-features {args.repa_features}")
     flow_mode = args.objective == "flow"
     if not flow_mode and (args.flow_shift != 1.0 or args.flow_timestep_density != "uniform"):
         raise ValueError("--flow-shift / --flow-timestep-density belong to --objective flow")
@@ -312,13 +410,16 @@ def main(argv=None):
         if args.data_loader == "device":
             ds, loader = DeviceLatentDataset(args.data_path, dev, seed=args.seed), None
         else:
-            ds = LatentDataset(args.data_path)
+            ds = LatentDataset(args.data_path) if repa is None else RepaLatentDataset(args.data_path, args.repa_features)
             sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True, drop_last=True) if world > 1 else None
             loader = torch.utils.data.DataLoader(ds, batch_size=per_rank, num_workers=args.num_workers, shuffle=sampler is None,
                                                  sampler=sampler, pin_memory=True, drop_last=True)
         args.in_channels, args.input_size = ds.channels, ds.data_size
         args.stats_std = [float(v) for v in ds.stats["std"]]
         args.stats_mean = [float(v) for v in ds.stats["mean"]]
+        if repa is not None:                     # (host work: the file's header against the data set, before the model exists)
+            patch = int(args.model.split("/")[1])
+            repa = ("file", check_repa_features_file(args.repa_features, len(ds), (ds.data_size // patch) ** 2))
 
     exp = None
     if rank == 0:
@@ -361,10 +462,24 @@ def main(argv=None):
                        grad_scale=reducer.grad_scale if K == 1 else reducer.grad_scale / K,
                        max_grad_norm=args.max_grad_norm)
     reducer.attach(opt)
+    head = head_opt = feats_rng = None
+    if repa is not None:
+        # REPA: the projector and its own optimiser - outside --max-grad-norm, the model's EMA, state dict and snapshots
+        B = args.repa_depth if args.repa_depth is not None else (8 if model.depth >= 24 else 4)
+        if not 1 <= B <= model.depth - 1:
+            raise ValueError(f"--repa-depth {B}: the tap must lie after 1 .. depth - 1 = {model.depth - 1} blocks of {args.model}")
+        model.hidden_tap = B - 1
+        repa_tokens, repa_dim = (args.input_size // model.patch_size) ** 2, repa[1]
+        head = RepaHead(model.hidden_size, repa_dim, hidden=args.repa_hidden, precision=args.precision, seed=args.seed).to(dev)
+        head_opt = FusedAdamEMA(head, lr=args.repa_lr, betas=(0.9, 0.99), ema_stds=(),
+                                lr_lambda=create_lr_lambda(args.num_lin_warmup, args.start_decay), grad_scale=1.0 if K == 1 else 1.0 / K)
+        log(f"REPA: {sum(p.numel() for p in head.parameters()):,} projector parameters, hidden state after {B} blocks, {repa_tokens} x {repa_dim} features")
     # the default draws with torch.randint below, exactly as before; the sampler object exists only with the flag
     t_sampler = create_named_schedule_sampler(args.schedule_sampler, diffusion) if args.schedule_sampler != "uniform" else None
     # --step-rng counter: one launch per micro-batch draws everything random in it; no torch generator is consumed in a step
     step_rng = StepRNG(args.seed, dev) if args.step_rng == "counter" else None
+    if repa is not None and repa[0] == "synthetic" and step_rng is not None:
+        feats_rng = StepRNG(args.seed ^ 0x52455041, dev)       # a stream of its own: features of (seed, step, slot in the global batch)
     start_step = 0
     if resume is not None:
         state = resume["train_state"]
@@ -375,6 +490,10 @@ def main(argv=None):
             if "schedule_sampler" not in resume:
                 raise ValueError(f"--resume {resume_path}: the checkpoint has no 'schedule_sampler' key, the run samples with {args.schedule_sampler}")
             t_sampler.load_state_dict(resume["schedule_sampler"])
+        if head is not None:
+            head.load_state_dict(resume["repa_head"])
+            head_opt.load_state_dict(resume["repa_opt"]["opt"])
+            head_opt.load_resume_state_dict({"ema": {}, "guard": resume["repa_opt"]["guard"]})
         start_step = int(state["train_steps"])
         log(f"resuming from {resume_path} at step {start_step} (saved by {state['world_size']} rank(s))")
         if loader is not None:
@@ -403,15 +522,17 @@ def main(argv=None):
                 while True:
                     yield None, None
             g = torch.Generator(device=dev).manual_seed(args.seed + 1 + rank)
+            gf = torch.Generator(device=dev).manual_seed(args.seed + 2 + rank) if head is not None else None
             while True:
-                yield (torch.randn(per_rank, 4, args.input_size, args.input_size, device=dev, generator=g),
-                       torch.randint(0, args.num_classes, (per_rank,), device=dev, generator=g))
+                xy = (torch.randn(per_rank, 4, args.input_size, args.input_size, device=dev, generator=g),
+                      torch.randint(0, args.num_classes, (per_rank,), device=dev, generator=g))
+                yield xy if gf is None else xy + (torch.randn(per_rank, repa_tokens, repa_dim, device=dev, generator=gf),)
         epoch = start_step // max(len(loader), 1)      # (a continued run starts a fresh epoch order: the loader's position is not kept)
         while True:
             if world > 1:
                 loader.sampler.set_epoch(epoch)
-            for x, y in loader:
-                yield x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
+            for b in loader:
+                yield tuple(v.to(dev, non_blocking=True) for v in b)
             epoch += 1
 
     def counter_loss(xk, yk, k):
@@ -433,21 +554,41 @@ def main(argv=None):
         t = diffusion.timesteps_from_normals(d.z) if logit_normal else d.t
         return diffusion.training_losses(model, xk, t, kw, noise=d.eps.view(shape))["loss"].mean()
 
+    running_repa = torch.zeros((), device=dev)
+
+    def with_repa(base, f, k):
+        """base + --repa-coeff x the mean alignment loss of micro-batch k: the projector reads the hidden state the forward behind `base`
+        tapped, and its backward hands d loss / d hidden to the engine.  `f`: this rank's features of the step, or None (drawn here)."""
+        if head is None:
+            return base
+        if feats_rng is not None:
+            fk = feats_rng.draw(train_steps, first_slot(lo, k, micro), micro, per=repa_tokens * repa_dim, want=["eps"]).eps
+            fk = fk.view(micro, repa_tokens, repa_dim)
+        else:
+            fk = f[k * micro:(k + 1) * micro]
+        term = head.loss(model.tapped_hidden, fk).mean()
+        running_repa.add_(term.detach() / K)
+        return base + args.repa_coeff * term
+
     train_steps, log_steps, running, start = start_step, 0, torch.zeros((), device=dev), time()
     if resume_path is not None:                  # the log accumulators: a checkpoint may fall between two log lines
         log_steps = int(state["log_steps"])
         running.fill_(float(state["running"]))
+        running_repa.fill_(float(state.get("running_repa", 0.0)))
     if train_steps >= args.num_steps:
         log(f"nothing to do: the checkpoint is at step {train_steps}, --num-steps is {args.num_steps}")
         return exp
     log(f"training for {args.num_steps} steps...")
-    for x, y in batches():
+    for batch in batches():
+        x, y, f = batch[0], batch[1], (batch[2] if len(batch) > 2 else None)
+        if head_opt is not None:
+            head_opt.zero_grad()
         if step_rng is not None:
             opt.zero_grad()
             loss = torch.zeros((), device=dev)
             for k in range(K):
                 sl = slice(k * micro, (k + 1) * micro)
-                part = counter_loss(None if x is None else x[sl], None if y is None else y[sl], k)
+                part = with_repa(counter_loss(None if x is None else x[sl], None if y is None else y[sl], k), f, k)
                 with (reducer.no_sync() if k < K - 1 else contextlib.nullcontext()):
                     part.backward()
                 loss = loss + part.detach()
@@ -458,6 +599,7 @@ def main(argv=None):
                 loss = diffusion.training_losses(model, x, t, dict(y=y))["loss"].mean()
             else:
                 loss = weighted_loss(x, y)
+            loss = with_repa(loss, f, 0)
             opt.zero_grad()
             loss.backward()
         else:
@@ -472,12 +614,15 @@ def main(argv=None):
                     part = diffusion.training_losses(model, xk, t, dict(y=yk))["loss"].mean()    # NOT divided by K: see grad_scale above
                 else:
                     part = weighted_loss(xk, yk)
+                part = with_repa(part, f, k)
                 with (reducer.no_sync() if k < K - 1 else contextlib.nullcontext()):
                     part.backward()
                 loss = loss + part.detach()
             loss = loss / K
         reducer.finish()
         opt.step()
+        if head_opt is not None:
+            head_opt.step()
         running += loss.detach()
         log_steps += 1
         train_steps += 1
@@ -495,7 +640,14 @@ def main(argv=None):
             clip_msg = ""
             if args.max_grad_norm is not None:   # the values of this step: one read-back per log line
                 clip_msg = ", grad norm: {:.4f}, clip: {:.3f}".format(*opt.clip_values())
-            log(f"(step={train_steps:07d}) train loss: {avg.item():.4f}, train steps/sec: {sps:.2f}{clip_msg}")
+            repa_msg = ""
+            if head is not None:
+                if head_opt.poll_overflow():
+                    log(f"(step={train_steps:07d}) projector step(s) refused: non-finite gradients; its fp16 loss scale now "
+                        f"{head.loss_scale or head.effective_loss_scale():g}")
+                repa_msg = ", repa: {:.4f}".format((running_repa / log_steps).item())
+                running_repa.zero_()
+            log(f"(step={train_steps:07d}) train loss: {avg.item():.4f}, train steps/sec: {sps:.2f}{clip_msg}{repa_msg}")
             running.zero_()
             log_steps, start = 0, time()
         if train_steps % args.ckpt_every == 0 or (args.ema_snapshot_every and train_steps % args.ema_snapshot_every == 0):
@@ -504,6 +656,9 @@ def main(argv=None):
             ckpt = {"model": model.state_dict(), "opt": opt.state_dict()}                      # reference train.py:125-132
             if t_sampler is not None:
                 ckpt["schedule_sampler"] = t_sampler.state_dict()
+            if head is not None:
+                ckpt["repa_head"] = head.state_dict()
+                ckpt["repa_opt"] = {"opt": head_opt.state_dict(), "guard": head_opt.resume_state_dict()["guard"]}
             if step_rng is not None:
                 # what --resume needs beyond the reference's keys: the fp32 EMA copies (the snapshots are fp16) and the loop's own state.
                 # (The default run's checkpoint stays the reference's, key for key.)
@@ -511,6 +666,8 @@ def main(argv=None):
                 ckpt["ema"] = rs["ema"]
                 ckpt["train_state"] = {"train_steps": train_steps, "running": running.item(), "log_steps": log_steps, "guard": rs["guard"],
                                        "step_rng": args.step_rng, "seed": args.seed, "world_size": world}
+                if head is not None:
+                    ckpt["train_state"]["running_repa"] = running_repa.item()
             torch.save(ckpt, os.path.join(exp, "checkpoints", f"{train_steps:07d}.pt"))
         if rank == 0 and args.ema_snapshot_every and train_steps % args.ema_snapshot_every == 0:
             for std in opt.ema_stds:                                   # reference src/ema.py:143-155
