@@ -136,6 +136,32 @@ void mapdit_gemm_tuning(int tile, int phases, long band);
  * (edge tiles, K tails).  mapdit_gemm_dma_extent_ok: rows x ld x 2 bytes of an operand fit an unsigned 32-bit byte offset. */
 int mapdit_gemm_dma_fast(int layout, int M, int N, int K, int lda, int ldb, int tile);
 int mapdit_gemm_dma_extent_ok(long rows, long ld);
+/* What the dispatcher decided for the most recent mapdit_gemm_* / mapdit_gemm_group_tn_* call of the CALLING THREAD (host logic, no GPU
+ * call: it launches nothing and changes no decision; additive within abi 5).  A test asks it which kernel served its call, so that a
+ * change of the tile rule cannot quietly take a test off the path it was written for.  mapdit_gemm_last_plan copies the record out and
+ * returns MAPDIT_OK; MAPDIT_ERR_ARG for a null `out`.  A call that was refused before any launch leaves family = MAPDIT_GEMM_NONE.
+ *   family      which kernel: the scalar fallback (gemm_simple_kernel), the 128 x 128 kernel, its 64-row form (64 x 128 tiles), the
+ *               256 x 256 kernel with the shared fp32 epilogue image, the 256 x 256 kernel with the wave-private epilogue, the group kernel
+ *   tile        rows of an output tile: 0 (scalar), 64, 128, 256
+ *   ktail       the instantiation with the zero-sourced K tail (K % 64 != 0)
+ *   fast        LDS-DMA from a scalar base and 32-bit lane offsets (mapdit_gemm_dma_fast held and no K tail)
+ *   fe          the straight-line epilogue of the shared-image 256 x 256 kernel (RESID: interior tiles, each inside one sample)
+ *   split_k     slabs of the K cut (1: none)
+ *   grid, tiles workgroups launched; output tiles (x split_k = units of work).  persistent: grid < tiles * split_k, each workgroup loops
+ *   stagger     start offset units of every second workgroup of a persistent launch (RESID: 2), band: column tiles per band of the tile order
+ *   col_split   the result was cut at column N - 128: everything above describes the launch on the first N - 128 columns, family2 is
+ *               the kernel of the launch on the last 128 (MAPDIT_GEMM_NONE without a split) */
+enum { MAPDIT_GEMM_NONE = 0, MAPDIT_GEMM_SCALAR = 1, MAPDIT_GEMM_128 = 2, MAPDIT_GEMM_64ROW = 3, MAPDIT_GEMM_256_SHARED = 4,
+       MAPDIT_GEMM_256_WAVE = 5, MAPDIT_GEMM_GROUP = 6 };
+typedef struct {
+    int family, tile;
+    int ktail, fast, fe;
+    int split_k;
+    int grid, tiles, persistent;
+    int stagger, band;
+    int col_split, family2;
+} mapdit_gemm_plan_t;
+int mapdit_gemm_last_plan(mapdit_gemm_plan_t* out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Weight normalisation of MPLinear / MPLinearChunk / MPEmbedding (src/utils.py:19-34, mp_linear.py:38-44,66-74,

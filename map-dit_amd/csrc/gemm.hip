@@ -1904,9 +1904,18 @@ inline void with_operand_kinds(int layout, F&& f) {
     else f(Kmaj(), Kmaj());
 }
 
+// The record behind mapdit_gemm_last_plan (host only; switches.hip holds the thread's slot).  `second`: the launch on the last 128
+// columns of a column split - it adds col_split / family2 to the record of the first launch instead of replacing it.
+inline void record_plan(bool second, int family, int tile, bool ktail, bool fast, bool fe, int split_k, int grid, int tiles, int stagger, int band) {
+    mapdit_gemm_plan_t& pl = mapdit_gemm_plan_slot();
+    if (second) { pl.col_split = 1; pl.family2 = family; return; }
+    pl = mapdit_gemm_plan_t{family, tile, ktail, fast, fe, split_k, grid, tiles, grid < tiles * split_k, stagger, band, 0, MAPDIT_GEMM_NONE};
+}
+
 template <class Epi>
 int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16_t* B, int ldb, Epi epi,
            hipStream_t st, int split_k = 1, int n_off = 0, bool force128 = false) {
+    if (!force128) mapdit_gemm_plan_slot() = mapdit_gemm_plan_t{};       // (a refused call reports MAPDIT_GEMM_NONE)
     bool a_kmaj = false, b_kmaj = false;
     with_operand_kinds(layout, [&](auto ak, auto bk) { a_kmaj = ak.value == OP_KMAJ; b_kmaj = bk.value == OP_KMAJ; });
     // Round 4: a result whose width is an odd multiple of 128 (DiT-XL: 1152) on few enough rows that the 256^2 tiles of its first
@@ -2000,6 +2009,11 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
             fe = M % BM2 == 0 && N % BN2 == 0 && epi.fast_ok();
         // FAST: the K loop stages from a scalar base and one lane offset per operand (DmaCtx) - interior tiles only, never with a K tail
         const bool fast = mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 256);
+        {
+            const bool tail = kHasTail<Epi> && ktail;
+            record_plan(false, use_w ? MAPDIT_GEMM_256_WAVE : MAPDIT_GEMM_256_SHARED, 256, tail, fast && !tail, fe && !use_w && !tail, split_k,
+                        grid, p.tiles, p.stagger, p.band);
+        }
         auto go = [&](auto tail, auto fst) {
             constexpr bool TAIL = decltype(tail)::value, FAST = decltype(fst)::value;
             with_operand_kinds(layout, [&](auto ak, auto bk) {
@@ -2030,6 +2044,7 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
                 GemmP p{A, B, lda, ldb, M, N, K, cdiv(N, BN), 0, 1, 0, 4, n_off, 0};
                 p.tiles = cdiv(M, 64) * p.tiles_n;
                 const bool fast = mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 64);
+                record_plan(force128, MAPDIT_GEMM_64ROW, 64, false, fast, false, 1, p.tiles, p.tiles, 0, 0);
                 with_operand_kinds(layout, [&](auto, auto bk) {       // (A is row-major here)
                     if (fast) hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi, true>), dim3(p.tiles), dim3(256), 0, st, p, epi);
                     else hipLaunchKernelGGL((gemm_mfma64_kernel<bk.value, Epi>), dim3(p.tiles), dim3(256), 0, st, p, epi);
@@ -2041,6 +2056,8 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
         GemmP p{A, B, lda, ldb, M, N, K, cdiv(N, BN), 0, split_k, 0, 4, n_off, 0};
         p.tiles = cdiv(M, BM) * p.tiles_n;
         const int grid = p.tiles * split_k;
+        const bool fast = !(kHasTail<Epi> && ktail) && mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 128);
+        record_plan(force128, MAPDIT_GEMM_128, 128, kHasTail<Epi> && ktail, fast, false, split_k, grid, p.tiles, 0, 0);
         if constexpr (kHasTail<Epi>) {
             if (ktail) {
                 with_operand_kinds(layout, [&](auto ak, auto bk) {
@@ -2050,7 +2067,6 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
                 return MAPDIT_OK;
             }
         }
-        const bool fast = mapdit_gemm_dma_fast(layout, M, N, K, lda, ldb, 128);
         with_operand_kinds(layout, [&](auto ak, auto bk) {
             if (fast) hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi, false, true>), dim3(grid), dim3(256), 0, st, p, epi);
             else hipLaunchKernelGGL((gemm_mfma_kernel<ak.value, bk.value, Epi>), dim3(grid), dim3(256), 0, st, p, epi);
@@ -2063,6 +2079,7 @@ int launch(int layout, int M, int N, int K, const bf16_t* A, int lda, const bf16
         const long sam = a_kmaj ? 1 : lda, sak = a_kmaj ? lda : 1;
         const long sbn = b_kmaj ? 1 : ldb, sbk = b_kmaj ? ldb : 1;
         const long total = (long)M * (N >> 3);
+        record_plan(false, MAPDIT_GEMM_SCALAR, 0, false, false, false, 1, cdiv(total, 256), 0, 0, 0);
         hipLaunchKernelGGL((gemm_simple_kernel<Epi>), dim3(cdiv(total, 256)), dim3(256), 0, st, A, sam, sak, B, sbn, sbk, M, N, K, epi);
     }
     MD_LAUNCH_CHECK();
@@ -2075,6 +2092,7 @@ MD_NS_CLOSE
 // 256^2 kernel (gemm_mfma256_group_kernel).  Every item must be on the MFMA path (K % 64 == 0, M_i, N_i, lda_i, ldb_i multiples of 8,
 // 16-byte aligned operands); the same accumulation order as a single launch with the same split_k: the same bits.
 extern "C" int MD_SYM_GEMM_GROUP(int n, const mapdit_gemm_group_item_t* items, int K, int split_k, void* stream) {
+    mapdit_gemm_plan_slot() = mapdit_gemm_plan_t{};
     MD_CHECK(items && n >= 1 && n <= GROUP_MAX, "gemm_group: 1..%d items", GROUP_MAX);
     MD_CHECK(K > 0 && K % BKT == 0 && split_k >= 1 && split_k <= K / BKT, "gemm_group: K=%d must be a multiple of 64 and split_k=%d <= K / 64", K, split_k);
     GroupArgs g{};
@@ -2098,6 +2116,7 @@ extern "C" int MD_SYM_GEMM_GROUP(int n, const mapdit_gemm_group_item_t* items, i
         fast = fast && mapdit_gemm_dma_fast(MAPDIT_TN, it.M, it.N, K, it.lda, it.ldb, 256);
     }
     // (one kernel for the whole group: the scalar-base staging only if every item qualifies)
+    mapdit_gemm_plan_slot() = mapdit_gemm_plan_t{MAPDIT_GEMM_GROUP, 256, 0, fast, 0, split_k, g.first[n], g.first[n] / split_k, 0, 0, g.p[0].band, 0, MAPDIT_GEMM_NONE};
     if (fast) hipLaunchKernelGGL(gemm_mfma256_group_kernel<true>, dim3(g.first[n]), dim3(512), 0, (hipStream_t)stream, g);
     else hipLaunchKernelGGL(gemm_mfma256_group_kernel<false>, dim3(g.first[n]), dim3(512), 0, (hipStream_t)stream, g);
     MD_LAUNCH_CHECK();
@@ -2106,6 +2125,7 @@ extern "C" int MD_SYM_GEMM_GROUP(int n, const mapdit_gemm_group_item_t* items, i
 
 extern "C" int MD_SYM_GEMM(int layout, int M, int N, int K, const uint16_t* A, int lda, const uint16_t* B,
                                 int ldb, const mapdit_epilogue_t* e, void* stream) {
+    mapdit_gemm_plan_slot() = mapdit_gemm_plan_t{};       // (a call refused below reports MAPDIT_GEMM_NONE)
     MD_CHECK(layout >= MAPDIT_NT && layout <= MAPDIT_TN, "gemm: bad layout %d", layout);
     MD_CHECK(M > 0 && N > 0 && K > 0 && A && B && e, "gemm: null/empty argument (M=%d N=%d K=%d)", M, N, K);
     MD_CHECK(e->out || e->kind == MAPDIT_EPI_SILU2 || e->kind == MAPDIT_EPI_SILU2_COND || e->kind == MAPDIT_EPI_RESID ||

@@ -4,6 +4,8 @@
 // tuning hook, tile-size rule, DMA-staging predicates).
 #pragma once
 
+#include "../../include/mapdit.h"
+
 struct MapditSwitches {
     // The three fields mapdit_gemm_tuning sets (it overrides what the environment said):
     // MAPDIT_GEMM_TILE = 128 | 256: force the tile edge of every MFMA launch (0: by shape, mapdit_gemm_tile_size_k)
@@ -33,3 +35,7 @@ struct MapditSwitches {
 
 // The one instance.  Not for writing while launches are in flight elsewhere.
 MapditSwitches& mapdit_switches();
+
+// The calling thread's record of what the GEMM dispatcher last decided (mapdit_gemm_last_plan reads it; gemm.hip's launch() and the
+// group entry point write it).  One slot for both operand formats.
+mapdit_gemm_plan_t& mapdit_gemm_plan_slot();

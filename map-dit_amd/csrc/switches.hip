@@ -47,6 +47,18 @@ extern "C" void mapdit_gemm_tuning(int tile, int phases, long band) {
     s.gemm_band = band;
 }
 
+// ---- which kernel served the last GEMM call ----------------------------------------------------------------
+// Written by the dispatcher (gemm.hip launch(), the group entry point) on the host, per thread; no kernel, no effect on any decision.
+mapdit_gemm_plan_t& mapdit_gemm_plan_slot() {
+    static thread_local mapdit_gemm_plan_t plan = {};
+    return plan;
+}
+extern "C" int mapdit_gemm_last_plan(mapdit_gemm_plan_t* out) {
+    MD_CHECK(out, "gemm_last_plan: null output");
+    *out = mapdit_gemm_plan_slot();
+    return MAPDIT_OK;
+}
+
 // ---- the tile edge of a GEMM launch ----------------------------------------------------------------------
 // Output tile edge the dispatcher uses for an [M, N] result.  Exposed so callers can size split-K.
 // 256 (8 waves, one workgroup per CU) for results that give most of the chip a tile, 128 (4 waves, two per CU) otherwise:

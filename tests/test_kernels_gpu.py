@@ -90,15 +90,20 @@ def run_gemm(L, layout, a, b, kind, M, N, K, **kw):
 @pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("shape", [(128, 128, 64), (256, 384, 128), (200, 136, 192), (1024, 768, 768), (77, 32, 64),
                                    (64, 24, 256), (8, 128, 32), (130, 128, 8),
-                                   # 256x256 staggered kernel (M >= 512, N >= 256): 1..7 K-tiles, ragged edges
+                                   # M >= 512, N >= 256 but fewer than 128 tiles of 256^2 (the largest: 96): the 128^2 kernel under
+                                   # today's tile rule (mapdit_gemm_tile_size_k); 1..12 K-tiles, ragged edges
                                    (512, 256, 64), (512, 256, 128), (768, 512, 192), (600, 264, 448), (2048, 3072, 768),
-                                   # K not a multiple of the 64-deep K-tile (zero-sourced tail): both MFMA kernels
+                                   # K not a multiple of the 64-deep K-tile (zero-sourced tail): the 128^2 kernel
                                    (512, 256, 32), (640, 384, 96), (1024, 768, 200), (96, 64, 40), (4608, 768, 32),
                                    # K % 8 != 0: the scalar fallback
-                                   (64, 32, 12)])
+                                   (64, 32, 12),
+                                   # the 256^2 kernel by the tile rule (128 and 160 tiles), asserted through mapdit_gemm_last_plan:
+                                   # interior, with a K tail, ragged both ways with a K tail (a fourth entry: the kernel family the
+                                   # shape was added for)
+                                   (8192, 1024, 64, "256_SHARED"), (8192, 1024, 200, "256_SHARED"), (8136, 1032, 96, "256_SHARED")])
 def test_gemm_layouts(L, layout, shape):
     """C = A B^T in the three storage layouts, incl. ragged M/N, K tails (K % 64 != 0) and the non-MFMA fallback (K % 8 != 0)."""
-    M, N, K = shape
+    M, N, K, *family = shape
     if layout == 2 and M % 8:
         pytest.skip("TN needs M % 8 == 0 (rows of the K-major operand are 16-byte chunks)")
     A = bf16_exact(M, K, seed=1)
@@ -108,6 +113,11 @@ def test_gemm_layouts(L, layout, shape):
     b = to_bf(B if layout == 0 else B.t())
     out = torch.full((M, N), float("nan"), device=DEV)
     run_gemm(L, layout, a, b, L.EPI_STORE_F32, M, N, K, out=p(out), ldo=N, alpha=1.0)
+    if family:             # a shape added for one kernel: that kernel served it (STORE_F32: the shared-image form), with the K tail where there is one
+        pl = L.GemmPlan()
+        L.lib().gemm_last_plan(C.byref(pl))
+        interior = M % 256 == 0 and N % 256 == 0 and K % 64 == 0
+        assert (pl.family, pl.tile, pl.ktail, pl.fast, pl.col_split) == (getattr(L, "GEMM_" + family[0]), 256, int(K % 64 != 0), int(interior), 0)
     assert rel_err(out.cpu().numpy(), ref.numpy()) < 2e-6
     assert float((out.cpu().double() - ref).abs().max()) < 1e-3
 
@@ -316,6 +326,12 @@ def test_gemm_epilogues(L):
     run_gemm(L, 0, a, b, L.EPI_SILU2, M, N, K, out=p(pre), out2=p(act), ldo=N)
     assert rel_err(pre.float().cpu().numpy(), acc.numpy()) < 3e-3
     assert rel_err(act.float().cpu().numpy(), (torch.nn.functional.silu(acc) / 0.596).numpy()) < 3e-3
+    # the same functor under the conditioning MLP's kernel symbol: the same bits
+    pre_c, act_c = torch.zeros_like(pre), torch.zeros_like(pre)
+    run_gemm(L, 0, a, b, L.EPI_SILU2_COND, M, N, K, out=p(pre_c), out2=p(act_c), ldo=N)
+    assert rel_err(pre_c.float().cpu().numpy(), acc.numpy()) < 3e-3
+    assert rel_err(act_c.float().cpu().numpy(), (torch.nn.functional.silu(acc) / 0.596).numpy()) < 3e-3
+    assert torch.equal(pre_c, pre) and torch.equal(act_c, act)
     # silu2 with the derivative factor instead of the pre-activation, and the product epilogue that consumes it
     dfac = torch.zeros_like(pre)
     act2 = torch.zeros_like(pre)
